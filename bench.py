@@ -1,7 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- ADMM iterations/sec on the BASELINE.json workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, warm-up, EXACTLY K
+timed steps, the outputs of the last step if --dump-outputs is given, one JSON
+line.  Warm-up = a second handle of the same problem iterating until
+--warm-seconds of wall time have gone by (steady clocks), then W steps on the
+timed handle; so the timed steps compute, for given arguments, the same thing on
+every run: the state after W + K iterations from the set-up state.  The inputs
+are seeded.  Everything else below (per-kernel rooflines, CPU
+baseline, configs[4], precision modes, iterations-to-epsilon, the repeated-block
+timing) runs only with --full.
 
 Workload (config.workload): BASELINE.json configs[2] -- a batch of 4096
 independent N=1000, n=6, m=3 Clohessy-Wiltshire rendezvous QPs per GPU, fp64,
@@ -20,7 +30,7 @@ kernel, i.e. every iteration evaluates the residuals on the device
 `value` = QP-iterations/s summed over all ranks.  (`plain_path` re-times the
 same steps with ADMM_FLAG_NO_ALTERNATE: xb + xscan + xfz + finalise.)
 
-Extra objects on the JSON line:
+Extra objects on the JSON line with --full:
   roofline     -- the dominant kernels, the pair xfze<RESID> / xbze<RESID>: each
                   moves 16 + 16 m/(n+m) = 21.33 B per stacked element (d, v read
                   and v+, db written, resp. db, v read and v+, d written; fp64,
@@ -66,18 +76,25 @@ def parse():
                          "ADMM_FLAG_NO_MFMA; fp64_mfma / mixed = the MFMA forms (configs[4]; compiled for n=12 m=6, n=6 m=3, n=10 m=4)")
     ap.add_argument("--segments", type=int, default=0)
     ap.add_argument("--zrows", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every side measurement and check (per-kernel rooflines, CPU baseline, configs[4], "
+                         "precision modes, iterations-to-epsilon, repeated-block timing); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step computed as DIR/<name>.npy (float64): w, z, y and "
+                         "the residual norms r, s, norm_w, norm_z, norm_y of a fixed, seeded sample of QPs (at most 64 MB)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="timed blocks of --steps steps each; the median block is reported (all blocks are listed)")
+                    help="--full: timed blocks of --steps steps each after the headline; the median block is reported "
+                         "(all blocks are listed)")
     ap.add_argument("--warm-seconds", type=float, default=0.6,
-                    help="after the --warmup steps, keep iterating until at least this much wall time has been spent "
-                         "warming up, so that the timed region runs at steady clocks however small --warmup is")
+                    help="before the --warmup steps, keep iterating until at least this much wall time has been spent "
+                         "warming up, so that the timed steps run at steady clocks however small --warmup is")
     ap.add_argument("--min-timed-seconds", type=float, default=1.0,
-                    help="the timed region (all blocks of the headline leg together) spans at least this long: the number of "
-                         "blocks is raised beyond --repeats as needed, each block stays EXACTLY --steps steps")
+                    help="--full: the repeated-block leg spans at least this long: the number of blocks is raised beyond "
+                         "--repeats as needed, each block stays EXACTLY --steps steps")
     ap.add_argument("--profile-launches", type=int, default=200,
                     help="launches of each kernel averaged by the HIP-event per-kernel timing (admm_profile)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs4", action="store_true", help="skip the compact configs[4] side object of the default line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-configs4", action="store_true", help="--full: skip the compact configs[4] side object")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     return ap.parse_args()
 
@@ -225,18 +242,65 @@ def launch_ranks(a):
     raise SystemExit(rc)
 
 
+def headline(sv, make_solver, a, barrier, max_over_ranks, chunk):
+    """The reported timing of the fresh handle `sv`: a second handle of the same problem (make_solver()) iterates in `chunk`-step
+    pieces for --warm-seconds (steady clocks, kernels loaded), then `sv` runs the --warmup steps and EXACTLY --steps timed steps
+    with residuals every step, bracketed by barrier + synchronize and reduced with MAX over the ranks.  `sv` starts from its
+    set-up state, so what the timed steps compute depends on the arguments alone.  Returns seconds."""
+    with make_solver() as warm_sv:
+        t_end = time.perf_counter() + a.warm_seconds
+        while time.perf_counter() < t_end:
+            warm_sv.run(chunk, residual_every=1, sync=True)
+        sv.run(a.warmup, residual_every=1, sync=True)
+        barrier()
+        t0 = time.perf_counter()
+        sv.run(a.steps, residual_every=1, sync=True)
+        barrier()
+        elapsed = time.perf_counter() - t0
+    return max_over_ranks(elapsed)
+
+
+DUMP_BYTES = 60e6       # --dump-outputs: at most this much (< 64 MB) for all arrays together
+
+
+def dump_outputs(directory, sv, np):
+    """--dump-outputs: what the last timed step computed, as a caller of admm_run / admm_get / admm_get_residuals receives it --
+    the state w, z, y (batch x L) and the residual norms r, s, norm_w, norm_z, norm_y of that step (batch) -- for a fixed sample
+    of this rank's QPs (seed 0, sorted; all of them when they fit in DUMP_BYTES), each as <directory>/<name>.npy in float64."""
+    os.makedirs(directory, exist_ok=True)
+    state = sv.get()
+    norms = sv.residuals()
+    k = min(sv.batch, max(1, int(DUMP_BYTES // (8 * (3 * sv.L + 5)))))
+    idx = np.arange(sv.batch) if k == sv.batch else np.sort(np.random.default_rng(0).choice(sv.batch, k, replace=False))
+    names = ("w", "z", "y", "r", "s", "norm_w", "norm_z", "norm_y")
+    for name, arr in zip(names, state + norms):
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr[idx], np.float64))
+
+
 def bench_perinstance(a, pkg, np, world, rank, dev_index, lo_i, hi_i, gbatch, barrier, max_over_ranks):
     """SIDE MEASUREMENT: per-instance dynamics (admm_problem.time_varying = 2, stage_bounds = 2).  A different
     roofline from the metric's: every QP streams its own factor operands, ~200 B per stacked element and iteration."""
     make = pkg.cw_formation_instances if a.workload == "cw_formation_perinstance" else pkg.cw_rendezvous_instances
     full = make(N=a.horizon, batch=hi_i - lo_i, seed0=pkg.SEED0 + lo_i)
     n_, m_, nb = full.n, full.m, full.nb
-    with pkg.Solver(full, pkg.Options(rho=0.05, check_interval=1, segments=a.segments, device=dev_index)) as sv:
+    opt = pkg.Options(rho=0.05, check_interval=1, segments=a.segments, device=dev_index)
+    with pkg.Solver(full, opt) as sv:
         geo = sv.geometry()
-        sv.run(max(a.warmup, 3), residual_every=1)
-        t_end = time.perf_counter() + a.warm_seconds
-        while time.perf_counter() < t_end:
-            sv.run(10, residual_every=1, sync=True)
+        dt = headline(sv, lambda: pkg.Solver(full, opt), a, barrier, max_over_ranks, chunk=10)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, sv, np)
+        line = {
+            "metric": "ADMM iterations/sec (fp64), per-instance dynamics (SIDE MEASUREMENT, not BASELINE's metric)",
+            "value": gbatch * a.steps / dt, "unit": "QP-iterations/s", "batch_iterations_per_s": a.steps / dt,
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"SIDE MEASUREMENT ({a.workload}): batch of {a.batch} N={a.horizon} n={n_} m={m_} QPs per GPU, "
+                                   f"every QP with its own dynamics and box (time_varying = 2, stage_bounds = 2), residuals every iteration",
+                       "N": a.horizon, "n": n_, "m": m_, "batch_per_gpu": a.batch, "global_batch": gbatch, **geo}}
+        if not a.full:
+            if rank == 0:
+                print(json.dumps(line))
+            return
         blocks = []
         for _ in range(a.repeats):
             barrier()
@@ -264,7 +328,7 @@ def bench_perinstance(a, pkg, np, world, rank, dev_index, lo_i, hi_i, gbatch, ba
             check = {"qps": [int(i) for i in idx], "iterations": 8, "max_abs_difference_w_z_y": err}
             if not err <= 1e-9:
                 raise SystemExit(f"bench.py: the HIP path disagrees with the oracle on the sampled QPs: {check}")
-    dt = float(np.median(blocks))
+    dtb = float(np.median(blocks))
     elems = full.L * geo["pitch"]
     seg_ops = n_ * m_ * 8.0 / nb if geo["segments"] > 1 else 0.0        # Omega_k (backward) / Psi_k (forward) with segments in time
     ops_b = (n_ * n_ + n_ * m_ + m_ * n_ + m_ * m_) * 8.0 / nb + seg_ops   # A, B, K, Si per stage -> per stacked element
@@ -275,13 +339,8 @@ def bench_perinstance(a, pkg, np, world, rank, dev_index, lo_i, hi_i, gbatch, ba
     ach = (b_xb + b_xfz) * elems / (ms * 1e-3) / 1e9
     if rank == 0:
         print(json.dumps({
-            "metric": "ADMM iterations/sec (fp64), per-instance dynamics (SIDE MEASUREMENT, not BASELINE's metric)",
-            "value": gbatch * a.steps / dt, "unit": "QP-iterations/s", "batch_iterations_per_s": a.steps / dt,
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "repeats": a.repeats, "ms_per_step": dt / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"SIDE MEASUREMENT ({a.workload}): batch of {a.batch} N={a.horizon} n={n_} m={m_} QPs per GPU, "
-                                   f"every QP with its own dynamics and box (time_varying = 2, stage_bounds = 2), residuals every iteration",
-                       "N": a.horizon, "n": n_, "m": m_, "batch_per_gpu": a.batch, "global_batch": gbatch, **geo},
+            **line,
+            "repeats": a.repeats, "ms_per_step_blocks_median": dtb / a.steps * 1e3,
             "roofline": {"kernel": ("pxb_rows_kernel + pxfz_rows_kernel (a QP's rows over the lanes of a wave; operands per QP from HBM)"
                                     if n_ >= 8 else "pxb_kernel + pxfz_kernel (one lane per QP; operands per QP from HBM)"),
                          "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
@@ -317,7 +376,7 @@ def main():
     # ~15 s of host work between the GPU legs would leave the GPU at idle clocks for whatever is timed next (r01: the
     # driver's 3.3 ms timed region ran on a 0.8 %-busy GPU).
     cpu_base = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu_base = cpu_baseline(a.horizon, a.cpu_seconds, a.workload)
     if pkg.device_count() < 1:
         raise SystemExit("bench.py: no HIP device visible; the solver has no CPU fallback")
@@ -389,15 +448,47 @@ def main():
             out.append(max_over_ranks(time.perf_counter() - t0))
         return out
 
-    solver.run(a.warmup, residual_every=1)          # the W untimed warmup steps ...
-    warm(solver, a.warm_seconds)                    # ... and then by time, whatever W was
+    dt = headline(solver, lambda: pkg.Solver(full, opt), a, barrier, max_over_ranks, chunk=200)
+    ms_per_step = dt / a.steps * 1e3
+    value = gbatch * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, solver, np)
+    n_, m_ = full.n, full.m
+    line = {
+        "metric": "ADMM iterations/sec (fp64) at N=1000 n=6 batch=4096",
+        "value": value, "unit": "QP-iterations/s",
+        "batch_iterations_per_s": a.steps / dt,
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
+        "timing": (f"one block of exactly {a.steps} steps bracketed by barrier + synchronize, reduced with MAX over ranks; "
+                   f"warm-up = {a.warm_seconds} s of iterations on a second handle, then {a.warmup} steps"),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64" if a.precision != "mixed" else "f64 state + f32/f64 x-update (mixed)", "data": "synthetic",
+        "config": {"workload": (f"configs[2]: batch of {a.batch} independent N={a.horizon} n=6 m=3 "
+                                f"Clohessy-Wiltshire QPs per GPU, residuals every iteration")
+                   if a.workload == "cw_rendezvous" else
+                   (f"configs[4]: x-update as MFMA batched GEMM ({a.precision}), batch of {a.batch} N={a.horizon} n={n_} m={m_} "
+                    f"Clohessy-Wiltshire formation QPs per GPU, residuals every iteration" if a.workload == "cw_formation" else
+                    f"SIDE MEASUREMENT ({a.workload}, {a.precision}): batch of {a.batch} N={a.horizon} n={n_} m={m_} "
+                    f"Clohessy-Wiltshire QPs per GPU, residuals every iteration"),
+                   "N": a.horizon, "n": n_, "m": m_, "batch_per_gpu": a.batch, "global_batch": gbatch,
+                   "rho": 0.05, "sharding": f"batch/{world}, no collective in the iteration",
+                   **geo, "path": path},
+        "precision": a.precision,
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line))
+        solver.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # --full from here on: the same path timed again as the median of repeated blocks, then every side measurement
     t_region = time.perf_counter()
     blocks = timed_blocks(solver, 1, a.min_timed_seconds)
     t_region = time.perf_counter() - t_region
-    dt = float(np.median(blocks))
-
-    ms_per_step = dt / a.steps * 1e3
-    value = gbatch * a.steps / dt
+    dtb = float(np.median(blocks))
 
     # per-kernel timing on the library's stream (HIP events)
     npf = max(1, min(a.profile_launches, 4096))     # launches of each kernel, regardless of --steps
@@ -415,7 +506,6 @@ def main():
     prof_unf = solver.profile(npf, residuals=True, fused=False)      # standalone z/dual kernel
     L = full.L
     elems = L * geo["pitch"]
-    n_, m_ = full.n, full.m
     uses_mfma = path["kernel_family"] != "one_lane_fp64"      # reported by the library, not re-derived here
     b_xfz = 8.0 * m_ / (n_ + m_) + 16.0          # d read + v read + v+ written
     xfz_ms = prof["xfz_ms"]
@@ -639,31 +729,15 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "ADMM iterations/sec (fp64) at N=1000 n=6 batch=4096",
-            "value": value, "unit": "QP-iterations/s",
-            "batch_iterations_per_s": a.steps / dt,
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_per_step,
+            **line,
             "repeats": len(blocks), "timed_region_s": t_region, "timed_steps_total": len(blocks) * a.steps,
-            "ms_per_step_blocks": {"min": min(blocks) / a.steps * 1e3, "median": dt / a.steps * 1e3, "max": max(blocks) / a.steps * 1e3,
+            "ms_per_step_blocks": {"min": min(blocks) / a.steps * 1e3, "median": dtb / a.steps * 1e3, "max": max(blocks) / a.steps * 1e3,
                                    "first": [b / a.steps * 1e3 for b in blocks[:5]]},
-            "timing": (f"median of {len(blocks)} blocks of exactly {a.steps} steps (>= {a.repeats}, as many as it takes to time "
-                       f">= {a.min_timed_seconds} s), each bracketed by barrier + synchronize and reduced with MAX over ranks; "
-                       f"warm-up = {a.warmup} steps + {a.warm_seconds} s"),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64" if a.precision != "mixed" else "f64 state + f32/f64 x-update (mixed)", "data": "synthetic",
-            "config": {"workload": (f"configs[2]: batch of {a.batch} independent N={a.horizon} n=6 m=3 "
-                                    f"Clohessy-Wiltshire QPs per GPU, residuals every iteration")
-                       if a.workload == "cw_rendezvous" else
-                       (f"configs[4]: x-update as MFMA batched GEMM ({a.precision}), batch of {a.batch} N={a.horizon} n={n_} m={m_} "
-                        f"Clohessy-Wiltshire formation QPs per GPU, residuals every iteration" if a.workload == "cw_formation" else
-                        f"SIDE MEASUREMENT ({a.workload}, {a.precision}): batch of {a.batch} N={a.horizon} n={n_} m={m_} "
-                        f"Clohessy-Wiltshire QPs per GPU, residuals every iteration"),
-                       "N": a.horizon, "n": n_, "m": m_, "batch_per_gpu": a.batch, "global_batch": gbatch,
-                       "rho": 0.05, "sharding": f"batch/{world}, no collective in the iteration",
-                       **geo, "path": path},
+            "timing_blocks": (f"after the headline: median of {len(blocks)} blocks of exactly {a.steps} steps (>= {a.repeats}, as many "
+                              f"as it takes to time >= {a.min_timed_seconds} s), each bracketed by barrier + synchronize and reduced "
+                              f"with MAX over ranks"),
             "roofline": roofline if roofline_mfma is None else roofline_mfma,
             "roofline_hbm": None if roofline_mfma is None else roofline,
-            "precision": a.precision,
             "configs4": configs4,
             "precision_modes": precision_modes,
             "iters_to_eps_precision_modes": iters_to_eps_modes,

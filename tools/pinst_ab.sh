@@ -3,6 +3,7 @@
 cd "$(dirname "$0")/.."
 set -- $1 "${@:2}"
 b=$1; n=$2; v=$3; shift 3
+set -- --full "$@"        # the line read below carries the roofline: a --full figure
 [ "$v" != "-" ] && export ADMM_HIP_LIB=$PWD/variants/libadmm_hip_$v.so
 timeout -k 10 280 python bench.py --workload cw_formation_perinstance --batch $b --horizon $n --no-cpu-baseline "$@" 2> gpurun_out/ab_$v.err | tail -n1 > gpurun_out/ab_$v.json
 python - <<PY

@@ -2,6 +2,7 @@
 # Build libadmm_hip.so variants on the GPU box and bench each (A/B of tuning constants).
 # usage: tools/variant_sweep.sh "<name>:<-D flags>" ...
 set -e
+BENCH_ARGS="--full $BENCH_ARGS"        # the figures read below (kernels_ms, check_interval_10) are --full ones
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out/variants
 for spec in "$@"; do
