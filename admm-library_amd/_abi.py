@@ -12,7 +12,7 @@ import numpy as np
 
 from .problems import Problem
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 ADMM_OK = 0
 STATUS_NAMES = {0: "ADMM_OK", 1: "ADMM_ERR_INVALID", 2: "ADMM_ERR_UNSUPPORTED",
@@ -124,6 +124,28 @@ def marshal_problem(p: Problem, row_major: bool = False):
                   A=dptr(keep["A"]), B=dptr(keep["B"]), Q=dptr(keep["Q"]), R=dptr(keep["R"]),
                   QN=dptr(keep["QN"]), x0=dptr(keep["x0"]), lo=dptr(keep["lo"]),
                   hi=dptr(keep["hi"]), q=dptr(keep["q"]), unorm=dptr(keep["unorm"]))
+    return cp, keep
+
+
+def marshal_device_problem(p, row_major: bool = False):
+    """marshal_problem of a DeviceProblem (validated here): the CProblem holds device pointers.  The layout work marshal_problem does
+    on the host -- column-major matrices, the broadcast of unorm -- is done by torch on the tensors' GPU (copies on the current
+    stream, bit for bit).  Returns (cproblem, keepalive)."""
+    import torch
+    p.validate()
+    with torch.cuda.device(p.device):
+        def colmajor(t):
+            return t.transpose(-1, -2).contiguous()
+
+        def ptr(t):
+            return C.cast(C.c_void_p(t.data_ptr()), c_double_p) if t is not None else c_double_p()
+        mat = (lambda t: t) if (row_major and p.per_instance) else colmajor
+        keep = {"A": mat(p.A), "B": mat(p.B), "Q": colmajor(p.Q), "R": colmajor(p.R), "QN": colmajor(p.QN),
+                "x0": p.x0, "lo": p.lo, "hi": p.hi, "q": p.q,
+                "unorm": None if p.unorm is None else p.unorm.reshape(-1).expand((p.N,) if p.lo.dim() >= 2 else (1,)).contiguous()}
+    cp = CProblem(N=p.N, n=p.n, m=p.m, batch=p.batch,
+                  time_varying=2 if p.per_instance else int(p.time_varying), stage_bounds=p.lo.dim() - 1,
+                  **{k: ptr(v) for k, v in keep.items()})
     return cp, keep
 
 

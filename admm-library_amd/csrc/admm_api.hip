@@ -133,8 +133,10 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
   return ADMM_OK;
 }
 
+// dev_src (admm_setup_device): p is a DeviceProblem's view -- small arrays on the host, the per-instance ones device memory, checked by
+// the device-side findings `scan`
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
-                        admm_exchange_fn ts_fn, void* ts_ctx) {
+                        admm_exchange_fn ts_fn, void* ts_ctx, bool dev_src = false, const DeviceScan* scan = nullptr) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   g_warn.clear();
@@ -142,7 +144,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   if (o_in) o = *o_in; else admm_default_options(&o);
   int rc;
   if ((rc = validate_options(&o))) return rc;
-  if ((rc = validate_problem(p))) return rc;
+  if ((rc = validate_problem(p, scan))) return rc;
   if (ts_n) {
     if (ts_n < 1 || ts_rank < 0 || ts_rank >= ts_n) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: need 0 <= rank < nranks");
     if (ts_n > 1 && !ts_fn) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: an exchange function is needed with more than one rank");
@@ -182,7 +184,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     return fail(ADMM_ERR_UNSUPPORTED, "ADMM_FLAG_ROW_MAJOR: per-instance dynamics only (time_varying = 2)");
   }
   if (p->time_varying == 2) {                    // per-instance dynamics: its own set-up (device factorisation)
-    rc = setup_pinst(h, p);
+    rc = setup_pinst(h, p, dev_src);
     if (rc) { std::string keep = g_err; release(h); g_err = keep; return rc; }
     *out = h;
     return ADMM_OK;
@@ -441,8 +443,8 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     TRY_RELEASE(upload_scan_dense(h->fac.scanW, h->fac.scanM, h->fac.scanK, h->scanWd, h->scan_rows));
     if (h->alt_allowed) TRY_RELEASE(upload_scan_dense(h->fac.scanWB, h->fac.scanM, h->fac.scanK, h->scanWBd, h->scan_rowsB));
   }
-  TRY_RELEASE(upload_transposed(h, p->x0, h->x0, h->n));
-  if (h->has_q) TRY_RELEASE(upload_transposed(h, p->q, h->q, h->L));
+  TRY_RELEASE(upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev_src));
+  if (h->has_q) TRY_RELEASE(upload_transposed(h, p->q, h->q, h->L, 0, 0, dev_src));
   HIP_TRY_RELEASE(hipStreamSynchronize(h->stream));
 #undef DALLOC_WIN
 #undef TRY_RELEASE
@@ -453,6 +455,33 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
 
 int admm_setup(admm_handle** out, const admm_problem* p, const admm_options* o) {
   return setup_common(out, p, o, 0, 0, nullptr, nullptr);
+}
+
+int admm_setup_device(admm_handle** out, const admm_problem* p, const admm_options* o, void* hip_stream) {
+  if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
+  *out = nullptr;
+  g_warn.clear();
+  admm_options oo;
+  if (o) oo = *o; else admm_default_options(&oo);
+  int rc;
+  if ((rc = validate_options(&oo)) || (rc = validate_dims(p))) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(ADMM_ERR_NO_DEVICE, "no HIP device visible: libadmm_hip has no CPU fallback");
+  int dev = oo.device;
+  if (dev < 0) HIP_TRY(hipGetDevice(&dev));
+  if (dev >= ndev) return fail(ADMM_ERR_INVALID, "device ordinal out of range");
+  HIP_TRY(hipSetDevice(dev));
+  oo.device = dev;
+  // the checks run on the caller's stream (ordered after its writes; the handle and its stream do not exist yet) and synchronise it,
+  // so the handle's uploads below read finished data
+  unsigned long long* scratch = nullptr;
+  if ((rc = dalloc(&scratch, 8))) return rc;
+  DeviceProblem d;
+  rc = prepare_device_problem(dev, static_cast<hipStream_t>(hip_stream), p, "admm_setup_device", scratch, d);
+  (void)hipFree(scratch);
+  if (rc) return rc;
+  return setup_common(out, &d.hp, &oo, 0, 0, nullptr, nullptr, true, &d.scan);
 }
 
 int admm_setup_timeshard(admm_handle** out, const admm_problem* p, const admm_options* o, int32_t rank, int32_t nranks,
@@ -492,6 +521,34 @@ int admm_update_instances(admm_handle* h, const double* x0, const double* q) {
 }
 
 
+// The device-memory form (ABI v9): everything is checked before anything is written.
+int admm_update_instances_device(admm_handle* h, const double* x0, const double* q, void* hip_stream) {
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_update_instances_device: not available on a time-sharded handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const char* fn = "admm_update_instances_device";
+  const size_t nx = (size_t)h->n * h->batch, nq = (size_t)h->L * h->batch;
+  int rc;
+  if ((x0 && (rc = check_device_ptr(h->device, x0, nx * sizeof(double), fn, "x0"))) ||
+      (q && (rc = check_device_ptr(h->device, q, nq * sizeof(double), fn, "q"))))
+    return rc;
+  if (!x0 && !q) return ADMM_OK;
+  if ((rc = check_scratch(h)) || (rc = wait_for_caller(h, hip_stream))) return rc;
+  HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, 2 * sizeof(unsigned long long), h->stream));
+  if ((x0 && (rc = scan_finite(h->stream, x0, nx, h->chk_d))) || (q && (rc = scan_finite(h->stream, q, nq, h->chk_d + 1)))) return rc;
+  unsigned long long found[2];
+  HIP_TRY(hipMemcpyAsync(found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (x0 && found[0] != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
+  if (q && !h->has_q) return fail(ADMM_ERR_INVALID, "handle was set up without q; cannot add one later");
+  if (q && found[1] != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
+  if ((rc = ensure_w(h))) return rc;                 // w of the last x-update belongs to the old instance data
+  h->alt_state = admm_handle::ALT_NONE;
+  if (x0 && (rc = upload_transposed(h, x0, h->x0, h->n, 0, 0, true))) return rc;
+  if (q && (rc = upload_transposed(h, q, h->q, h->L, 0, 0, true))) return rc;
+  return ADMM_OK;
+}
+
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
   HIP_TRY(hipSetDevice(h->device));
@@ -510,6 +567,42 @@ int admm_set_state(admm_handle* h, const double* w, const double* z, const doubl
     if (y && (rc = upload_transposed(h, y, h->y, h->L))) return rc;
     h->zy_valid = true;
     h->v_valid = false;                         // an arbitrary (z, y) pair need not be of the form (clip(v), v - clip(v))
+    h->alt_state = admm_handle::ALT_NONE;
+  }
+  return ADMM_OK;
+}
+
+// The device-memory form (ABI v9): all three are checked before any is written.
+int admm_set_state_device(admm_handle* h, const double* w, const double* z, const double* y, void* hip_stream) {
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_set_state_device: not available on a time-sharded handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const char* fn = "admm_set_state_device";
+  const size_t cnt = (size_t)h->L * h->batch;
+  int rc;
+  if ((w && (rc = check_device_ptr(h->device, w, cnt * sizeof(double), fn, "w"))) ||
+      (z && (rc = check_device_ptr(h->device, z, cnt * sizeof(double), fn, "z"))) ||
+      (y && (rc = check_device_ptr(h->device, y, cnt * sizeof(double), fn, "y"))))
+    return rc;
+  if (!w && !z && !y) return ADMM_OK;
+  if ((rc = check_scratch(h)) || (rc = wait_for_caller(h, hip_stream))) return rc;
+  HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, sizeof(unsigned long long), h->stream));
+  for (const double* a : {w, z, y})
+    if (a && (rc = scan_finite(h->stream, a, cnt, h->chk_d))) return rc;
+  unsigned long long found = 0;
+  HIP_TRY(hipMemcpyAsync(&found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (found != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in w, z or y");
+  if (w) {
+    if ((rc = upload_transposed(h, w, h->w, h->L, 0, 0, true))) return rc;
+    h->w_stale = false;
+  }
+  if (z || y) {
+    if ((rc = ensure_zy(h))) return rc;        // keep the one that is not overwritten
+    if (z && (rc = upload_transposed(h, z, h->z, h->L, 0, 0, true))) return rc;
+    if (y && (rc = upload_transposed(h, y, h->y, h->L, 0, 0, true))) return rc;
+    h->zy_valid = true;
+    h->v_valid = false;
     h->alt_state = admm_handle::ALT_NONE;
   }
   return ADMM_OK;
@@ -827,6 +920,33 @@ int admm_get(admm_handle* h, double* w, double* z, double* y) {
   if (w && (rc = download_transposed(h, h->w, w, h->L))) return rc;
   if (z && (rc = download_transposed(h, h->z, z, h->L))) return rc;
   if (y && (rc = download_transposed(h, h->y, y, h->L))) return rc;
+  return ADMM_OK;
+}
+
+// The device-memory form (ABI v9): the read-out kernels write the caller's arrays on the handle's stream, after what the caller had
+// queued on hip_stream; hip_stream then waits for them (no host synchronisation), or, with hip_stream = NULL, this call does.
+int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_stream) {
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_get_device: not available on a time-sharded handle");
+  HIP_TRY(hipSetDevice(h->device));
+  const char* fn = "admm_get_device";
+  const size_t bytes = sizeof(double) * (size_t)h->L * h->batch;
+  int rc;
+  if ((w && (rc = check_device_ptr(h->device, w, bytes, fn, "w"))) || (z && (rc = check_device_ptr(h->device, z, bytes, fn, "z"))) ||
+      (y && (rc = check_device_ptr(h->device, y, bytes, fn, "y"))))
+    return rc;
+  if (w && (rc = ensure_w(h))) return rc;
+  if ((z || y) && (rc = ensure_zy(h))) return rc;
+  if ((rc = wait_for_caller(h, hip_stream))) return rc;
+  if (w && (rc = download_transposed(h, h->w, w, h->L, true))) return rc;
+  if (z && (rc = download_transposed(h, h->z, z, h->L, true))) return rc;
+  if (y && (rc = download_transposed(h, h->y, y, h->L, true))) return rc;
+  if (!hip_stream) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
   return ADMM_OK;
 }
 

@@ -66,8 +66,9 @@ int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes) {
 }
 
 // QP-major host array (batch x rows) -> batch-minor device array (rows x pitch)
-int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr, int nc) {
+int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr, int nc, bool dev) {
   if (rows == h->L && windowed(h)) {
+    if (dev) return fail(ADMM_ERR_UNSUPPORTED, "internal: device-memory source on a time-sharded handle");
     // a state-sized array of a handle that holds a stage window only: rows [r0, r0 + Lw) of every QP's vector (a strided 2-D
     // copy out of the caller's L x batch array), transposed into the window (dst is the biased pointer)
     const size_t r0 = win_row0(h), Lw = win_rows(h);
@@ -79,30 +80,39 @@ int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, 
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ADMM_OK;
   }
-  if ((size_t)rows > h->stage_rows) return fail(ADMM_ERR_INVALID, "internal: staging buffer too small");
-  int rc_up;
-  if ((rc_up = upload_h2d(h, h->stage, src, sizeof(double) * (size_t)rows * h->batch))) return rc_up;
+  const double* staged = src;                 // (a device-memory source is read by the kernel where it is)
+  if (!dev) {
+    if ((size_t)rows > h->stage_rows) return fail(ADMM_ERR_INVALID, "internal: staging buffer too small");
+    int rc_up;
+    if ((rc_up = upload_h2d(h, h->stage, src, sizeof(double) * (size_t)rows * h->batch))) return rc_up;
+    staged = h->stage;
+  }
   dim3 grid((rows + admm::T_TILE - 1) / admm::T_TILE, (h->pitch + admm::T_TILE - 1) / admm::T_TILE), block(admm::T_TILE * 8);
-  hipLaunchKernelGGL(admm::to_batch_minor_kernel, grid, block, 0, h->stream, h->stage, dst, h->batch, rows, h->pitch, nr, nc);
+  hipLaunchKernelGGL(admm::to_batch_minor_kernel, grid, block, 0, h->stream, staged, dst, h->batch, rows, h->pitch, nr, nc);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return ADMM_OK;
 }
 
 // QP-major host operand (batch x N x E) -> the wide shapes' tiled device layout
-int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr, int nc) {
+int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr, int nc, bool dev) {
   const size_t rows = (size_t)h->N * E;
-  if (rows > h->stage_rows) return fail(ADMM_ERR_INVALID, "internal: staging buffer too small");
-  int rc_up;
-  if ((rc_up = upload_h2d(h, h->stage, src, sizeof(double) * rows * h->batch))) return rc_up;
-  admm::launch_to_tiled(h->stream, h->stage, dst, h->batch, h->N, E, h->n, h->pitch, nr, nc);
+  const double* staged = src;
+  if (!dev) {
+    if (rows > h->stage_rows) return fail(ADMM_ERR_INVALID, "internal: staging buffer too small");
+    int rc_up;
+    if ((rc_up = upload_h2d(h, h->stage, src, sizeof(double) * rows * h->batch))) return rc_up;
+    staged = h->stage;
+  }
+  admm::launch_to_tiled(h->stream, staged, dst, h->batch, h->N, E, h->n, h->pitch, nr, nc);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return ADMM_OK;
 }
 
-int download_transposed(admm_handle* h, const double* src, double* dst, int rows) {
+int download_transposed(admm_handle* h, const double* src, double* dst, int rows, bool dev) {
   if (rows == h->L && windowed(h)) {          // the window's rows only; the caller's other rows are left alone
+    if (dev) return fail(ADMM_ERR_UNSUPPORTED, "internal: device-memory destination on a time-sharded handle");
     const size_t r0 = win_row0(h), Lw = win_rows(h);
     dim3 gridw(((int)Lw + admm::T_TILE - 1) / admm::T_TILE, (h->pitch + admm::T_TILE - 1) / admm::T_TILE), blockw(admm::T_TILE * 8);
     hipLaunchKernelGGL(admm::from_batch_minor_kernel, gridw, blockw, 0, h->stream, src + win_bias(h), h->stage, h->batch, (int)Lw, h->pitch);
@@ -113,8 +123,9 @@ int download_transposed(admm_handle* h, const double* src, double* dst, int rows
     return ADMM_OK;
   }
   dim3 grid((rows + admm::T_TILE - 1) / admm::T_TILE, (h->pitch + admm::T_TILE - 1) / admm::T_TILE), block(admm::T_TILE * 8);
-  hipLaunchKernelGGL(admm::from_batch_minor_kernel, grid, block, 0, h->stream, src, h->stage, h->batch, rows, h->pitch);
+  hipLaunchKernelGGL(admm::from_batch_minor_kernel, grid, block, 0, h->stream, src, dev ? dst : h->stage, h->batch, rows, h->pitch);
   HIP_TRY(hipGetLastError());
+  if (dev) return ADMM_OK;                    // (the caller of a device-memory read-out orders it against its own stream)
   return download_d2h(h, dst, h->stage, sizeof(double) * (size_t)rows * h->batch);
 }
 
@@ -152,7 +163,8 @@ int validate_options(const admm_options* o) {
   return ADMM_OK;
 }
 
-int validate_problem(const admm_problem* p) {
+// sizes, NULL pointers, modes: what can be checked without reading an array
+int validate_dims(const admm_problem* p) {
   if (p->N < 1 || p->n < 1 || p->m < 1 || p->batch < 1) return fail(ADMM_ERR_INVALID, "N, n, m, batch must be positive");
   if (!p->A || !p->B || !p->Q || !p->R || !p->QN || !p->x0 || !p->lo || !p->hi)
     return fail(ADMM_ERR_INVALID, "A, B, Q, R, QN, x0, lo, hi must be non-NULL");
@@ -164,28 +176,44 @@ int validate_problem(const admm_problem* p) {
     return fail(ADMM_ERR_INVALID, "time_varying / stage_bounds must be 0, 1 or 2");
   if (p->stage_bounds == 2 && p->time_varying != 2)
     return fail(ADMM_ERR_INVALID, "per-instance bounds (stage_bounds = 2) need per-instance dynamics (time_varying = 2)");
+  return ADMM_OK;
+}
+
+// d != NULL: p describes a problem of the *_device entry points (DeviceProblem::hp): the findings of the device-side checks
+// stand in for the per-instance arrays, which are device memory; everything else is checked here, in the same order.
+int validate_problem(const admm_problem* p, const DeviceScan* d) {
+  int rc;
+  if ((rc = validate_dims(p))) return rc;
+  const int nb = p->n + p->m;
+  const size_t L = (size_t)p->N * nb;
   if (p->time_varying == 2) {
     if (!p->Q || !p->R || !p->QN) return fail(ADMM_ERR_INVALID, "Q, R, QN must be non-NULL");
-    if (!finite_all(p->A, (size_t)p->n * p->n * p->N * p->batch) || !finite_all(p->B, (size_t)p->n * p->m * p->N * p->batch) ||
-        !finite_all(p->Q, (size_t)p->n * p->n) || !finite_all(p->R, (size_t)p->m * p->m) || !finite_all(p->QN, (size_t)p->n * p->n))
+    const bool ab_bad = d ? d->ab_bad
+                          : !finite_all(p->A, (size_t)p->n * p->n * p->N * p->batch) || !finite_all(p->B, (size_t)p->n * p->m * p->N * p->batch);
+    if (ab_bad || !finite_all(p->Q, (size_t)p->n * p->n) || !finite_all(p->R, (size_t)p->m * p->m) || !finite_all(p->QN, (size_t)p->n * p->n))
       return fail(ADMM_ERR_INVALID, "non-finite entry in A, B, Q, R or QN");
   }
+  const bool dev_box = d && p->stage_bounds == 2;
   const size_t nbnd = (size_t)nb * (p->stage_bounds ? p->N : 1) * (p->stage_bounds == 2 ? p->batch : 1);
   {
     std::atomic<size_t> first_bad{SIZE_MAX};         // smallest offending index (threads take disjoint ranges)
     const double *lo = p->lo, *hi = p->hi;
-    host_parallel(nbnd, 2 * sizeof(double), [lo, hi, &first_bad](size_t b, size_t e) {
-      for (size_t i = b; i < e; ++i)
-        if (!(lo[i] <= hi[i]) || lo[i] == INFINITY || hi[i] == -INFINITY) {      // (!(<=) also catches NaN)
-          size_t cur = first_bad.load();
-          while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
-          return;
-        }
-    });
+    if (dev_box)
+      first_bad = d->bnd_bad;
+    else
+      host_parallel(nbnd, 2 * sizeof(double), [lo, hi, &first_bad](size_t b, size_t e) {
+        for (size_t i = b; i < e; ++i)
+          if (!(lo[i] <= hi[i]) || lo[i] == INFINITY || hi[i] == -INFINITY) {      // (!(<=) also catches NaN)
+            size_t cur = first_bad.load();
+            while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+            return;
+          }
+      });
     const size_t i = first_bad.load();
     if (i != SIZE_MAX) {
-      if (std::isnan(p->lo[i]) || std::isnan(p->hi[i])) return fail(ADMM_ERR_INVALID, "NaN in bounds");
-      if (p->lo[i] > p->hi[i]) return fail(ADMM_ERR_INVALID, "lo > hi at bound index " + std::to_string(i));
+      const double lo_i = dev_box ? d->bnd_lo : p->lo[i], hi_i = dev_box ? d->bnd_hi : p->hi[i];
+      if (std::isnan(lo_i) || std::isnan(hi_i)) return fail(ADMM_ERR_INVALID, "NaN in bounds");
+      if (lo_i > hi_i) return fail(ADMM_ERR_INVALID, "lo > hi at bound index " + std::to_string(i));
       return fail(ADMM_ERR_INVALID, "lo = +inf or hi = -inf");
     }
   }
@@ -194,7 +222,9 @@ int validate_problem(const admm_problem* p) {
     for (int k = 0; k < cnt; ++k) {
       const double ub = p->unorm[k];
       if (std::isnan(ub) || !(ub > 0.0)) return fail(ADMM_ERR_INVALID, "unorm entries must be positive (inf = off)");
-      if (std::isfinite(ub))
+      if (std::isfinite(ub) && dev_box) {
+        if ((size_t)k == d->un_stage) return fail(ADMM_ERR_INVALID, "control rows must be unbounded (-inf, inf) where unorm is finite");
+      } else if (std::isfinite(ub))
         for (int b = 0; b < (p->stage_bounds == 2 ? p->batch : 1); ++b)       // (per-instance box: every QP's)
           for (int j = 0; j < p->m; ++j) {
             const size_t o = ((size_t)b * cnt + k) * nb + j;
@@ -203,9 +233,111 @@ int validate_problem(const admm_problem* p) {
           }
     }
   }
-  if (!finite_all(p->x0, (size_t)p->n * p->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
-  if (p->q && !finite_all(p->q, L * p->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
+  if (d ? d->x0_bad : !finite_all(p->x0, (size_t)p->n * p->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
+  if (p->q && (d ? d->q_bad : !finite_all(p->q, L * p->batch))) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
   return ADMM_OK;
+}
+
+
+// ---- caller arrays in device memory (the *_device entry points, ABI v9) ----
+
+// `ptr` must be device memory of `device` (not pageable or pinned host memory, not another GPU's), holding at least `bytes`
+// where the runtime reports the allocation's extent.  `fn` / `name` name the entry point and the argument in the message.
+int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name) {
+  hipPointerAttribute_t a{};
+  const hipError_t e = hipPointerGetAttributes(&a, ptr);
+  if (e != hipSuccess) (void)hipGetLastError();          // (pageable host memory: some ROCm versions fail the query itself)
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device)
+    return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " is not device memory of the handle's GPU (device " + std::to_string(device) + ")");
+  if (reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
+    return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " is not 8-byte aligned");
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void*>(ptr)) == hipSuccess) {
+    if (static_cast<const char*>(ptr) + bytes > static_cast<const char*>(base) + size)
+      return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " ends before its " + std::to_string(bytes / sizeof(double)) + " doubles");
+  } else {
+    (void)hipGetLastError();
+  }
+  return ADMM_OK;
+}
+
+// check_finite_kernel over a[0, count) on s; slot receives the smallest offending index (it must hold ~0 beforehand)
+int scan_finite(hipStream_t s, const double* a, size_t count, unsigned long long* slot) {
+  const size_t blocks = std::min<size_t>((count + admm::CHECK_THREADS - 1) / admm::CHECK_THREADS, 8192);
+  if (!blocks) return ADMM_OK;
+  hipLaunchKernelGGL(admm::check_finite_kernel, dim3((unsigned)blocks), dim3(admm::CHECK_THREADS), 0, s, a, count, slot);
+  HIP_TRY(hipGetLastError());
+  return ADMM_OK;
+}
+
+// The checks of a problem whose arrays are device memory of `device`, on stream s (ordered after the caller's writes): the pointers,
+// then the small arrays copied to the host and the per-instance ones read once on the device (slots: scratch[0..5] = A, B, box,
+// thrust-magnitude stage, x0, q).  Fills d; returns with s synchronised.  The data checks themselves are validate_problem(&d.hp,
+// &d.scan): the caller's.
+int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, const char* fn, unsigned long long* scratch,
+                           DeviceProblem& d) {
+  int rc;
+  if ((rc = validate_dims(p))) return rc;
+  const size_t n = p->n, m = p->m, N = p->N, B = p->batch, nb = n + m, L = N * nb;
+  const size_t stages = p->time_varying ? N : 1, per = p->time_varying == 2 ? B : 1;
+  const size_t nA = n * n * stages * per, nB = n * m * stages * per;
+  const size_t nbnd = nb * (p->stage_bounds ? N : 1) * (p->stage_bounds == 2 ? B : 1), nun = p->stage_bounds ? N : 1;
+  const struct { const double* ptr; size_t count; const char* name; } arrays[] = {
+      {p->A, nA, "A"}, {p->B, nB, "B"}, {p->Q, n * n, "Q"}, {p->R, m * m, "R"}, {p->QN, n * n, "QN"}, {p->x0, n * B, "x0"},
+      {p->lo, nbnd, "lo"}, {p->hi, nbnd, "hi"}, {p->q, L * B, "q"}, {p->unorm, nun, "unorm"}};
+  for (const auto& a : arrays)
+    if (a.ptr && (rc = check_device_ptr(device, a.ptr, a.count * sizeof(double), fn, a.name))) return rc;
+  d.hp = *p;
+  auto to_host = [&](const double* src, size_t count, std::vector<double>& v, const double** field) -> int {
+    v.resize(count);
+    HIP_TRY(hipMemcpyAsync(v.data(), src, sizeof(double) * count, hipMemcpyDeviceToHost, s));
+    *field = v.data();
+    return ADMM_OK;
+  };
+  if ((rc = to_host(p->Q, n * n, d.Q, &d.hp.Q)) || (rc = to_host(p->R, m * m, d.R, &d.hp.R)) || (rc = to_host(p->QN, n * n, d.QN, &d.hp.QN)))
+    return rc;
+  if (p->time_varying != 2 && ((rc = to_host(p->A, nA, d.A, &d.hp.A)) || (rc = to_host(p->B, nB, d.B, &d.hp.B)))) return rc;
+  if (p->stage_bounds != 2 && ((rc = to_host(p->lo, nbnd, d.lo, &d.hp.lo)) || (rc = to_host(p->hi, nbnd, d.hi, &d.hp.hi)))) return rc;
+  if (p->unorm && (rc = to_host(p->unorm, nun, d.un, &d.hp.unorm))) return rc;
+  HIP_TRY(hipMemsetAsync(scratch, 0xff, 6 * sizeof(unsigned long long), s));
+  if (p->time_varying == 2 && ((rc = scan_finite(s, p->A, nA, scratch)) || (rc = scan_finite(s, p->B, nB, scratch + 1)))) return rc;
+  if (p->stage_bounds == 2) {
+    const size_t blocks = std::min<size_t>((nbnd + admm::CHECK_THREADS - 1) / admm::CHECK_THREADS, 8192);
+    hipLaunchKernelGGL(admm::check_bounds_kernel, dim3((unsigned)blocks), dim3(admm::CHECK_THREADS), 0, s, p->lo, p->hi, nbnd, p->unorm,
+                       (int)nb, (int)m, (int)N, scratch + 2);
+    HIP_TRY(hipGetLastError());
+  }
+  if ((rc = scan_finite(s, p->x0, n * B, scratch + 4))) return rc;
+  if (p->q && (rc = scan_finite(s, p->q, L * B, scratch + 5))) return rc;
+  unsigned long long found[6];
+  HIP_TRY(hipMemcpyAsync(found, scratch, sizeof found, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const unsigned long long none = ~0ull;
+  d.scan = DeviceScan{};
+  d.scan.ab_bad = found[0] != none || found[1] != none;
+  if (found[2] != none) {
+    d.scan.bnd_bad = (size_t)found[2];
+    HIP_TRY(hipMemcpy(&d.scan.bnd_lo, p->lo + found[2], sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&d.scan.bnd_hi, p->hi + found[2], sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (found[3] != none) d.scan.un_stage = (size_t)found[3];
+  d.scan.x0_bad = found[4] != none;
+  d.scan.q_bad = found[5] != none;
+  return ADMM_OK;
+}
+
+// the handle's stream waits for what the caller has queued on its stream so far (NULL: the caller vouches for its data)
+int wait_for_caller(admm_handle* h, void* hip_stream) {
+  if (!hip_stream) return ADMM_OK;
+  if (!h->ext_ev) HIP_TRY(hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ext_ev, static_cast<hipStream_t>(hip_stream)));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ext_ev, 0));
+  return ADMM_OK;
+}
+
+int check_scratch(admm_handle* h) {
+  return h->chk_d ? ADMM_OK : dalloc(&h->chk_d, 8);
 }
 
 
@@ -298,6 +430,8 @@ void release(admm_handle* h) {
     if (h->pin[i]) { (void)hipHostFree(h->pin[i]); h->pin[i] = nullptr; }
     if (h->pin_ev[i]) { (void)hipEventDestroy(h->pin_ev[i]); h->pin_ev[i] = nullptr; }
   }
+  if (h->ext_ev) { (void)hipEventDestroy(h->ext_ev); h->ext_ev = nullptr; }
+  if (h->chk_d) { (void)hipFree(h->chk_d); h->chk_d = nullptr; }
   if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
   delete h;
 }

@@ -1603,4 +1603,46 @@ static __global__ __launch_bounds__(T_TILE * 8) void from_batch_minor_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// Checks of caller arrays that live in device memory (the *_device entry points, admm_hostio.hip): the rules of the host's
+// validate_problem, with the smallest offending index found by a 64-bit atomic min on a vector address (each thread offers
+// the first hit of its own grid-stride range, so the minimum over the grid is exact).  Bit tests instead of isnan / isfinite:
+// device code is compiled with -fno-honor-nans.  Bandwidth-bound, one read of the array.
+// ---------------------------------------------------------------------------
+constexpr int CHECK_THREADS = 256;
+__device__ inline bool nonfinite_bits(double x) { return ((__double_as_longlong(x) >> 52) & 0x7ff) == 0x7ff; }
+
+// *first_bad = min(*first_bad, smallest i < count with a[i] NaN or +-inf)
+static __global__ __launch_bounds__(CHECK_THREADS) void check_finite_kernel(const double* __restrict__ a, size_t count,
+                                                                           unsigned long long* __restrict__ first_bad) {
+  for (size_t i = (size_t)blockIdx.x * CHECK_THREADS + threadIdx.x; i < count; i += (size_t)gridDim.x * CHECK_THREADS)
+    if (nonfinite_bits(a[i])) {
+      atomicMin(first_bad, (unsigned long long)i);
+      return;
+    }
+}
+
+// The box lo, hi (count entries; entry i is row i % nb of stage (i / nb) % N):
+//   out[0] = min(out[0], smallest i with a NaN, lo > hi, lo = +inf or hi = -inf)
+//   out[1] = min(out[1], smallest stage k whose thrust-magnitude bound ub[k] is finite while some control row (row < m) of that
+//            stage has a finite lo or hi)   (ub = NULL: no such bound)
+static __global__ __launch_bounds__(CHECK_THREADS) void check_bounds_kernel(const double* __restrict__ lo, const double* __restrict__ hi,
+                                                                           size_t count, const double* __restrict__ ub, int nb, int m,
+                                                                           int N, unsigned long long* __restrict__ out) {
+  constexpr long long PINF = 0x7ff0000000000000LL, MINF = (long long)0xfff0000000000000ULL, ABS = 0x7fffffffffffffffLL;
+  unsigned long long bad = ~0ull, kbad = ~0ull;
+  for (size_t i = (size_t)blockIdx.x * CHECK_THREADS + threadIdx.x; i < count; i += (size_t)gridDim.x * CHECK_THREADS) {
+    const double l = lo[i], u = hi[i];
+    const long long bl = __double_as_longlong(l), bu = __double_as_longlong(u);
+    const bool nan = (bl & ABS) > PINF || (bu & ABS) > PINF;
+    if (bad == ~0ull && (nan || l > u || bl == PINF || bu == MINF)) bad = i;
+    if (ub && (int)(i % nb) < m) {
+      const unsigned long long k = (i / nb) % N;
+      if (k < kbad && !nonfinite_bits(ub[k]) && (!nonfinite_bits(l) || !nonfinite_bits(u))) kbad = k;
+    }
+  }
+  if (bad != ~0ull) atomicMin(&out[0], bad);
+  if (kbad != ~0ull) atomicMin(&out[1], kbad);
+}
+
 }  // namespace admm

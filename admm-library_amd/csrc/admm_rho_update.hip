@@ -224,6 +224,34 @@ int admm_update_problem(admm_handle* h, const admm_problem* p) {
   HIP_TRY(hipSetDevice(h->device));
   int rc;
   if ((rc = validate_problem(p))) return rc;
+  return update_problem_checked(h, p, false);
+}
+
+// The device-memory form (ABI v9): the same update, from arrays in the handle's GPU memory.  Everything is checked before anything of
+// the handle is written: the data (validate_problem over the device-side findings), then -- per-instance dynamics -- the trial
+// factorisation from the caller's A, B; bounds, x0 and q are read only after the commit, and those reads cannot be refused.
+int admm_update_problem_device(admm_handle* h, const admm_problem* p, void* hip_stream) {
+  if (!h || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_update_problem_device: not available on a time-sharded handle");
+  g_warn.clear();
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  DeviceProblem d;
+  if ((rc = check_scratch(h)) || (rc = validate_dims(p)) || (rc = wait_for_caller(h, hip_stream)) ||
+      (rc = prepare_device_problem(h->device, h->stream, p, "admm_update_problem_device", h->chk_d, d)))
+    return rc;
+  if ((rc = validate_problem(&d.hp, &d.scan))) return rc;
+  return update_problem_checked(h, &d.hp, true);
+}
+
+}  // extern "C"
+
+namespace admm {
+namespace rt {
+
+// admm_update_problem after validate_problem: dev = the per-instance arrays of p (A, B, box, x0, q) are device memory
+int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
+  int rc;
   if (p->N != h->N || p->n != h->n || p->m != h->m || p->batch != h->batch)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: N, n, m, batch must equal those of admm_setup");
   if ((p->q != nullptr) != h->has_q)
@@ -237,7 +265,7 @@ int admm_update_problem(admm_handle* h, const admm_problem* p) {
     // with the rho it has; only if every factor exists and meets the conditioning bound is anything of the handle replaced
     // (pointer swaps) -- "on failure the handle is unchanged" holds for this mode as for shared dynamics.
     if ((rc = pinst_alloc_trial(h, true))) return rc;
-    if ((rc = pinst_upload_dynamics(h, p, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2))) return rc;
+    if ((rc = pinst_upload_dynamics(h, p, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2, dev))) return rc;
     int not_pd = 0, grown = 0;
     if ((rc = pinst_try(h, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2, h->rho_d, nullptr, &not_pd, &grown))) return rc;
     if (not_pd) return fail(ADMM_ERR_NUMERIC, "problem update refused: R + rho I + B'PB is not positive definite for " + std::to_string(not_pd) + " QP(s)");
@@ -253,9 +281,9 @@ int admm_update_problem(admm_handle* h, const admm_problem* p) {
     std::swap(h->Ad, h->Ad2); std::swap(h->Bd, h->Bd2); std::swap(h->Kd, h->Kd2); std::swap(h->Sd, h->Sd2);      // commit
     std::swap(h->Qd, h->Qd2); std::swap(h->Rd, h->Rd2); std::swap(h->QNd, h->QNd2);
     h->stage_bounds = p->stage_bounds;
-    if ((rc = pinst_upload_bounds(h, p))) return rc;
-    if ((rc = upload_transposed(h, p->x0, h->x0, h->n))) return rc;
-    if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L))) return rc;
+    if ((rc = pinst_upload_bounds(h, p, dev))) return rc;
+    if ((rc = upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev))) return rc;
+    if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L, 0, 0, dev))) return rc;
     return pinst_segments(h);                    // transfer matrices of the new factor
   }
   admm::Factor f;
@@ -278,11 +306,11 @@ int admm_update_problem(admm_handle* h, const admm_problem* p) {
   h->fac = std::move(f);
   if ((rc = upload_factor(h))) return rc;
   if ((rc = upload_bounds(h, p))) return rc;
-  if ((rc = upload_transposed(h, p->x0, h->x0, h->n))) return rc;
-  if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L))) return rc;
+  if ((rc = upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev))) return rc;
+  if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L, 0, 0, dev))) return rc;
   destroy_graph(h);
   return ADMM_OK;
 }
 
-
-}  // extern "C"
+}  // namespace rt
+}  // namespace admm

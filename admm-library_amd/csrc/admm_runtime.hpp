@@ -138,6 +138,9 @@ struct admm_handle {
   // pinned bounce buffers of large host-to-device uploads (allocated on first use; upload_h2d)
   unsigned char* pin[2] = {nullptr, nullptr};
   hipEvent_t pin_ev[2] = {nullptr, nullptr};
+  // the *_device entry points (ABI v9): ordering against the caller's stream, result slots of the device-side checks
+  hipEvent_t ext_ev = nullptr;
+  unsigned long long* chk_d = nullptr;
   int iters_run = 0;
   bool resid_valid = false;
   // A residual-evaluating alternating iteration leaves its finalise to the NEXT scan launch (finalise
@@ -249,12 +252,37 @@ int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int i
 // ---- host <-> device transfers, validation, uploads of the factor, handle lifetime (admm_hostio.hip)
 int upload_h2d(admm_handle* h, void* dst, const void* src, size_t bytes);
 int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes);   // ... and back; returns with the copy complete
-int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr = 0, int nc = 0);   // per-instance operand (batch x N x E) -> tiled layout; nr x nc: row-major source blocks
-int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr = 0, int nc = 0);   // nr x nc: the rows are stacks of row-major blocks
-int download_transposed(admm_handle* h, const double* src, double* dst, int rows);
+// dev: the caller's array (src of an upload, dst of a download) is device memory of the handle's GPU instead of host memory; it is
+// then read / written by the layout kernels directly, and a download returns with its kernel queued on the handle's stream
+int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr = 0, int nc = 0, bool dev = false);   // per-instance operand (batch x N x E) -> tiled layout; nr x nc: row-major source blocks
+int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr = 0, int nc = 0, bool dev = false);   // nr x nc: the rows are stacks of row-major blocks
+int download_transposed(admm_handle* h, const double* src, double* dst, int rows, bool dev = false);
 bool finite_all(const double* a, size_t cnt);
 int validate_options(const admm_options* o);
-int validate_problem(const admm_problem* p);
+// What the device-side checks of a *_device call found in the caller's large arrays; validate_problem reads these instead of
+// the arrays themselves (which it cannot dereference), so both forms refuse the same data with the same status and message.
+struct DeviceScan {
+  bool ab_bad = false;               // a non-finite entry in per-instance A or B
+  size_t bnd_bad = SIZE_MAX;         // per-instance box: smallest offending index ...
+  double bnd_lo = 0.0, bnd_hi = 0.0; // ... and its lo, hi
+  size_t un_stage = SIZE_MAX;        // per-instance box: smallest stage whose finite unorm meets a bounded control row of some QP
+  bool x0_bad = false, q_bad = false;
+};
+// A problem whose arrays are device memory, as the library uses it: the small arrays (Q, R, QN, unorm; batch-shared A, B and box)
+// copied to the host, the per-instance ones (per-instance A, B and box, x0, q) still the caller's device pointers.
+struct DeviceProblem {
+  admm_problem hp{};
+  std::vector<double> A, B, Q, R, QN, lo, hi, un;
+  DeviceScan scan;
+};
+int validate_dims(const admm_problem* p);
+int validate_problem(const admm_problem* p, const DeviceScan* d = nullptr);
+int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name);
+int scan_finite(hipStream_t s, const double* a, size_t count, unsigned long long* slot);
+int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, const char* fn, unsigned long long* scratch,
+                           DeviceProblem& d);
+int wait_for_caller(admm_handle* h, void* hip_stream);
+int check_scratch(admm_handle* h);
 void set_mixed_form(admm_handle* h, bool fp32);
 void warn_alt_gate(const admm::Factor& f, double rho, const char* when);
 double scan_growth(const admm::Factor& f);
@@ -269,14 +297,15 @@ bool problem_has_soc(const admm_problem* p);
 // ---- per-instance dynamics (admm_pinst_rt.hip)
 int pinst_factor(admm_handle* h, bool only_marked = false);
 int pinst_fill_rho(admm_handle* h, double rho);
-int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, double* Bd, double* Qd, double* Rd, double* QNd);
-int pinst_upload_bounds(admm_handle* h, const admm_problem* p);
-int pinst_upload(admm_handle* h, const admm_problem* p);
+int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, double* Bd, double* Qd, double* Rd, double* QNd,
+                          bool dev = false);   // dev: A, B are device memory (the weights are host arrays either way)
+int pinst_upload_bounds(admm_handle* h, const admm_problem* p, bool dev = false);   // dev: a per-instance box is device memory
+int pinst_upload(admm_handle* h, const admm_problem* p, bool dev = false);
 int pinst_alloc_trial(admm_handle* h, bool dynamics);
 int pinst_try(admm_handle* h, const double* Ad, const double* Bd, const double* Qd, const double* Rd, const double* QNd,
               const double* rhov, const int* todo, int* n_not_pd, int* n_grown);
 int pinst_segments(admm_handle* h);
-int setup_pinst(admm_handle* h, const admm_problem* p);
+int setup_pinst(admm_handle* h, const admm_problem* p, bool dev = false);
 
 // ---- refactors: background candidates of the adaptive rule, rho changes (admm_rho_update.hip)
 admm_problem shared_problem(const admm_handle* h);
@@ -285,6 +314,7 @@ void spec_reap(admm_handle* h, bool all);
 std::unique_ptr<SpecFactor> spec_take(admm_handle* h, double rho);
 void spec_start(admm_handle* h);
 int set_rho_internal(admm_handle* h, double rho_new);
+int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev);
 
 // ---- the stage window of the big per-stage arrays (see admm_handle::wk0)
 inline size_t win_row0(const admm_handle* h) { return (size_t)h->wk0 * h->nb; }                       // first stacked row held

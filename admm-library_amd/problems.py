@@ -136,6 +136,97 @@ class Problem:
                 raise ValueError("non-finite problem data")
 
 
+
+@dataclasses.dataclass
+class DeviceProblem:
+    """A Problem whose arrays are fp64 torch tensors in the memory of ONE GPU (same fields, same shapes, same C order as Problem):
+    what Solver hands to the device-memory entry points (admm_setup_device, admm_update_problem_device) -- a
+    caller that builds its QP data on the GPU (scvx.linearise_device) gives it to the library without a trip through host memory.
+    The data themselves are checked by the library, on the device; validate() checks types, devices, shapes and layout."""
+    N: int
+    A: "torch.Tensor"
+    B: "torch.Tensor"
+    Q: "torch.Tensor"
+    R: "torch.Tensor"
+    QN: "torch.Tensor"
+    x0: "torch.Tensor"
+    lo: "torch.Tensor"
+    hi: "torch.Tensor"
+    q: Optional["torch.Tensor"] = None
+    unorm: Optional["torch.Tensor"] = None      # 0-d, or (N,) with per-stage bounds
+    name: str = ""
+
+    n = Problem.n
+    m = Problem.m
+    nb = Problem.nb
+    L = Problem.L
+    batch = Problem.batch
+    time_varying = Problem.time_varying
+    per_instance = Problem.per_instance
+    per_instance_bounds = Problem.per_instance_bounds
+
+    @property
+    def device(self):
+        return self.x0.device
+
+    @classmethod
+    def from_problem(cls, p: Problem, device="cuda:0") -> "DeviceProblem":
+        """The same data, copied to `device` (bit for bit)."""
+        import torch
+
+        def t(a):
+            return None if a is None else torch.as_tensor(np.ascontiguousarray(a, np.float64), device=device)
+        return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
+                   unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name)
+
+    def validate(self) -> None:
+        """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
+        import torch
+        dev = self.x0.device if torch.is_tensor(self.x0) else None
+        for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
+            a = getattr(self, name)
+            if a is None and name in ("q", "unorm"):
+                continue
+            check_device_tensor(name, a, dev)
+        n, m, N, batch = self.n, self.m, self.N, self.batch
+        if N < 1 or n < 1 or m < 1:
+            raise ValueError("N, n, m must be positive")
+        shapes = {"A": {(n, n), (N, n, n), (batch, N, n, n)}, "B": {(n, m), (N, n, m), (batch, N, n, m)},
+                  "Q": {(n, n)}, "R": {(m, m)}, "QN": {(n, n)}, "x0": {(batch, n)},
+                  "lo": {(n + m,), (N, n + m), (batch, N, n + m)}, "hi": {(n + m,), (N, n + m), (batch, N, n + m)}}
+        for name, ok in shapes.items():
+            if tuple(getattr(self, name).shape) not in ok:
+                raise ValueError(f"{name}: shape {tuple(getattr(self, name).shape)} is none of {sorted(ok)}")
+        if self.A.dim() != self.B.dim():
+            raise ValueError("A and B must both be LTI, both LTV or both per-instance")
+        if self.lo.shape != self.hi.shape:
+            raise ValueError("lo and hi must have the same shape")
+        if self.lo.dim() == 3 and not self.per_instance:
+            raise ValueError("per-instance bounds need per-instance dynamics")
+        if self.q is not None and tuple(self.q.shape) != (batch, self.L):
+            raise ValueError("q must be (batch, L)")
+        if self.unorm is not None and tuple(self.unorm.shape) not in ({(), (N,)} if self.lo.dim() >= 2 else {()}):
+            raise ValueError("unorm must be a scalar, or (N,) together with per-stage bounds")
+
+
+def check_device_tensor(name: str, a, device=None, shape=None) -> None:
+    """ValueError unless `a` is a contiguous fp64 CUDA tensor (on `device`, of `shape`, where given): what the device-memory entry
+    points take.  A CPU tensor -- pinned or not -- is refused here, before the library is called."""
+    import torch
+    if not torch.is_tensor(a):
+        raise ValueError(f"{name}: expected a torch tensor in GPU memory, got {type(a).__name__}")
+    if a.dtype != torch.float64:
+        raise ValueError(f"{name}: dtype {a.dtype}, expected torch.float64")
+    if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(a.shape)}, expected {tuple(shape)}")
+    if not a.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if not a.is_cuda:
+        raise ValueError(f"{name}: a CPU tensor; the device-memory form takes GPU tensors")
+    if device is not None and a.device != torch.device(device):
+        raise ValueError(f"{name}: on {a.device}, expected {torch.device(device)}")
+
+
 def double_integrator(N: int = 50, batch: int = 1, seed0: int = SEED0,
                       dt: float = 0.2, u_max: float = 1.0) -> Problem:
     """BASELINE.json configs[0]: 2-state LQR QP, box input constraint |u| <= u_max.

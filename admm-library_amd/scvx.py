@@ -94,11 +94,12 @@ def linearise(xprev: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, eps: f
 
 
 def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = "cuda:0", eps: float = 1e-6,
-                     substeps: int = 4, rc: float = RC_KM) -> Tuple[np.ndarray, np.ndarray]:
+                     substeps: int = 4, rc: float = RC_KM, keep_on_device: bool = False):
     """linearise() of the shipped model (rk4_step of relative_motion_rhs) with the n + m central differences evaluated as ONE
     batch of torch tensors on `device`: the same formulas in the same order, fp64.  The NumPy version makes 2 (n + m) x 16
     passes over (B, N, 6) arrays -- 10 s per outer iteration of a 4096-trajectory batch, most of the wall time of
-    examples/scvx_batch_rendezvous.py; this is host plumbing, not the solver."""
+    examples/scvx_batch_rendezvous.py; this is host plumbing, not the solver.
+    keep_on_device: return A, B as the torch tensors on `device` (for a DeviceProblem) instead of NumPy copies."""
     import torch
     xp = torch.as_tensor(np.ascontiguousarray(xprev), dtype=torch.float64, device=device)
     up = torch.as_tensor(np.ascontiguousarray(u), dtype=torch.float64, device=device)
@@ -127,7 +128,10 @@ def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = 
     eu = eps * torch.eye(m, dtype=torch.float64, device=device).reshape((m,) + (1,) * (up.dim() - 1) + (m,))
     A = (step(xp[None] + ex, up[None]) - step(xp[None] - ex, up[None])) / (2.0 * eps)        # (n, ..., n): [j, ..., i] = dF_i / dx_j
     B = (step(xp[None].expand((m,) + xp.shape), up[None] + eu) - step(xp[None].expand((m,) + xp.shape), up[None] - eu)) / (2.0 * eps)
-    return torch.movedim(A, 0, -1).contiguous().cpu().numpy(), torch.movedim(B, 0, -1).contiguous().cpu().numpy()
+    A, B = torch.movedim(A, 0, -1).contiguous(), torch.movedim(B, 0, -1).contiguous()
+    if keep_on_device:
+        return A, B
+    return A.cpu().numpy(), B.cpu().numpy()
 
 
 @dataclasses.dataclass
@@ -171,10 +175,11 @@ def correction_qp(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, 
                    name=f"scvx_correction_N{N}")
 
 
-def gpu_qp_solver(**options) -> Callable[[Problem], Tuple[np.ndarray, int]]:
+def gpu_qp_solver(qp_data_on_device: bool = False, **options) -> Callable[[Problem], Tuple[np.ndarray, int]]:
     """QP solver for scvx(): the HIP solver (raises without a device: no CPU fallback).  One handle
     serves every outer iteration: admm_update_problem refactors in place (same N, n, m, batch), each
-    solve starts cold (z = y = 0), like a fresh handle."""
+    solve starts cold (z = y = 0), like a fresh handle.  A DeviceProblem (correction_qp_batch(..., qp_data_on_device=True))
+    goes in through the device-memory entry points; qp_data_on_device: z comes back through admm_get_device as well."""
     from .solver import Options, Solver
     state = {"solver": None, "shape": None}
 
@@ -189,7 +194,11 @@ def gpu_qp_solver(**options) -> Callable[[Problem], Tuple[np.ndarray, int]]:
         s = state["solver"]
         zero = np.zeros((p.batch, p.L))
         info = s.solve(z0=zero, y0=zero)
-        _, z, _ = s.get(w=False)
+        if qp_data_on_device:
+            _, z, _ = s.get_device(w=False, y=False)
+            z = z.cpu().numpy()
+        else:
+            _, z, _ = s.get(w=False)
         return z, int(info.iters_run)      # z: the feasible (projected) iterate
     return solve
 
@@ -255,13 +264,21 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
 
 
 def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
-                        tr_u: np.ndarray, tr_x: np.ndarray, step=rk4_step, device: Optional[str] = None) -> Problem:
+                        tr_u: np.ndarray, tr_x: np.ndarray, step=rk4_step, device: Optional[str] = None,
+                        qp_data_on_device: bool = False):
     """The correction QPs of B trajectories as ONE batch with per-instance dynamics, box and linear term
-    (xb (B, N, n), ub (B, N, m), x0 (B, n), trust radii (B,))."""
+    (xb (B, N, n), ub (B, N, m), x0 (B, n), trust radii (B,)).
+    qp_data_on_device (with device): a DeviceProblem -- A, B stay where linearise_device made them, the rest is built here
+    exactly as for the Problem and copied to the device."""
     Bn, N, n = xb.shape
     m = ub.shape[-1]
     xprev = np.concatenate([x0[:, None, :], xb[:, :-1, :]], axis=1)
-    A, B = linearise_device(xprev, ub, dt, device) if (device is not None and step is rk4_step) else linearise(xprev, ub, dt, step)
+    if qp_data_on_device and (device is None or step is not rk4_step):
+        raise ValueError("qp_data_on_device needs the device linearisation (device = 'cuda:k', the shipped rk4_step)")
+    if device is not None and step is rk4_step:
+        A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device)
+    else:
+        A, B = linearise(xprev, ub, dt, step)
     q = np.empty((Bn, N, m + n))
     q[..., :m] = ub @ R.T
     q[:, :-1, m:] = xb[:, :-1, :] @ Q.T
@@ -272,21 +289,32 @@ def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: floa
     hi[..., :m] = np.minimum(u_hi - ub, tr_u[:, None, None])
     lo[..., m:] = -tr_x[:, None, None]
     hi[..., m:] = tr_x[:, None, None]
-    return Problem(N=N, A=A, B=B, Q=np.asarray(Q, np.float64), R=np.asarray(R, np.float64),
-                   QN=np.asarray(QN, np.float64), x0=np.zeros((Bn, n)), lo=lo, hi=hi, q=q.reshape(Bn, -1),
-                   name=f"scvx_correction_batch{Bn}_N{N}")
+    p = Problem(N=N, A=A, B=B, Q=np.asarray(Q, np.float64), R=np.asarray(R, np.float64),
+                QN=np.asarray(QN, np.float64), x0=np.zeros((Bn, n)), lo=lo, hi=hi, q=q.reshape(Bn, -1),
+                name=f"scvx_correction_batch{Bn}_N{N}")
+    if not qp_data_on_device:
+        return p
+    import torch
+    from .problems import DeviceProblem
+
+    def t(a):
+        return torch.as_tensor(np.ascontiguousarray(a, np.float64), device=device)
+    return DeviceProblem(N=N, A=A, B=B, Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(lo), hi=t(hi), q=t(p.q), name=p.name)
 
 
 def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
                qp_solver: Optional[Callable[[Problem], Tuple[np.ndarray, int]]] = None,
                tr_u: float = 0.1, tr_x: float = 20.0, max_outer: int = 20, tol: float = 1e-6,
                rho_reject: float = 0.1, rho_expand: float = 0.7, step=rk4_step,
-               qp_options: Optional[dict] = None, linearise_on: Optional[str] = None) -> List[ScvxResult]:
+               qp_options: Optional[dict] = None, linearise_on: Optional[str] = None,
+               qp_data_on_device: bool = False) -> List[ScvxResult]:
     """scvx() for B initial conditions x0 (B, n) at once: the same trust-region loop per trajectory (own trust radii,
     own accept / reject decisions, own stop), but ONE batched QP solve per outer iteration -- per-instance dynamics,
     bounds and linear term (correction_qp_batch).  A trajectory that has stopped keeps its place in the batch with a
     zero-width box (its correction is then exactly zero) until the last one stops.
-    linearise_on = "cuda:0": the central differences of the shipped model run as torch tensors on that device (linearise_device)."""
+    linearise_on = "cuda:0": the central differences of the shipped model run as torch tensors on that device (linearise_device).
+    qp_data_on_device (with linearise_on): the QP data go to the solver as a DeviceProblem -- A, B never leave the GPU -- and z
+    comes back through admm_get_device; the QPs, and so every decision, are those of the default path bit for bit."""
     x0 = np.atleast_2d(np.asarray(x0, np.float64))
     Bn = x0.shape[0]
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
@@ -294,8 +322,8 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     u_lo = np.broadcast_to(np.asarray(u_lo, np.float64), (m,))
     u_hi = np.broadcast_to(np.asarray(u_hi, np.float64), (m,))
     if qp_solver is None:
-        qp_solver = gpu_qp_solver(**(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
-                                                        check_interval=25)))
+        qp_solver = gpu_qp_solver(qp_data_on_device, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
+                                                                           check_interval=25)))
     ub = np.zeros((Bn, N, m))
     xb = rollout(x0, ub, dt, step)
     J = trajectory_cost(xb, ub, Q, R, QN)
@@ -309,7 +337,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         if not active.any():
             break
         p = correction_qp_batch(xb, ub, x0, dt, Q, R, QN, u_lo, u_hi, np.where(active, tru, 0.0), np.where(active, trx, 0.0), step,
-                                device=linearise_on)
+                                device=linearise_on, qp_data_on_device=qp_data_on_device)
         z, admm_iters = qp_solver(p)
         d = np.asarray(z, np.float64).reshape(Bn, N, m + n)
         du, dx = d[..., :m], d[..., m:]

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import CInfo, COptions, CProblem, c_double_p, c_int32_p, dptr, iptr
-from .problems import Problem
+from .problems import DeviceProblem, Problem, check_device_tensor
 
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _LIB_NAME = "libadmm_hip.so"
@@ -79,6 +79,12 @@ _SIGNATURES = {
     "admm_host_scan_matrices_timeshard": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p,
                                                    c_int32_p]),
     "admm_update_problem": (C.c_int, [C.c_void_p, C.POINTER(CProblem)]),
+    # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
+    "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
+    "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
+    "admm_update_instances_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_set_state_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_get_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),
@@ -116,6 +122,26 @@ def _check(lib, rc: int):
         if "non-finite entry in A, B" in msg or "non-finite entry in x0" in msg:    # what Problem.validate raises for small arrays (it leaves the large ones to the library)
             raise ValueError("non-finite problem data: " + msg)
         raise AdmmError(rc, msg)
+
+
+def _on_gpu(a) -> bool:
+    return getattr(a, "is_cuda", False) is True
+
+
+def _tptr(t):
+    """double* of a (checked) CUDA tensor; None -> NULL."""
+    return c_double_p() if t is None else C.cast(C.c_void_p(t.data_ptr()), c_double_p)
+
+
+def _stream(device):
+    """The caller's stream of the device-memory entry points: torch's current stream on `device`.  torch's default stream is the
+    null stream, which the library's non-blocking stream is not ordered against: it is synchronised here and passed as NULL (the
+    caller vouches for its data) -- what torch has queued on it (copies, transposes of marshal_device_problem) is then complete."""
+    import torch
+    s = torch.cuda.current_stream(device)
+    if not s.cuda_stream:
+        s.synchronize()
+    return C.c_void_p(s.cuda_stream)
 
 
 def last_warning() -> str:
@@ -167,9 +193,13 @@ class SolveInfo:
 
 
 class Solver:
-    """One handle = one batch of QPs on one GPU."""
+    """One handle = one batch of QPs on one GPU.
 
-    def __init__(self, problem: Problem, options: Optional[Options] = None, timeshard=None):
+    Given a DeviceProblem (torch tensors on one GPU) it is set up through admm_setup_device, and update_problem(DeviceProblem),
+    update_instances / set_state with CUDA tensors and get_device() use the device-memory entry points: the data stay on the GPU,
+    ordered on torch's current stream.  NumPy arrays take the host entry points as before."""
+
+    def __init__(self, problem, options: Optional[Options] = None, timeshard=None):
         """timeshard = (rank, nranks, exchange): a TIME-SHARDED handle (admm_setup_timeshard; sharding.TimeShardedSolver builds
         the exchange function over torch.distributed) -- `exchange` is an _abi.EXCHANGE_FN the caller keeps alive."""
         self._lib = load_library()
@@ -177,15 +207,30 @@ class Solver:
         self.problem = problem
         self.options = options or Options()
         co = self.options.to_c()
+        on_device = isinstance(problem, DeviceProblem)
+        if on_device:
+            problem.validate()
+            if timeshard is not None:
+                raise ValueError("time-sharded handles take host arrays (admm_setup_timeshard has no device-memory form)")
+            if co.device < 0:
+                co.device = problem.device.index
+            elif co.device != problem.device.index:
+                raise ValueError(f"options.device = {co.device}, but the DeviceProblem lives on {problem.device}")
+        # the handle's GPU, for the wrapper's checks of CUDA tensors (None: the current device at setup, asked for when needed)
+        self.device_index = co.device if co.device >= 0 else None
         # per-instance dynamics: NumPy's row-major blocks go to the library as they are (ADMM_FLAG_ROW_MAJOR, transposed on the
         # device); ADMM_PY_COLMAJOR=1 keeps the host transposition (the column-major path of the ABI)
         self._row_major = bool(problem.per_instance and not os.environ.get("ADMM_PY_COLMAJOR"))
         if self._row_major:
             co.flags |= _abi.FLAG_ROW_MAJOR
-        cp, keep = _abi.marshal_problem(problem, self._row_major)
-        if timeshard is None:
+        if on_device:
+            cp, keep = _abi.marshal_device_problem(problem, self._row_major)
+            _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
+        elif timeshard is None:
+            cp, keep = _abi.marshal_problem(problem, self._row_major)
             _check(self._lib, self._lib.admm_setup(C.byref(self._h), C.byref(cp), C.byref(co)))
         else:
+            cp, keep = _abi.marshal_problem(problem, self._row_major)
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -229,18 +274,46 @@ class Solver:
             raise ValueError(f"expected shape {(self.batch, rows or self.L)}, got {a.shape}")
         return a
 
+    def _device(self):
+        if self.device_index is None:
+            import torch
+            self.device_index = torch.cuda.current_device()
+        return self.device_index
+
+    def _tensors(self, **arrays):
+        """The CUDA-tensor arguments of a device-memory call, checked (ValueError before the library is called); None stays None."""
+        dev = f"cuda:{self._device()}"
+        for name, (a, cols) in arrays.items():
+            if a is not None:
+                check_device_tensor(name, a, dev, (self.batch, cols))
+        return dev
+
     # -- C ABI, one method per entry point -------------------------------
     def update_instances(self, x0=None, q=None):
+        """x0 (batch, n), q (batch, L): NumPy arrays, or CUDA tensors on the handle's GPU (admm_update_instances_device)."""
+        if _on_gpu(x0) or _on_gpu(q):
+            dev = self._tensors(x0=(x0, self.problem.n), q=(q, self.L))
+            _check(self._lib, self._lib.admm_update_instances_device(self._h, _tptr(x0), _tptr(q), _stream(dev)))
+            return
         x0 = self._vec(x0, self.problem.n)
         q = self._vec(q)
         _check(self._lib, self._lib.admm_update_instances(self._h, dptr(x0), dptr(q)))
 
-    def update_problem(self, problem: Problem):
-        """New shared data (dynamics, weights, box, x0, q) on this handle; same N, n, m, batch."""
-        cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
+    def update_problem(self, problem):
+        """New shared data (dynamics, weights, box, x0, q) on this handle; same N, n, m, batch.  A DeviceProblem on the handle's GPU
+        goes through admm_update_problem_device."""
         import time
-        t0 = time.perf_counter()
-        _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
+        if isinstance(problem, DeviceProblem):
+            problem.validate()
+            dev = f"cuda:{self._device()}"
+            check_device_tensor("x0", problem.x0, dev)
+            cp, keep = _abi.marshal_device_problem(problem, self._row_major)
+            t0 = time.perf_counter()
+            _check(self._lib, self._lib.admm_update_problem_device(self._h, C.byref(cp), _stream(dev)))
+        else:
+            cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
+            t0 = time.perf_counter()
+            _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
         self.last_update_ms = (time.perf_counter() - t0) * 1e3      # the C call alone (validation, upload, refactor)
         del keep
         self.problem = problem
@@ -251,6 +324,11 @@ class Solver:
         self._warn()
 
     def set_state(self, w=None, z=None, y=None):
+        """(batch, L) each: NumPy arrays, or CUDA tensors on the handle's GPU (admm_set_state_device)."""
+        if _on_gpu(w) or _on_gpu(z) or _on_gpu(y):
+            dev = self._tensors(w=(w, self.L), z=(z, self.L), y=(y, self.L))
+            _check(self._lib, self._lib.admm_set_state_device(self._h, _tptr(w), _tptr(z), _tptr(y), _stream(dev)))
+            return
         w, z, y = self._vec(w), self._vec(z), self._vec(y)
         _check(self._lib, self._lib.admm_set_state(self._h, dptr(w), dptr(z), dptr(y)))
 
@@ -322,6 +400,15 @@ class Solver:
     def get(self, w=True, z=True, y=True):
         outs = [np.empty((self.batch, self.L)) if f else None for f in (w, z, y)]
         _check(self._lib, self._lib.admm_get(self._h, *[dptr(o) for o in outs]))
+        return tuple(outs)
+
+    def get_device(self, w=True, z=True, y=True):
+        """The state as (batch, L) fp64 tensors on the handle's GPU (None where not asked for), written by admm_get_device and
+        ordered on torch's current stream: work queued on it afterwards sees them, without a host synchronisation."""
+        import torch
+        dev = f"cuda:{self._device()}"
+        outs = [torch.empty((self.batch, self.L), dtype=torch.float64, device=dev) if f else None for f in (w, z, y)]
+        _check(self._lib, self._lib.admm_get_device(self._h, *[_tptr(o) for o in outs], _stream(dev)))
         return tuple(outs)
 
     def profile(self, iters: int, residuals: bool = True, fused: bool = True, alternating: bool = False,

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define ADMM_HIP_ABI_VERSION 8
+#define ADMM_HIP_ABI_VERSION 9
 
 typedef enum admm_status {
   ADMM_OK = 0,
@@ -246,6 +246,28 @@ int admm_get_residuals(admm_handle* h, double* r, double* s, double* nw, double*
 
 /* Copy out the state; any pointer may be NULL.  Each is L*batch. */
 int admm_get(admm_handle* h, double* w, double* z, double* y);
+
+/* DEVICE-MEMORY forms (ABI v9): the same calls with every array pointer in device memory of the handle's GPU
+ * (admm_setup_device: of options.device, or of the current device if that is -1) -- for callers that hold their data on the GPU
+ * already (torch tensors, hipMalloc'd arrays): nothing crosses PCIe but the small arrays below.  Sizes, layouts, NULL rules, flags
+ * (ADMM_FLAG_ROW_MAJOR included) and the data checks are those of the host forms, with the same status and message for the same
+ * data; on failure nothing of the handle has changed.  Any alignment of 8 bytes or more is accepted (a view at an offset).
+ *   - Every non-NULL pointer is checked with hipPointerGetAttributes: pageable or pinned host memory, another GPU's memory, or an
+ *     allocation shorter than the array gives ADMM_ERR_INVALID with a message naming the argument.
+ *   - hip_stream is the caller's stream (a hipStream_t).  The library's stream waits for what the caller has queued on it before
+ *     reading (or, admm_get_device, writing) the caller's arrays.  hip_stream = NULL: the caller vouches that its data are ready.
+ *   - The input calls (setup, update_problem, update_instances, set_state) return once the caller's arrays have been consumed:
+ *     the caller may overwrite or free them then.  admm_get_device returns WITHOUT a host synchronisation: hip_stream waits for the
+ *     library's writes (work queued on it afterwards sees the state); with hip_stream = NULL it returns with the writes complete.
+ *   - The per-instance arrays (A, B of time_varying = 2, the box of stage_bounds = 2, x0, q, w, z, y) are read on the device, the
+ *     large ones checked there in one pass; the small ones (Q, R, QN, unorm, batch-shared A, B and box) are copied to the host
+ *     (the host factorisation of batch-shared dynamics needs them there).
+ *   - Time-sharded handles (admm_setup_timeshard): ADMM_ERR_UNSUPPORTED from each of the four calls on a handle. */
+int admm_setup_device(admm_handle** out, const admm_problem* p, const admm_options* o, void* hip_stream);
+int admm_update_problem_device(admm_handle* h, const admm_problem* p, void* hip_stream);
+int admm_update_instances_device(admm_handle* h, const double* x0, const double* q, void* hip_stream);
+int admm_set_state_device(admm_handle* h, const double* w, const double* z, const double* y, void* hip_stream);
+int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_stream);
 
 /* Per-QP results of the last admm_solve: first checked iteration at which the
  * rule held (max_iter if never), status (1 converged / 0 not), last r and s. */
