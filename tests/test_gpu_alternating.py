@@ -4,6 +4,8 @@ substitution sweep is fused with the next elimination sweep.  It is the default 
 the forward form passes its host check (practically always); ADMM_FLAG_NO_ALTERNATE (8) selects the
 plain xb + xfz kernels.  Checked against the C oracle (PARITY UNPINNED, see test_gpu_parity.py)
 and against the plain path, tolerance 1e-10 on O(1) iterates."""
+from contextlib import nullcontext
+
 import numpy as np
 import pytest
 
@@ -11,7 +13,8 @@ import admm_library_amd as pkg
 from admm_library_amd import _abi
 import oracle_c as oc
 
-pytestmark = pytest.mark.gpu
+# a handle that silently leaves the alternating kernels is an error (the cases that fall back say so, below)
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error:.*forward-elimination form failed:RuntimeWarning")]
 TOL = 1e-10
 NO_ALT = _abi.FLAG_NO_ALTERNATE
 
@@ -33,7 +36,8 @@ ALT_CASES = [
     (lambda: pkg.random_ltv(N=20, n=9, m=3, batch=5, seed=54, with_q=False), 0.3, 2),
     (lambda: pkg.random_ltv(N=20, n=10, m=4, batch=5, seed=55, with_q=False), 0.3, 2),
     (lambda: pkg.random_ltv(N=40, n=12, m=3, batch=4, seed=16, with_q=False), 0.2, 3),
-    (lambda: pkg.random_ltv(N=40, n=12, m=6, batch=3, seed=17, with_q=False), 0.4, 2),
+    (lambda: pkg.random_ltv(N=40, n=12, m=6, batch=3, seed=17, with_q=False), 0.4, 2),        # (fails the probe: ALT_EXPECT_PLAIN)
+    (lambda: pkg.random_ltv(N=40, n=12, m=6, batch=3, seed=18, with_q=False), 0.4, 2),        # the same shape, passing it
     (lambda: pkg.cw_formation(N=120, batch=66), 0.05, 0),
     # with a linear term q (per-stage bounds, full weights): the HASQ kernel forms
     (lambda: pkg.random_ltv(N=37, n=6, m=3, batch=70, seed=2), 0.3, 5),
@@ -45,6 +49,7 @@ ALT_CASES = [
     (lambda: pkg.random_ltv(N=37, n=6, m=3, batch=9, seed=31, thrust_norm=True), 0.3, 5),
     (lambda: pkg.random_ltv(N=20, n=4, m=2, batch=5, seed=32, thrust_norm=True, with_q=False), 0.3, 3),
 ]
+ALT_EXPECT_PLAIN = {15}          # ALT_CASES whose problem fails the forward-elimination probe: plain kernels, with a warning
 
 
 def _close(a, b):
@@ -62,7 +67,12 @@ def test_alternating_iterates_match_oracle(gpu, idx):
         # FLAG_NO_MFMA: the one-lane kernels this file is about (for small batches of q-free problems of an
         # MFMA-compiled shape the default is the fp64 MFMA form, tests/test_gpu_mfma.py)
         for flags in (0, _abi.FLAG_NO_MFMA, _abi.FLAG_NO_MFMA | _abi.FLAG_GRAPH):
-            with pkg.Solver(p, pkg.Options(rho=rho, segments=segs, flags=flags)) as s:
+            with pytest.warns(RuntimeWarning, match="forward-elimination") if idx in ALT_EXPECT_PLAIN else nullcontext():
+                s = pkg.Solver(p, pkg.Options(rho=rho, segments=segs, flags=flags))
+            with s:
+                assert s.path()["alternating"] == (idx not in ALT_EXPECT_PLAIN)
+                if flags:
+                    assert s.path()["kernel_family"] == "one_lane_fp64"
                 s.iterate(K)
                 w, z, y = s.get()
             assert _close(w, ref["w"]) and _close(z, ref["z"]) and _close(y, ref["y"]), (K, flags)
@@ -93,7 +103,10 @@ def test_falls_back_to_the_plain_kernels_when_the_forward_form_is_unavailable(gp
     A = np.array(p.A)
     A[5] = np.diag([1.0, 0.0, 0.5])
     p = pkg.Problem(N=p.N, A=A, B=p.B, Q=p.Q, R=p.R, QN=p.QN, x0=p.x0, lo=p.lo, hi=p.hi)
-    with pkg.Solver(p, pkg.Options(rho=0.3, segments=3)) as s:
+    with pytest.warns(RuntimeWarning, match="forward-elimination"):
+        s = pkg.Solver(p, pkg.Options(rho=0.3, segments=3))
+    with s:
+        assert not s.path()["alternating"] and s.path()["alt_requested"]
         with pytest.raises(pkg.AdmmError):
             s.profile(1, alternating=True)
         s.iterate(9)
@@ -163,9 +176,14 @@ def test_update_problem_equals_a_fresh_handle(gpu):
     p1 = pkg.random_ltv(N=33, n=6, m=3, batch=20, seed=41)
     p2 = pkg.random_ltv(N=33, n=6, m=3, batch=20, seed=42)
     zero = np.zeros((p2.batch, p2.L))
+    # (p2 fails the forward-elimination probe: the update moves the handle from the alternating kernels to the plain ones, and
+    # says so, as a fresh handle of p2 does)
     with pkg.Solver(p1, pkg.Options(rho=0.3, segments=4)) as s:
+        assert s.path()["alternating"]
         s.run(7, residual_every=1)
-        s.update_problem(p2)
+        with pytest.warns(RuntimeWarning, match="forward-elimination"):
+            s.update_problem(p2)
+        assert not s.path()["alternating"]
         s.set_state(z=zero, y=zero)
         s.run(12, residual_every=1)
         got = s.get() + tuple(s.residuals())
@@ -175,7 +193,10 @@ def test_update_problem_equals_a_fresh_handle(gpu):
         with pytest.raises(pkg.AdmmError):
             s.update_problem(pkg.random_ltv(N=33, n=6, m=3, batch=20, seed=42, with_q=False))
         s.iterate(2)
-    with pkg.Solver(p2, pkg.Options(rho=0.3, segments=4)) as s:
+    with pytest.warns(RuntimeWarning, match="forward-elimination"):
+        s = pkg.Solver(p2, pkg.Options(rho=0.3, segments=4))
+    with s:
+        assert not s.path()["alternating"]
         s.run(12, residual_every=1)
         want = s.get() + tuple(s.residuals())
         info2 = s.solve(z0=zero, y0=zero)

@@ -15,7 +15,8 @@ import pytest
 import admm_library_amd as pkg
 import oracle_c as oc
 
-pytestmark = pytest.mark.gpu
+# a handle that silently leaves the default path is an error
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error:.*forward-elimination form failed:RuntimeWarning")]
 TOL = 1e-10
 
 
@@ -32,6 +33,7 @@ def test_config1_iterates_default_path(gpu, flags):
     this small is the fp64 MFMA form of the fused kernels; ADMM_FLAG_NO_MFMA = the one-lane kernels."""
     p = pkg.cw_rendezvous(N=1000, batch=1)
     with pkg.Solver(p, pkg.Options(rho=0.05, flags=flags)) as s:
+        assert (s.path()["alternating"], s.path()["kernel_family"]) == (True, "one_lane_fp64" if flags else "mfma_fp64")
         geo = s.geometry()
         assert geo["segments"] > 1                       # the parallel-in-time form really runs
         done = 0
@@ -52,6 +54,7 @@ def test_config1_solve_default_path(gpu, flags):
     kw = dict(rho=0.05, eps_abs=1e-6, eps_rel=1e-6, max_iter=4000, check_interval=10)
     ref = oc.solve(p, **kw)
     with pkg.Solver(p, pkg.Options(flags=flags, **kw)) as s:
+        assert (s.path()["alternating"], s.path()["kernel_family"]) == (True, "one_lane_fp64" if flags else "mfma_fp64")
         info = s.solve()
         w, z, y = s.get()
     assert int(info.iters_run) == int(ref["iters_run"])

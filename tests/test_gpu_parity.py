@@ -6,6 +6,8 @@ variables scaled to O(1).  The oracle is the build's own CPU restatement
 (PARITY UNPINNED: the reference ships no code or fixtures), and it
 uses the plain sequential Riccati sweep, not the segmented form of the kernels.
 """
+from contextlib import nullcontext
+
 import numpy as np
 import pytest
 
@@ -13,8 +15,26 @@ import admm_library_amd as pkg
 import admm_ref as ar
 import oracle_c as oc
 
-pytestmark = pytest.mark.gpu
+# a handle that silently leaves the path a test names is an error (cases that fall back are marked, below)
+pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error:.*forward-elimination form failed:RuntimeWarning")]
 TOL = 1e-10
+PLAIN_FLAGS = 2 | 4 | 8          # ADMM_FLAG_UNFUSED / _SCAN_CHAIN / _NO_ALTERNATE: the alternating kernels are not requested
+
+
+def _solver(p, opts, expect_plain):
+    """Set up a handle; expect_plain: the problem fails the forward-elimination probe, so where the alternating kernels are
+    requested the handle must say so (warning) and run the plain fused ones."""
+    requested = not opts.flags & PLAIN_FLAGS
+    with pytest.warns(RuntimeWarning, match="forward-elimination") if expect_plain and requested else nullcontext():
+        s = pkg.Solver(p, opts)
+    path = s.path()
+    assert path["alternating"] == (requested and not expect_plain), path
+    # the fp64 MFMA form is the default at its pairs for small batches (admm_api.hip), a linear term at (6, 3) only
+    pitch = (p.batch + 63) // 64 * 64
+    mfma = ((p.n, p.m) in ((6, 3), (10, 4), (12, 6)) and (p.q is None or ((p.n, p.m) == (6, 3) and pitch <= 128))
+            and p.unorm is None and path["alternating"] and not opts.flags & 32 and (pitch <= 64 or (p.n >= 9 and pitch <= 128)))
+    assert path["kernel_family"] == ("mfma_fp64" if mfma else "one_lane_fp64"), path
+    return s
 
 
 def _g(p, z, y, rho):
@@ -53,7 +73,12 @@ CASES = [
     (lambda: pkg.random_ltv(N=1, n=4, m=2, batch=3, seed=18), 0.3, 0),
     (lambda: pkg.random_ltv(N=2, n=6, m=3, batch=2, seed=19), 0.3, 0),
     (lambda: pkg.random_ltv(N=3, n=2, m=1, batch=129, seed=20), 0.3, 3),
+    # cases 13 - 15 fail the forward-elimination probe (EXPECT_PLAIN): the same shapes with problems that pass it
+    (lambda: pkg.random_ltv(N=11, n=6, m=2, batch=4, seed=18), 0.2, 2),
+    (lambda: pkg.random_ltv(N=11, n=12, m=3, batch=4, seed=18), 0.2, 2),
+    (lambda: pkg.random_ltv(N=40, n=12, m=6, batch=3, seed=18), 0.4, 2),
 ]
+EXPECT_PLAIN = {13, 14, 15}      # CASES that run the plain fused kernels (forward-elimination probe failed, with a warning)
 
 
 @pytest.mark.parametrize("flags", [0, 4], ids=["scan_mfma", "scan_chain"])
@@ -66,7 +91,8 @@ def test_x_update_kernels(gpu, idx, flags):
     rng = np.random.default_rng(100 + idx)
     z = rng.standard_normal((p.batch, p.L))
     y = rng.standard_normal((p.batch, p.L))
-    with pkg.Solver(p, pkg.Options(rho=rho, segments=segs, flags=flags)) as s:
+    with _solver(p, pkg.Options(rho=rho, segments=segs, flags=flags), idx in EXPECT_PLAIN) as s:
+        assert s.path()["scan_form"] == ("sequential_chain" if flags & 4 else "matrix_vector" if p.batch <= 4 else "mfma_gemm")
         s.set_state(z=z, y=y)
         s.step_x()
         w, z2, y2 = s.get()
@@ -113,7 +139,7 @@ def test_zdual_kernel(gpu, alpha, resid):
 
 
 @pytest.mark.parametrize("flags", [0, 32, 8, 2], ids=["default", "one_lane", "fused_plain", "unfused"])
-@pytest.mark.parametrize("idx", [0, 1, 3, 5, 7, 9, 15, 16, 17, 18, 20])
+@pytest.mark.parametrize("idx", [0, 1, 3, 5, 7, 9, 15, 16, 17, 18, 20, 28])
 def test_iterate_parity(gpu, idx, flags):
     """T4: iterates of the full loop vs the C oracle after 1, 2, 10, 40 iterations, on the
     default path (the alternating-direction kernels where compiled, tests/test_gpu_alternating.py,
@@ -121,7 +147,7 @@ def test_iterate_parity(gpu, idx, flags):
     ADMM_FLAG_UNFUSED path (xb, xscan, xf, zdual).  w is re-materialised by admm_get on the fused paths."""
     make, rho, segs = CASES[idx]
     p = make()
-    with pkg.Solver(p, pkg.Options(rho=rho, segments=segs, flags=flags)) as s:
+    with _solver(p, pkg.Options(rho=rho, segments=segs, flags=flags), idx in EXPECT_PLAIN) as s:
         done = 0
         for upto in (1, 2, 10, 40):
             s.iterate(upto - done)
@@ -242,7 +268,9 @@ SOC_CASES = [
     (lambda: pkg.random_ltv(N=31, n=4, m=2, batch=66, seed=4, thrust_norm=True), 0.3, 1.5),
     (lambda: pkg.random_ltv(N=12, n=12, m=6, batch=3, seed=5, thrust_norm=True), 0.5, 1.0),
     (lambda: pkg.random_ltv(N=9, n=3, m=1, batch=4, seed=6, thrust_norm=True), 0.5, 1.2),   # m = 1: |u| <= ub
+    (lambda: pkg.random_ltv(N=12, n=12, m=6, batch=3, seed=6, thrust_norm=True), 0.5, 1.0),  # case 3's shape, passing the probe
 ]
+SOC_EXPECT_PLAIN = {3}           # (fails the forward-elimination probe: the plain fused kernels, with a warning)
 
 
 @pytest.mark.parametrize("flags", [0, 2], ids=["fused", "unfused"])
@@ -253,7 +281,7 @@ def test_thrust_magnitude_constraint(gpu, idx, flags):
     unfused (block-structured standalone kernels) paths."""
     make, rho, alpha = SOC_CASES[idx]
     p = make()
-    with pkg.Solver(p, pkg.Options(rho=rho, alpha=alpha, flags=flags)) as s:
+    with _solver(p, pkg.Options(rho=rho, alpha=alpha, flags=flags), idx in SOC_EXPECT_PLAIN) as s:
         done = 0
         for upto in (1, 2, 9, 30):
             s.run(upto - done, residual_every=3)
@@ -269,7 +297,7 @@ def test_thrust_magnitude_constraint(gpu, idx, flags):
     assert (nr <= un[None] * (1 + 1e-14)).all()
     kw = dict(rho=rho, alpha=alpha, eps_abs=1e-6, eps_rel=1e-6, max_iter=1500, check_interval=10)
     ref = oc.solve(p, **kw)
-    with pkg.Solver(p, pkg.Options(flags=flags, **kw)) as s:
+    with _solver(p, pkg.Options(flags=flags, **kw), idx in SOC_EXPECT_PLAIN) as s:
         info = s.solve()
         _, z, _ = s.get(False, True, False)
     assert info.iters_run == ref["iters_run"] and info.n_converged == int(ref["status"].sum())
