@@ -127,6 +127,11 @@ def marshal_problem(p: Problem, row_major: bool = False):
     return cp, keep
 
 
+def marshal_fuel(p: Problem):
+    """The weights of p.fuel as admm_setup_fuel / admm_set_fuel read them (unorm's shape rule): (N,) with per-stage bounds, else (1,)."""
+    return np.array(np.broadcast_to(np.asarray(p.fuel, np.float64), (p.N,) if p.lo.ndim >= 2 else (1,)), np.float64)
+
+
 def marshal_device_problem(p, row_major: bool = False):
     """marshal_problem of a DeviceProblem (validated here): the CProblem holds device pointers.  The layout work marshal_problem does
     on the host -- column-major matrices, the broadcast of unorm -- is done by torch on the tensors' GPU (copies on the current

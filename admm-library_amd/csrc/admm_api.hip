@@ -135,8 +135,10 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
 
 // dev_src (admm_setup_device): p is a DeviceProblem's view -- small arrays on the host, the per-instance ones device memory, checked by
 // the device-side findings `scan`
+// fuel (admm_setup_fuel): the weights of the minimum-fuel term, in unorm's shape; NULL = none
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
-                        admm_exchange_fn ts_fn, void* ts_ctx, bool dev_src = false, const DeviceScan* scan = nullptr) {
+                        admm_exchange_fn ts_fn, void* ts_ctx, bool dev_src = false, const DeviceScan* scan = nullptr,
+                        const double* fuel = nullptr) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   g_warn.clear();
@@ -145,6 +147,14 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   int rc;
   if ((rc = validate_options(&o))) return rc;
   if ((rc = validate_problem(p, scan))) return rc;
+  if (fuel) {
+    if ((rc = validate_fuel(p, fuel, false))) return rc;
+    // the shrink-and-scale projection is built into the one-lane fp64 kernels of batch-shared dynamics only
+    if (p->time_varying == 2) return fail(ADMM_ERR_UNSUPPORTED, "a fuel term needs batch-shared dynamics (time_varying = 0 or 1)");
+    if (o.precision_mode != ADMM_PRECISION_FP64)
+      return fail(ADMM_ERR_UNSUPPORTED, "precision_mode " + std::to_string(o.precision_mode) + ": a fuel term is not supported by the MFMA forms (use ADMM_PRECISION_FP64)");
+    if (ts_n) return fail(ADMM_ERR_UNSUPPORTED, "a fuel term is not supported on time-sharded handles");
+  }
   if (ts_n) {
     if (ts_n < 1 || ts_rank < 0 || ts_rank >= ts_n) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: need 0 <= rank < nranks");
     if (ts_n > 1 && !ts_fn) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: an exchange function is needed with more than one rank");
@@ -178,7 +188,12 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   h->wk0 = 0; h->wk1 = p->N;           // stage window of the big arrays: the whole horizon unless this becomes a time shard (below)
   h->pitch = ((p->batch + 63) / 64) * 64;
   h->has_q = p->q != nullptr;
-  h->has_soc = problem_has_soc(p);
+  h->has_soc = problem_has_soc(p) || fuel != nullptr;      // a fuel handle runs the SOC forms with or without a thrust bound
+  if (fuel) {
+    h->has_fuel = true;
+    h->fuel.resize(p->N);
+    for (int k = 0; k < p->N; ++k) h->fuel[k] = fuel[p->stage_bounds ? k : 0];
+  }
   if ((h->opt.flags & ADMM_FLAG_ROW_MAJOR) && p->time_varying != 2) {
     release(h);
     return fail(ADMM_ERR_UNSUPPORTED, "ADMM_FLAG_ROW_MAJOR: per-instance dynamics only (time_varying = 2)");
@@ -252,7 +267,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     if (!compiled) why = "(n, m) has no MFMA instantiation; compiled: " + std::string(admm::dims_mfma());
     else if (h->has_q && !(p->n == 6 && p->m == 3 && h->pitch <= 128 && o.precision_mode != ADMM_PRECISION_MIXED))
       why = "a linear term q is supported by the fp64 MFMA forms of (6, 3) for batches of up to 128 QPs only";
-    else if (h->has_soc) why = "a thrust-magnitude bound is not supported by the MFMA forms";
+    else if (h->has_soc) why = "a thrust-magnitude bound or fuel term is not supported by the MFMA forms";
     else if (o.flags & (ADMM_FLAG_UNFUSED | ADMM_FLAG_SCAN_CHAIN)) why = "ADMM_FLAG_UNFUSED / ADMM_FLAG_SCAN_CHAIN exclude the MFMA forms";
     if (o.precision_mode != ADMM_PRECISION_FP64) {
       if (!why.empty()) { release(h); return fail(ADMM_ERR_UNSUPPORTED, "precision_mode " + std::to_string(o.precision_mode) + ": " + why); }
@@ -271,7 +286,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   h->scan_gemv = h->batch <= admm::SCAN_GEMV_MAXCOLS && !(o.flags & ADMM_FLAG_SCAN_CHAIN) &&
                  std::getenv("ADMM_NO_GEMV_SCAN") == nullptr;
   std::string err;
-  rc = admm::factorise(*p, o.rho, h->S, h->fac, err, h->mfma_mode, !h->scan_gemv, ts_n);
+  rc = admm::factorise(*p, o.rho, h->S, h->fac, err, h->mfma_mode, !h->scan_gemv, ts_n, fuel_of(h));
   if (rc) { release(h); return fail(rc, err); }
   // Conditioning guard of the parallel-in-time form: the segment coupling is exact in exact
   // arithmetic, but its transfer matrices are products of closed-loop matrices, and for a barely
@@ -288,7 +303,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   if (o.segments == 0 && !ts_n) {
     while (h->fac.S > 1 && scan_growth(h->fac) > SCAN_GROWTH_MAX) {
       const int S2 = std::max(1, h->fac.S / 2);
-      rc = admm::factorise(*p, o.rho, S2, h->fac, err, h->mfma_mode, !h->scan_gemv);
+      rc = admm::factorise(*p, o.rho, S2, h->fac, err, h->mfma_mode, !h->scan_gemv, 0, fuel_of(h));
       if (rc) { release(h); return fail(rc, err); }
     }
   }
@@ -411,6 +426,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   TRY_RELEASE(dalloc(&h->lo, L));
   TRY_RELEASE(dalloc(&h->hi, L));
   TRY_RELEASE(dalloc(&h->ub, (size_t)h->N));
+  TRY_RELEASE(dalloc(&h->kap, (size_t)h->N));
   TRY_RELEASE(dalloc(&h->recB, h->fac.recB.size()));
   TRY_RELEASE(dalloc(&h->recF, h->fac.recF.size()));
   TRY_RELEASE(dalloc(&h->recS, h->fac.recS.size()));
@@ -455,6 +471,38 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
 
 int admm_setup(admm_handle** out, const admm_problem* p, const admm_options* o) {
   return setup_common(out, p, o, 0, 0, nullptr, nullptr);
+}
+
+int admm_setup_fuel(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel) {
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, false, nullptr, fuel);
+}
+
+int admm_get_fuel(admm_handle* h, double* fuel) {
+  if (!h || !fuel) return fail(ADMM_ERR_INVALID, "NULL argument");
+  for (int k = 0; k < h->N; ++k) fuel[k] = h->has_fuel ? h->fuel[k] : 0.0;
+  return ADMM_OK;
+}
+
+// New weights on a fuel handle: nothing of the handle is written before every check has passed.  The state is switched to the
+// (z, y) pair (as admm_set_rho does): v alone would be read back through the NEW prox.
+int admm_set_fuel(admm_handle* h, const double* fuel) {
+  if (!h || !fuel) return fail(ADMM_ERR_INVALID, "NULL argument");
+  g_warn.clear();
+  if (!h->has_fuel) return fail(ADMM_ERR_INVALID, "admm_set_fuel: a fuel term cannot be added to a handle (set it up with admm_setup_fuel)");
+  HIP_TRY(hipSetDevice(h->device));
+  const admm_problem p = shared_problem(h);
+  int rc;
+  if ((rc = validate_fuel(&p, fuel, false))) return rc;
+  if ((rc = ensure_w(h))) return rc;          // w of the last x-update belongs to the old records
+  if ((rc = ensure_zy(h))) return rc;
+  h->zy_valid = true;
+  h->v_valid = false;
+  HIP_TRY(hipStreamSynchronize(h->stream));   // kernels of the old weights are done before the records change
+  h->spec.clear();                            // candidate factors of the adaptive rule carry the old weights (joins their threads)
+  h->spec_stale.clear();
+  for (int k = 0; k < h->N; ++k) h->fuel[k] = fuel[h->stage_bounds ? k : 0];
+  admm::fill_fuel(h->fac, h->fuel.data());
+  return upload_factor(h);
 }
 
 int admm_setup_device(admm_handle** out, const admm_problem* p, const admm_options* o, void* hip_stream) {

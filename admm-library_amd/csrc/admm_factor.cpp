@@ -995,9 +995,27 @@ static int factorise_impl(const admm_problem& p, double rho, int segments, Facto
 }
 
 // No exception leaves the factorisation (C ABI above it; worker threads below it -- parallel_for rethrows theirs here).
-int factorise(const admm_problem& p, double rho, int segments, Factor& f, std::string& err, int mfma_mode, bool pack_scan_mfma, int ts_ranks) {
+void fill_fuel(Factor& f, const double* fuel) {
+  const int ub_b = rec_b_layout(f.n, f.m).UB, ub_f = rec_f_layout(f.n, f.m).UB;
+  const int ub_fe = rec_fe_layout(f.n, f.m).UB, ub_be = rec_be_layout(f.n, f.m).UB;
+  const bool alt = f.alt_ok && f.recFE.size() == (size_t)f.N * f.RFE && f.recBE.size() == (size_t)f.N * f.RBE;
+  for (int k = 0; k < f.N; ++k) {
+    const double kap = fuel ? fuel[k] / f.rho : 0.0;
+    f.recB[(size_t)k * f.RB + ub_b + 1] = kap;
+    f.recF[(size_t)k * f.RF + ub_f + 1] = kap;
+    if (alt) {
+      f.recFE[(size_t)k * f.RFE + ub_fe + 1] = kap;
+      f.recBE[(size_t)k * f.RBE + ub_be + 1] = kap;
+    }
+  }
+}
+
+int factorise(const admm_problem& p, double rho, int segments, Factor& f, std::string& err, int mfma_mode, bool pack_scan_mfma, int ts_ranks,
+              const double* fuel) {
   try {
-    return factorise_impl(p, rho, segments, f, err, mfma_mode, pack_scan_mfma, ts_ranks);
+    const int rc = factorise_impl(p, rho, segments, f, err, mfma_mode, pack_scan_mfma, ts_ranks);
+    if (rc == ADMM_OK) fill_fuel(f, fuel);
+    return rc;
   } catch (const std::bad_alloc&) {
     err = "out of host memory in the KKT factorisation";
     return ADMM_ERR_ALLOC;

@@ -112,8 +112,12 @@ inline int rec_be_size(int n, int m) { return rec_be_layout(n, m).SIZE; }
 //   [ rank 0: tseg of its S / ts_ranks segments | eseg of them ] [ rank 1: ... ] ... | x0 | pad
 // instead of tseg(0..S-1) | x0 | eseg(0..S-1), so that the segment summaries of all ranks are completed by ONE all-gather of
 // contiguous, equal slices (the columns of scanW / scanWB are permuted accordingly before they are packed).
+// fuel != NULL (N entries, the per-stage weights f_k of the minimum-fuel term sum_k f_k ||u_k||_2): the
+// records carry kappa_k = f_k / rho beside the thrust bound; NULL leaves that entry 0.
 int factorise(const admm_problem& p, double rho, int segments, Factor& out, std::string& err, int mfma_mode = 0,
-              bool pack_scan_mfma = true, int ts_ranks = 0);
+              bool pack_scan_mfma = true, int ts_ranks = 0, const double* fuel = nullptr);
+// kappa_k = fuel[k] / f.rho into the four record sets of f (fuel = NULL: zeros): what factorise does, for a change of the weights alone
+void fill_fuel(Factor& f, const double* fuel);
 
 // The per-stage / per-segment loops of factorise run on host threads (ADMM_FACTOR_THREADS, default min(cores, 16)); this
 // caps the count for factorisations started from the calling thread (0 = no cap).  Used by the background refactors of

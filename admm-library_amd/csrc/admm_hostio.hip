@@ -392,7 +392,7 @@ void release(admm_handle* h) {
   for (double** b : {&h->dbuf, &h->mvec})
     if (*b) *b += win_bias_m(h);
   double** bufs[] = {&h->w, &h->z, &h->y, &h->v, &h->q, &h->dbuf, &h->scan_in, &h->scan_out, &h->scanWp,
-                     &h->part, &h->resid, &h->lo, &h->hi, &h->ub, &h->recB, &h->recF, &h->recS, &h->stage,
+                     &h->part, &h->resid, &h->lo, &h->hi, &h->ub, &h->kap, &h->recB, &h->recF, &h->recS, &h->stage,
                      &h->recFE, &h->recBE, &h->mvec, &h->scanWpB};
   for (auto b : bufs)
     if (*b) { (void)hipFree(*b); *b = nullptr; }
@@ -475,6 +475,7 @@ int upload_factor(admm_handle* h) {
       HIP_TRY(hipMemcpy(h->recMB64, h->fac.recMB64.data(), h->fac.recMB64.size(), hipMemcpyHostToDevice));
     }
   }
+  if (h->has_fuel && (rc = upload_kappa(h))) return rc;             // kappa = weight / rho follows every refactor
   if (h->alt_allowed) {
     HIP_TRY(hipMemcpy(h->recFE, h->fac.recFE.data(), sizeof(double) * h->fac.recFE.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->recBE, h->fac.recBE.data(), sizeof(double) * h->fac.recBE.size(), hipMemcpyHostToDevice));
@@ -502,6 +503,17 @@ int upload_bounds(admm_handle* h, const admm_problem* p) {
     for (int k = 0; k < h->N; ++k) ub[k] = p->unorm[p->stage_bounds ? k : 0];
   HIP_TRY(hipMemcpyAsync(h->ub, ub.data(), sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
+  return upload_kappa(h);
+}
+
+// kappa_k = fuel weight / rho per stage (zeros without a fuel term), for the block-structured z kernels: the same quotient as
+// in the records (admm::fill_fuel)
+int upload_kappa(admm_handle* h) {
+  std::vector<double> kap(h->N, 0.0);
+  if (h->has_fuel)
+    for (int k = 0; k < h->N; ++k) kap[k] = h->fuel[k] / h->fac.rho;
+  HIP_TRY(hipMemcpyAsync(h->kap, kap.data(), sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return ADMM_OK;
 }
 
@@ -526,6 +538,24 @@ void keep_shared(admm_handle* h, const admm_problem* p) {
     for (int r = h->m; open && r < h->nb; ++r)
       open = p->lo[k * h->nb + r] == -INFINITY && p->hi[k * h->nb + r] == INFINITY;
   h->xfree = open;
+}
+
+// The weights of the minimum-fuel term sum_k f_k ||u_k||_2 (admm_setup_fuel) against a validated problem:
+// per_stage = false: `fuel` has unorm's shape (1 entry with stage_bounds = 0, else N); true: N entries (a handle's own copy).
+int validate_fuel(const admm_problem* p, const double* fuel, bool per_stage) {
+  const int cnt = (per_stage || p->stage_bounds) ? p->N : 1;
+  for (int k = 0; k < cnt; ++k)
+    if (!std::isfinite(fuel[k]) || !(fuel[k] >= 0.0)) return fail(ADMM_ERR_INVALID, "fuel entries must be finite and >= 0");
+  if (p->stage_bounds == 2) return ADMM_OK;         // (per-instance box: refused with per-instance dynamics by the caller)
+  const int nb = p->n + p->m;
+  for (int k = 0; k < p->N; ++k) {
+    if (!(fuel[cnt == 1 ? 0 : k] > 0.0)) continue;
+    const size_t o = p->stage_bounds ? (size_t)k * nb : 0;
+    for (int j = 0; j < p->m; ++j)
+      if (std::isfinite(p->lo[o + j]) || std::isfinite(p->hi[o + j]))
+        return fail(ADMM_ERR_INVALID, "control rows must be unbounded (-inf, inf) where fuel is positive");
+  }
+  return ADMM_OK;
 }
 
 bool problem_has_soc(const admm_problem* p) {

@@ -269,17 +269,23 @@ __device__ __forceinline__ void dpp_matvec_acc(const double (&v)[NREG], const do
 }
 
 // Thrust-magnitude (second-order-cone) projection factor of one block: the control
-// rows u of a stage with a finite bound ub are scaled onto the ball ||u||_2 <= ub,
-//     c = ||u|| > ub ? ub / ||u|| : 1,      z_u = c u.
-// sqrt and the division are the correctly rounded fp64 forms, accumulated in row order with fma --
-// the same operations as the CPU oracle.
+// rows u of a stage with a thrust bound ub and a fuel weight f (kap = f / rho; cost term f ||u||_2)
+// are shrunk by kap, then scaled onto the ball ||u||_2 <= ub,
+//     t = min(ub, max(||u|| - kap, 0)),     c = ||u|| > t ? t / ||u|| : 1,      z_u = c u.
+// kap = 0 is the plain ball projection (t = min(ub, ||u||); ||u|| > t iff ||u|| > ub), and kap = 0 with
+// ub = +inf gives c = 1 exactly; ||u|| <= kap gives c = 0: a coast stage.  sqrt and the division are the
+// correctly rounded fp64 forms, accumulated in row order with fma -- the same operations as the CPU oracle.
+__device__ __forceinline__ double soc_factor(double nrm, double ub, double kap) {
+  const double t = fmin(ub, fmax(nrm - kap, 0.0));
+  return nrm > t ? t / nrm : 1.0;
+}
+
 template <int NU, int NB>
-__device__ __forceinline__ double soc_scale(const double (&vblk)[NB], double ub) {
+__device__ __forceinline__ double soc_scale(const double (&vblk)[NB], double ub, double kap) {
   double ss = 0.0;
 #pragma unroll
   for (int j = 0; j < NU; ++j) ss = fma(vblk[j], vblk[j], ss);
-  const double nrm = sqrt(ss);
-  return nrm > ub ? ub / nrm : 1.0;
+  return soc_factor(sqrt(ss), ub, kap);
 }
 
 // ---------------------------------------------------------------------------
@@ -399,7 +405,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xb_kernel(
           // compiled only for problems with a thrust-magnitude bound.  Branch-free: ub = +inf (no bound at this
           // stage) gives cs = 1 exactly, and where ub is finite the control rows' box is (-inf, inf), so
           // clip(cs v_u) is the ball projection there and the box projection elsewhere (see xfze_kernel)
-          if (SOC) cs = soc_scale<NU, NB>(lz[j], rb[LB.UB]);
+          if (SOC) cs = soc_scale<NU, NB>(lz[j], rb[LB.UB], rb[LB.UB + 1]);
         }
         double g[NB];
 #pragma unroll
@@ -1169,8 +1175,8 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xfz_kernel(
         // factors = 1 exactly; where ub is finite the control rows' box is (-inf, inf) (see xfze_kernel)
         double cs_old = 1.0, cs_new = 1.0;
         if constexpr (SOC) {
-          const double ub = rf[LF.UB];
-          if (VIN) cs_old = soc_scale<NU, NB>(c0, ub);
+          const double ub = rf[LF.UB], kap = rf[LF.UB + 1];
+          if (VIN) cs_old = soc_scale<NU, NB>(c0, ub, kap);
           if (RESID) {                           // z+ needs ||v+_u||: form the control rows of v+ first
             double vnew[NB];
 #pragma unroll
@@ -1186,7 +1192,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xfz_kernel(
                 vnew[r] = 0.0;
               }
             }
-            cs_new = soc_scale<NU, NB>(vnew, ub);
+            cs_new = soc_scale<NU, NB>(vnew, ub, kap);
           }
         }
 #pragma unroll
@@ -1414,18 +1420,17 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
 // over its m control rows for ||v_u|| (the re-read hits L1/L2), once to apply.  Unfused path and
 // read-out only; the fused xfz / xb kernels do the same work on register-resident blocks.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ double2 soc_scale2(double2 ss, double ub) {
+__device__ __forceinline__ double2 soc_scale2(double2 ss, double ub, double kap) {
   double2 c;
-  const double nx = sqrt(ss.x), ny = sqrt(ss.y);
-  c.x = nx > ub ? ub / nx : 1.0;
-  c.y = ny > ub ? ub / ny : 1.0;
+  c.x = soc_factor(sqrt(ss.x), ub, kap);
+  c.y = soc_factor(sqrt(ss.y), ub, kap);
   return c;
 }
 
 template <bool RESID, bool RELAX>
 __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
     const double* __restrict__ w, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_,
+    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_, const double* __restrict__ kap_,
     double* __restrict__ part, double alpha, int L, int zrows, int pitch, int nb, int m) {
   const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
   if (col >= pitch) return;
@@ -1436,10 +1441,11 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
   cdouble_p lo = as_const(lo_);
   cdouble_p hi = as_const(hi_);
   cdouble_p ubv = as_const(ub_);
+  cdouble_p kapv = as_const(kap_);
   double2 a_r = {0, 0}, a_s = {0, 0}, a_w = {0, 0}, a_z = {0, 0}, a_y = {0, 0};
   for (int rb = r_begin; rb < r_end; rb += nb) {
-    const double ub = ubv[rb / nb];
-    const bool soc = ub < INFINITY;
+    const double ub = ubv[rb / nb], kap = kapv[rb / nb];
+    const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their box)
     double2 cs = {1.0, 1.0};
     if (soc) {
       double2 ss = {0.0, 0.0};
@@ -1457,7 +1463,7 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
         ss.x = fma(vx, vx, ss.x);
         ss.y = fma(vy, vy, ss.y);
       }
-      cs = soc_scale2(ss, ub);
+      cs = soc_scale2(ss, ub, kap);
     }
     for (int r = 0; r < nb; ++r) {
       const int row = rb + r;
@@ -1509,7 +1515,7 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
 
 static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
     const double* __restrict__ v, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_,
+    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_, const double* __restrict__ kap_,
     int L, int zrows, int pitch, int nb, int m) {
   const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
   if (col >= pitch) return;
@@ -1518,9 +1524,10 @@ static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
   cdouble_p lo = as_const(lo_);
   cdouble_p hi = as_const(hi_);
   cdouble_p ubv = as_const(ub_);
+  cdouble_p kapv = as_const(kap_);
   for (int rb = r_begin; rb < r_end; rb += nb) {
-    const double ub = ubv[rb / nb];
-    const bool soc = ub < INFINITY;
+    const double ub = ubv[rb / nb], kap = kapv[rb / nb];
+    const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their box)
     double2 cs = {1.0, 1.0};
     if (soc) {
       double2 ss = {0.0, 0.0};
@@ -1529,7 +1536,7 @@ static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
         ss.x = fma(vv.x, vv.x, ss.x);
         ss.y = fma(vv.y, vv.y, ss.y);
       }
-      cs = soc_scale2(ss, ub);
+      cs = soc_scale2(ss, ub, kap);
     }
     for (int r = 0; r < nb; ++r) {
       const int row = rb + r;

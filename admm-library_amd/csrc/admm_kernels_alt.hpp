@@ -276,8 +276,8 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         // sqrt / division sequences inside it, and the kernels went to scratch at most shapes.)
         double cs_old = 1.0, cs_new = 1.0;
         if constexpr (SOC) {
-          const double ub = rf[LF.UB];
-          cs_old = soc_scale<NU, NB>(c0, ub);
+          const double ub = rf[LF.UB], kap = rf[LF.UB + 1];      // kap = fuel weight / rho (0: none)
+          cs_old = soc_scale<NU, NB>(c0, ub, kap);
           double vnu[NB];
 #pragma unroll
           for (int r = 0; r < NB; ++r) {
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
               vnu[r] = 0.0;
             }
           }
-          cs_new = soc_scale<NU, NB>(vnu, ub);
+          cs_new = soc_scale<NU, NB>(vnu, ub, kap);
         }
 #pragma unroll
         for (int r = 0; r < NB; ++r) {
@@ -550,8 +550,8 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         const unsigned r0 = (unsigned)SIDX(k) * NB * PB;
         double cs_old = 1.0, cs_new = 1.0;     // thrust-magnitude bound, branch-free (see xfze_kernel)
         if constexpr (SOC) {
-          const double ub = rb[LB.UB];
-          cs_old = soc_scale<NU, NB>(c0, ub);
+          const double ub = rb[LB.UB], kap = rb[LB.UB + 1];
+          cs_old = soc_scale<NU, NB>(c0, ub, kap);
           double vnu[NB];
 #pragma unroll
           for (int r = 0; r < NB; ++r) {
@@ -564,7 +564,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
               vnu[r] = 0.0;
             }
           }
-          cs_new = soc_scale<NU, NB>(vnu, ub);
+          cs_new = soc_scale<NU, NB>(vnu, ub, kap);
         }
 #pragma unroll
         for (int r3 = 0; r3 < NB; r3 += 3) {

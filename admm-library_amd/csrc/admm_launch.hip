@@ -195,7 +195,7 @@ int ensure_zy(admm_handle* h) {
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, (Lw + h->zrows - 1) / h->zrows), block(Z_THREADS);
   if (h->has_soc)
     hipLaunchKernelGGL(admm::v_to_zy_soc_kernel, grid, block, 0, h->stream, (const double*)(h->v + b), h->z + b, h->y + b,
-                       h->lo + r0, h->hi + r0, h->ub + h->wk0, Lw, h->zrows, h->pitch, h->nb, h->m);
+                       h->lo + r0, h->hi + r0, h->ub + h->wk0, h->kap + h->wk0, Lw, h->zrows, h->pitch, h->nb, h->m);
   else
     hipLaunchKernelGGL(admm::v_to_zy_kernel, grid, block, 0, h->stream, (const double*)(h->v + b), h->z + b, h->y + b,
                        h->lo + r0, h->hi + r0, Lw, h->zrows, h->pitch);
@@ -210,7 +210,7 @@ int launch_z(admm_handle* h, bool resid) {
   do {                                                                                                   \
     if (h->has_soc)                                                                                      \
       hipLaunchKernelGGL((admm::zdual_soc_kernel<RS, RX>), grid, block, 0, h->stream, h->w, h->z, h->y,  \
-                         h->lo, h->hi, h->ub, h->part, h->opt.alpha, h->L, h->zrows, h->pitch, h->nb, h->m); \
+                         h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L, h->zrows, h->pitch, h->nb, h->m); \
     else                                                                                                 \
       hipLaunchKernelGGL((admm::zdual_kernel<RS, RX>), grid, block, 0, h->stream, h->w, h->z, h->y,      \
                          h->lo, h->hi, h->part, h->opt.alpha, h->L, h->zrows, h->pitch);                 \

@@ -11,8 +11,9 @@ namespace admm {
 
 constexpr int even_up(int v) { return (v + 1) & ~1; }
 
-// Backward record:  AT [n][n] | BT [m][n] | SI [m][m] | KT [n][m] | OM [n][m] | LO [m+n] | HI [m+n] | UB [1]
-// (UB = thrust-magnitude bound of the stage, +inf when the control rows use their box)
+// Backward record:  AT [n][n] | BT [m][n] | SI [m][m] | KT [n][m] | OM [n][m] | LO [m+n] | HI [m+n] | UB [2]
+// (UB = thrust-magnitude bound of the stage, +inf when the control rows use their box; UB + 1 = kappa, the stage's
+//  fuel weight / rho, 0 without a fuel term -- in all four layouts)
 struct RecBLayout {
   int AT, BT, SI, KT, OM, LO, HI, UB, SIZE;
 };
@@ -30,7 +31,7 @@ constexpr RecBLayout rec_b_layout(int n, int m) {
   return l;
 }
 
-// Forward record:  PSI [m][n] | K [m][n] | A [n][n] | B [n][m] | LO [m+n] | HI [m+n] | UB [1]
+// Forward record:  PSI [m][n] | K [m][n] | A [n][n] | B [n][m] | LO [m+n] | HI [m+n] | UB [2]
 struct RecFLayout {
   int PSI, K, A, B, LO, HI, UB, SIZE;
 };

@@ -79,6 +79,7 @@ int pinst_upload_bounds(admm_handle* h, const admm_problem* p, bool dev) {
       for (int k = 0; k < h->N; ++k) ub[k] = p->unorm[k];
     HIP_TRY(hipMemcpyAsync(h->ub, ub.data(), sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = upload_kappa(h))) return rc;          // (zeros: no fuel term with per-instance dynamics)
   } else if ((rc = upload_bounds(h, p))) {
     return rc;
   }
@@ -259,7 +260,7 @@ int setup_pinst(admm_handle* h, const admm_problem* p, bool dev) {
   }
   PD(h->part, (size_t)std::max(h->zchunks, h->S) * 5 * P);
   PD(h->resid, 5 * P);
-  PD(h->lo, L); PD(h->hi, L); PD(h->ub, (size_t)N);
+  PD(h->lo, L); PD(h->hi, L); PD(h->ub, (size_t)N); PD(h->kap, (size_t)N);
   PD(h->Ad, (size_t)N * n * n * P); PD(h->Bd, (size_t)N * n * m * P);
   PD(h->Kd, (size_t)N * m * n * P); PD(h->Sd, (size_t)N * m * m * P);
   if (h->pbounds) { PD(h->lod, L * P); PD(h->hid, L * P); }

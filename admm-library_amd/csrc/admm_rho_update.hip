@@ -80,7 +80,7 @@ void spec_start(admm_handle* h) {
       try {
         admm::Factor f;
         std::string err;
-        rc = admm::factorise(p, s->rho, hc->S, f, err, hc->mfma_mode, !hc->scan_gemv, hc->ts_n);
+        rc = admm::factorise(p, s->rho, hc->S, f, err, hc->mfma_mode, !hc->scan_gemv, hc->ts_n, fuel_of(hc));
         s->f = std::move(f);
         s->err = std::move(err);
       } catch (...) {
@@ -160,7 +160,7 @@ int set_rho_internal(admm_handle* h, double rho_new) {
     f = std::move(sp->f);
     ++h->spec_hits;
   } else {
-    rc = admm::factorise(p, rho_new, h->S, f, err, h->mfma_mode, !h->scan_gemv, h->ts_n);
+    rc = admm::factorise(p, rho_new, h->S, f, err, h->mfma_mode, !h->scan_gemv, h->ts_n, fuel_of(h));
     ++h->spec_misses;
   }
   lap("factor (take / compute)");
@@ -256,7 +256,10 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
     return fail(ADMM_ERR_INVALID, "admm_update_problem: N, n, m, batch must equal those of admm_setup");
   if ((p->q != nullptr) != h->has_q)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: q must be given iff the handle was set up with one");
-  if (problem_has_soc(p) != h->has_soc)
+  if (h->has_fuel) {         // the weights stay in force (a fuel handle runs the SOC forms with or without a thrust bound)
+    if (p->time_varying == 2) return fail(ADMM_ERR_UNSUPPORTED, "a fuel term needs batch-shared dynamics (time_varying = 0 or 1)");
+    if ((rc = validate_fuel(p, h->fuel.data(), true))) return rc;
+  } else if (problem_has_soc(p) != h->has_soc)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: a thrust-magnitude bound cannot be added to or removed from a handle");
   if ((p->time_varying == 2) != h->pinst || (h->pinst && (p->stage_bounds == 2) != h->pbounds))
     return fail(ADMM_ERR_INVALID, "admm_update_problem: per-instance dynamics / bounds cannot be added to or removed from a handle");
@@ -288,7 +291,7 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
   }
   admm::Factor f;
   std::string err;
-  if ((rc = admm::factorise(*p, h->opt.rho, h->S, f, err, h->mfma_mode, !h->scan_gemv, h->ts_n))) return fail(rc, err);
+  if ((rc = admm::factorise(*p, h->opt.rho, h->S, f, err, h->mfma_mode, !h->scan_gemv, h->ts_n, fuel_of(h)))) return fail(rc, err);
   if (f.recB.size() != h->fac.recB.size() || f.scanWp.size() != h->fac.scanWp.size())
     return fail(ADMM_ERR_NUMERIC, "internal: record sizes changed on refactor");
   if (h->auto_segments && h->S > 1 && scan_growth(f) > SCAN_GROWTH_MAX)

@@ -49,7 +49,9 @@ struct admm_handle {
   int xfree_mode = 1;            // 2 while enqueue_one launches an iteration whose successor will not read those rows' v
   bool auto_segments = false;    // the segment count was chosen by admm_setup (and is guarded by scan_growth)
   bool has_q = false;
-  bool has_soc = false;          // some stage has a finite thrust-magnitude bound
+  bool has_soc = false;          // some stage has a finite thrust-magnitude bound, or the handle has a fuel term
+  bool has_fuel = false;         // set up by admm_setup_fuel with weights: cost term sum_k fuel[k] ||u_k||_2
+  std::vector<double> fuel;      // its N per-stage weights (the records and h->kap hold fuel[k] / rho)
   admm_options opt{};
   admm::Factor fac;
   // host copy of the shared problem data (the caller's pointers are never kept): admm_set_rho refactors from it
@@ -79,6 +81,7 @@ struct admm_handle {
   double *w = nullptr, *z = nullptr, *y = nullptr, *v = nullptr, *q = nullptr, *x0 = nullptr;
   double *dbuf = nullptr, *tseg = nullptr, *eseg = nullptr, *tin = nullptr, *xin = nullptr;
   double *part = nullptr, *resid = nullptr, *lo = nullptr, *hi = nullptr, *ub = nullptr;
+  double* kap = nullptr;         // [N] fuel weight / rho per stage beside ub (zeros without a fuel term): block-structured z kernels
   double *recB = nullptr, *recF = nullptr, *recS = nullptr;
   double *scan_in = nullptr, *scan_out = nullptr, *scanWp = nullptr;   // tseg|x0|eseg and t_in|x_in live inside these
   int* scan_range = nullptr;
@@ -293,6 +296,9 @@ int upload_factor(admm_handle* h);
 int upload_bounds(admm_handle* h, const admm_problem* p);
 void keep_shared(admm_handle* h, const admm_problem* p);
 bool problem_has_soc(const admm_problem* p);
+int validate_fuel(const admm_problem* p, const double* fuel, bool per_stage);
+int upload_kappa(admm_handle* h);
+inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fuel.data() : nullptr; }
 
 // ---- per-instance dynamics (admm_pinst_rt.hip)
 int pinst_factor(admm_handle* h, bool only_marked = false);

@@ -25,7 +25,7 @@ SEED0 = 20231004               # fixed base seed of the synthetic workloads
 class Problem:
     """One batch of QPs sharing dynamics, weights and box; differing in x0 (and q).
 
-    minimise   1/2 sum_k [u_k' R u_k + x_{k+1}' Q_{k+1} x_{k+1}] + q' w
+    minimise   1/2 sum_k [u_k' R u_k + x_{k+1}' Q_{k+1} x_{k+1}] + q' w  [+ sum_k fuel_k ||u_k||_2]
     subject to x_{k+1} = A_k x_k + B_k u_k,  x_0 given,  lo <= w <= hi
     with w = (u_0, x_1, ..., u_{N-1}, x_N), block k = (u_k, x_{k+1}).
     """
@@ -43,6 +43,9 @@ class Problem:
     # Where finite, the box of the control rows must be (-inf, inf).
     unorm: Optional[np.ndarray] = None
     name: str = ""
+    # minimum-fuel cost  + sum_k fuel_k ||u_k||_2  (fuel >= 0: scalar, or (N,) when the box is per stage); None = off.
+    # Where positive, the box of the control rows must be (-inf, inf).  Batch-shared dynamics only.
+    fuel: Optional[np.ndarray] = None
 
     @property
     def n(self) -> int:
@@ -129,6 +132,18 @@ class Problem:
             fin = np.isfinite(np.broadcast_to(un, (lo_u.shape[1],)))
             if np.any(np.isfinite(lo_u[:, fin])) or np.any(np.isfinite(hi_u[:, fin])):
                 raise ValueError("control rows must be unbounded (-inf, inf) where unorm is finite")
+        if self.fuel is not None:
+            fu = np.asarray(self.fuel, np.float64)
+            if fu.ndim > 1 or (fu.ndim == 1 and (self.lo.ndim < 2 or fu.shape != (N,))):
+                raise ValueError("fuel must be a scalar, or (N,) together with per-stage bounds")
+            if not np.all(np.isfinite(fu)) or np.any(fu < 0):
+                raise ValueError("fuel must be finite and >= 0")
+            if self.per_instance:
+                raise ValueError("fuel needs batch-shared dynamics (A, B LTI or LTV)")
+            lo_u, hi_u = np.atleast_2d(self.lo)[:, :m], np.atleast_2d(self.hi)[:, :m]
+            pos = np.broadcast_to(fu, (lo_u.shape[0],)) > 0
+            if np.any(np.isfinite(lo_u[pos])) or np.any(np.isfinite(hi_u[pos])):
+                raise ValueError("control rows must be unbounded (-inf, inf) where fuel is positive")
         for a in (self.A, self.B, self.Q, self.R, self.QN, self.x0):
             # (stacks of hundreds of MB -- per-instance dynamics -- are left to the library's own threaded check at admm_setup /
             #  admm_update_problem, which Solver reports as the same ValueError: NumPy's pass over 7 GB costs 0.4 s per call)
@@ -155,6 +170,7 @@ class DeviceProblem:
     q: Optional["torch.Tensor"] = None
     unorm: Optional["torch.Tensor"] = None      # 0-d, or (N,) with per-stage bounds
     name: str = ""
+    fuel: Optional["torch.Tensor"] = None       # Problem's field; the device entry points have no fuel term (Solver refuses it)
 
     n = Problem.n
     m = Problem.m
@@ -177,11 +193,15 @@ class DeviceProblem:
         def t(a):
             return None if a is None else torch.as_tensor(np.ascontiguousarray(a, np.float64), device=device)
         return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
-                   unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name)
+                   unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name,
+                   fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)))
 
     def validate(self) -> None:
         """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
         import torch
+        if self.fuel is not None:
+            raise ValueError("fuel: the minimum-fuel term has no device-memory form (its weights are at most N doubles): "
+                             "give a Problem with NumPy arrays")
         dev = self.x0.device if torch.is_tensor(self.x0) else None
         for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
             a = getattr(self, name)
@@ -312,6 +332,17 @@ def cw_rendezvous(N: int = 1000, batch: int = 1, seed0: int = SEED0,
     hi = np.array([u_max] * 3 + [inf] * 6)
     return Problem(N=N, A=A, B=B, Q=Q, R=R, QN=QN, x0=x0, lo=lo, hi=hi,
                    name=f"cw_rendezvous_N{N}_b{batch}")
+
+
+def cw_rendezvous_fuel(N: int = 1000, batch: int = 1, seed0: int = SEED0, u_max: float = 0.2,
+                       fuel: Optional[float] = None) -> Problem:
+    """The fuel-optimal form of cw_rendezvous(thrust_norm=True): the same QPs with the cost term  + fuel sum_k ||u_k||_2  under
+    the thrust bound ||u_k||_2 <= u_max.  fuel = None: dt = 2 pi / N, the scale of R in this generator -- the
+    quadratic and the fuel term then weigh alike, and the solutions coast (u_k = 0 exactly) over a good part of the orbit and
+    burn at the bound over another.  rho 0.05 ... 0.1 suits it."""
+    p = cw_rendezvous(N=N, batch=batch, seed0=seed0, u_max=u_max, thrust_norm=True)
+    f = 2.0 * np.pi / N if fuel is None else float(fuel)
+    return dataclasses.replace(p, fuel=np.float64(f), name=f"cw_rendezvous_fuel_N{N}_b{batch}")
 
 
 def cw_formation(N: int = 1000, batch: int = 1, seed0: int = SEED0, u_max: float = 0.2) -> Problem:

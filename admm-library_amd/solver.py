@@ -79,6 +79,10 @@ _SIGNATURES = {
     "admm_host_scan_matrices_timeshard": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p,
                                                    c_int32_p]),
     "admm_update_problem": (C.c_int, [C.c_void_p, C.POINTER(CProblem)]),
+    # minimum-fuel cost (ADMM_HIP_HAS_FUEL)
+    "admm_setup_fuel": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p]),
+    "admm_set_fuel": (C.c_int, [C.c_void_p, c_double_p]),
+    "admm_get_fuel": (C.c_int, [C.c_void_p, c_double_p]),
     # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
     "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
     "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
@@ -209,7 +213,7 @@ class Solver:
         co = self.options.to_c()
         on_device = isinstance(problem, DeviceProblem)
         if on_device:
-            problem.validate()
+            problem.validate()               # (ValueError for a DeviceProblem with a fuel term: no device-memory form)
             if timeshard is not None:
                 raise ValueError("time-sharded handles take host arrays (admm_setup_timeshard has no device-memory form)")
             if co.device < 0:
@@ -228,9 +232,15 @@ class Solver:
             _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
         elif timeshard is None:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
-            _check(self._lib, self._lib.admm_setup(C.byref(self._h), C.byref(cp), C.byref(co)))
+            if problem.fuel is not None:
+                keep["fuel"] = _abi.marshal_fuel(problem)
+                _check(self._lib, self._lib.admm_setup_fuel(C.byref(self._h), C.byref(cp), C.byref(co), dptr(keep["fuel"])))
+            else:
+                _check(self._lib, self._lib.admm_setup(C.byref(self._h), C.byref(cp), C.byref(co)))
         else:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
+            if problem.fuel is not None:
+                raise AdmmError(2, "a fuel term is not supported on time-sharded handles")
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -311,6 +321,8 @@ class Solver:
             t0 = time.perf_counter()
             _check(self._lib, self._lib.admm_update_problem_device(self._h, C.byref(cp), _stream(dev)))
         else:
+            if problem.fuel is not None or getattr(self.problem, "fuel", None) is not None:
+                problem = self._keep_fuel(problem)
             cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
             t0 = time.perf_counter()
             _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
@@ -318,6 +330,35 @@ class Solver:
         del keep
         self.problem = problem
         self._warn()
+
+    def _keep_fuel(self, problem):
+        """update_problem on a handle with a fuel term: the handle's weights stay in force (admm_update_problem); the problem that
+        becomes self.problem carries them, and the new box is validated against them."""
+        import dataclasses
+        if getattr(self.problem, "fuel", None) is None:
+            raise ValueError("a fuel term cannot be added to a handle: set up a new Solver")
+        cur = self.fuel()
+        if problem.fuel is not None and not np.array_equal(np.broadcast_to(np.asarray(problem.fuel, np.float64), cur.shape), cur):
+            raise ValueError("update_problem keeps the handle's fuel weights: change them with set_fuel")
+        if problem.lo.ndim < 2 and np.any(cur != cur[0]):
+            raise ValueError("per-stage fuel weights need per-stage bounds")
+        return dataclasses.replace(problem, fuel=cur if problem.lo.ndim >= 2 else np.float64(cur[0]))
+
+    def set_fuel(self, fuel):
+        """New weights of the minimum-fuel term (scalar, or (N,) with per-stage bounds) on a handle set up with Problem.fuel:
+        continuation in the weight, the state kept as a warm start (admm_set_fuel)."""
+        import dataclasses
+        cand = dataclasses.replace(self.problem, fuel=np.asarray(fuel, np.float64))
+        cand.validate()
+        _check(self._lib, self._lib.admm_set_fuel(self._h, dptr(_abi.marshal_fuel(cand))))
+        self.problem = cand
+        self._warn()
+
+    def fuel(self) -> np.ndarray:
+        """(N,) weights of the minimum-fuel term in force, per stage (zeros on a handle without the term)."""
+        out = np.zeros(self.problem.N)
+        _check(self._lib, self._lib.admm_get_fuel(self._h, dptr(out)))
+        return out
 
     def set_rho(self, rho: float):
         _check(self._lib, self._lib.admm_set_rho(self._h, float(rho)))

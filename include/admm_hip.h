@@ -200,6 +200,30 @@ int admm_set_rho(admm_handle* h, double rho);
  * unchanged. */
 int admm_update_problem(admm_handle* h, const admm_problem* p);
 
+/* Minimum-fuel cost (new symbols of ABI v9, announced by ADMM_HIP_HAS_FUEL -- no struct or signature changed):
+ *
+ *     ... + sum_k fuel_k ||u_k||_2,   fuel_k >= 0
+ *
+ * the propellant of a single gimballed thruster, usually together with the thrust bound ||u_k||_2 <= unorm_k.  Its solutions
+ * coast and burn: where the term wins, the control rows of z are exactly zero.  Only the z-update changes: the control rows of a
+ * stage are shrunk by fuel_k / rho, then scaled onto the ball (with fuel_k = 0 the thrust-bound projection, bit for bit).
+ *
+ * admm_setup_fuel: admm_setup with the weights `fuel`, in unorm's shape -- 1 entry with stage_bounds = 0, N entries with
+ *   stage_bounds = 1; finite and >= 0, and where an entry is positive the box of that stage's control rows must be (-inf, +inf)
+ *   (ADMM_ERR_INVALID otherwise, checked before a device is looked for).  fuel = NULL is exactly admm_setup.  Needs batch-shared
+ *   dynamics (time_varying 0 or 1) and ADMM_PRECISION_FP64; per-instance dynamics, the MFMA precision modes and time-sharded
+ *   handles are refused with ADMM_ERR_UNSUPPORTED.  The handle runs the one-lane fp64 kernels (thrust-magnitude forms) whether
+ *   or not unorm is given; all of the solver -- adaptive rho, over-relaxation, q, warm starts, admm_update_instances,
+ *   admm_update_problem (which keeps the weights and checks the new box against them), admm_set_rho -- works on it.
+ * admm_set_fuel: replace the weights (same shape) of such a handle between iterations -- continuation in the weight with a warm
+ *   start.  The state is kept as the (z, y) pair; on failure nothing has changed.  ADMM_ERR_INVALID on a handle that was not set
+ *   up with weights: a fuel term cannot be added to a handle.
+ * admm_get_fuel: the N per-stage weights in force (zeros on a handle without the term). */
+#define ADMM_HIP_HAS_FUEL 1
+int admm_setup_fuel(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel);
+int admm_set_fuel(admm_handle* h, const double* fuel);
+int admm_get_fuel(admm_handle* h, double* fuel);
+
 /* Warm start / test hook: overwrite device state.  Any pointer may be NULL
  * (left unchanged).  Each is L*batch and must be finite (ADMM_ERR_INVALID otherwise, nothing uploaded). */
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y);

@@ -161,7 +161,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     o.adapt_tau = scalar_or(O, "adapt_tau", o.adapt_tau);
     o.precision_mode = static_cast<int32_t>(scalar_or(O, "precision_mode", o.precision_mode));   // ADMM_PRECISION_*
     admm_handle* h = nullptr;
-    check(admm_setup(&h, &p, &o));
+    // optional problem field `fuel` (minimum-fuel cost + sum_k fuel_k ||u_k||_2): 1 or N entries, as unorm
+    const mxArray* fu = field(prhs[1], "fuel", false);
+    const double* fuel = dbl(fu, "fuel");
+    if (fuel && static_cast<int32_t>(mxGetNumberOfElements(fu)) != (p.stage_bounds ? p.N : 1))
+      fail("admm:input", "fuel must have 1 entry, or N entries together with per-stage bounds");
+    check(admm_setup_fuel(&h, &p, &o, fuel));      // (fuel = NULL: admm_setup)
     remember(h, L, p.batch);
     plhs[0] = mxCreateNumericMatrix(1, 1, mxUINT64_CLASS, mxREAL);
     *static_cast<uint64_t*>(mxGetData(plhs[0])) = static_cast<uint64_t>(reinterpret_cast<uintptr_t>(h));
