@@ -415,6 +415,12 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     TRY_RELEASE(dalloc(&h->scan_rangeB, h->fac.scanRangeB.size()));
     DALLOC_WIN(h->mvec, Nmw * P, win_bias_m(h));               // db rows of the forward elimination
     HIP_TRY_RELEASE(hipMemsetAsync(h->mvec + win_bias_m(h), 0, sizeof(double) * Nmw * P, h->stream));
+    if (admm::alt_lean_dims(h->n, h->m) && !h->ts_n) {         // side data of the lean residual forms (admm_kernels_alt.hpp)
+      DALLOC_WIN(h->wu, Nmw * P, win_bias_m(h));
+      HIP_TRY_RELEASE(hipMemsetAsync(h->wu + win_bias_m(h), 0, sizeof(double) * Nmw * P, h->stream));
+      TRY_RELEASE(dalloc(&h->xbnd, (size_t)h->S * h->n * P));
+      HIP_TRY_RELEASE(hipMemsetAsync(h->xbnd, 0, sizeof(double) * (size_t)h->S * h->n * P, h->stream));
+    }
     HIP_TRY_RELEASE(hipMemcpy(h->recFE, h->fac.recFE.data(), sizeof(double) * h->fac.recFE.size(), hipMemcpyHostToDevice));
     HIP_TRY_RELEASE(hipMemcpy(h->recBE, h->fac.recBE.data(), sizeof(double) * h->fac.recBE.size(), hipMemcpyHostToDevice));
     if (!h->scan_gemv) HIP_TRY_RELEASE(hipMemcpy(h->scanWpB, h->fac.scanWpB.data(), sizeof(double) * h->fac.scanWpB.size(), hipMemcpyHostToDevice));
@@ -497,6 +503,7 @@ int admm_set_fuel(admm_handle* h, const double* fuel) {
   if ((rc = ensure_zy(h))) return rc;
   h->zy_valid = true;
   h->v_valid = false;
+  drop_side_data(h);
   HIP_TRY(hipStreamSynchronize(h->stream));   // kernels of the old weights are done before the records change
   h->spec.clear();                            // candidate factors of the adaptive rule carry the old weights (joins their threads)
   h->spec_stale.clear();
@@ -555,6 +562,7 @@ int admm_update_instances(admm_handle* h, const double* x0, const double* q) {
   HIP_TRY(hipSetDevice(h->device));
   int rc;
   if ((x0 || q) && (rc = ensure_w(h))) return rc;   // w of the last x-update belongs to the old instance data
+  if (x0 || q) drop_side_data(h);
   if (x0 || q) h->alt_state = admm_handle::ALT_NONE;
   if (x0) {
     if (!finite_all(x0, (size_t)h->n * h->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
@@ -591,6 +599,7 @@ int admm_update_instances_device(admm_handle* h, const double* x0, const double*
   if (q && !h->has_q) return fail(ADMM_ERR_INVALID, "handle was set up without q; cannot add one later");
   if (q && found[1] != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
   if ((rc = ensure_w(h))) return rc;                 // w of the last x-update belongs to the old instance data
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
   if (x0 && (rc = upload_transposed(h, x0, h->x0, h->n, 0, 0, true))) return rc;
   if (q && (rc = upload_transposed(h, q, h->q, h->L, 0, 0, true))) return rc;
@@ -615,6 +624,7 @@ int admm_set_state(admm_handle* h, const double* w, const double* z, const doubl
     if (y && (rc = upload_transposed(h, y, h->y, h->L))) return rc;
     h->zy_valid = true;
     h->v_valid = false;                         // an arbitrary (z, y) pair need not be of the form (clip(v), v - clip(v))
+    drop_side_data(h);
     h->alt_state = admm_handle::ALT_NONE;
   }
   return ADMM_OK;
@@ -651,6 +661,7 @@ int admm_set_state_device(admm_handle* h, const double* w, const double* z, cons
     if (y && (rc = upload_transposed(h, y, h->y, h->L, 0, 0, true))) return rc;
     h->zy_valid = true;
     h->v_valid = false;
+    drop_side_data(h);
     h->alt_state = admm_handle::ALT_NONE;
   }
   return ADMM_OK;
@@ -677,6 +688,7 @@ int admm_step_z(admm_handle* h, int32_t residuals) {
   if (!rc) rc = launch_z(h, residuals != 0);
   if (rc) return rc;
   h->v_valid = false;
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
   if (residuals) {
     launch_finalize(h, 0, h->zchunks);
@@ -699,8 +711,9 @@ int admm_run(admm_handle* h, int32_t iters, int32_t residual_every) {
   }
   for (int it = 1; it <= iters; ++it) {
     const bool resid = residual_every > 0 && (it % residual_every == 0);
-    const bool next_plain = it < iters && !(residual_every > 0 && ((it + 1) % residual_every == 0));
-    int rc = enqueue_one(h, resid, use_graph, iters - it + 1, 0, next_plain);
+    const bool next_resid = it < iters && residual_every > 0 && ((it + 1) % residual_every == 0);
+    const bool next_plain = it < iters && !next_resid;
+    int rc = enqueue_one(h, resid, use_graph, iters - it + 1, 0, next_plain, next_resid);
     if (rc) return rc;
   }
   int rcf = flush_finalize(h);
@@ -710,6 +723,12 @@ int admm_run(admm_handle* h, int32_t iters, int32_t residual_every) {
 }
 
 int admm_iterate(admm_handle* h, int32_t iters) { return admm_run(h, iters, 0); }
+
+int admm_get_lean_iterations(admm_handle* h, int64_t* count) {
+  if (!h || !count) return fail(ADMM_ERR_INVALID, "NULL argument");
+  *count = (int64_t)h->lean_count;
+  return ADMM_OK;
+}
 
 int admm_sync(admm_handle* h) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");

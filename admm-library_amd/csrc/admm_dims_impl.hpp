@@ -65,21 +65,29 @@ void launch_dim(const XLaunch& l, XKernel k, bool a, bool b) {
         const bool relax = l.alpha != 1.0;
         // the scan's input / output slots are shared by both directions: (tseg, eseg) = (mseg, epsseg),
         // (tin, xin) = (m_in, x_end)
-#define ALT4(RS, RX, HQ, SC, XF)                                                                                \
+#define ALT5(RS, RX, HQ, SC, XF, LN)                                                                            \
   do {                                                                                                       \
     if (k == XKernel::XFZE)                                                                                  \
-      hipLaunchKernelGGL((xfze_kernel<NX, NU, RS, RX, HQ, SC, XF>), grid, block, 0, l.stream, l.dbuf, l.tin, l.xin,  \
+      hipLaunchKernelGGL((xfze_kernel<NX, NU, RS, RX, HQ, SC, XF, LN>), grid, block, 0, l.stream, l.dbuf, l.tin, l.xin,  \
                          l.recFE, l.seg_start, l.q, l.v, l.mvec, l.tseg, l.eseg, l.part, l.alpha, l.rho,     \
-                         l.pitch, l.nsplit, l.split_stride);                                                 \
+                         l.pitch, l.nsplit, l.split_stride, l.wu, l.xbnd);                                   \
     else                                                                                                     \
-      hipLaunchKernelGGL((xbze_kernel<NX, NU, RS, RX, HQ, SC, XF>), grid, block, 0, l.stream, l.mvec, l.tin, l.xin,  \
+      hipLaunchKernelGGL((xbze_kernel<NX, NU, RS, RX, HQ, SC, XF, LN>), grid, block, 0, l.stream, l.mvec, l.tin, l.xin,  \
                          l.recBE, l.seg_start, l.q, l.v, l.dbuf, l.tseg, l.eseg, l.part, l.alpha, l.rho,     \
-                         l.pitch, l.nsplit, l.split_stride);                                                 \
+                         l.pitch, l.nsplit, l.split_stride, l.wu, l.xbnd);                                   \
   } while (0)
+#define ALT4(RS, RX, HQ, SC, XF) ALT5(RS, RX, HQ, SC, XF, 0)
 // XFREE forms (state rows unbounded everywhere: their v is not read -- 1 -- and, when the next iteration is of the same kind,
 // not written either -- 2) exist for the non-residual, non-relaxed kernels only
+// lean residual forms (l.lean = ALT_LEAN_SD | NR | NW, set by enqueue_one for the shapes of alt_lean_dims only)
 #define ALT3(RS, RX, HQ, SC)                                                                                  \
   do {                                                                                                       \
+    if constexpr ((RS) && !(RX) && !(HQ) && !(SC) && alt_lean_dims(NX, NU)) {                                \
+      if (l.lean == 7) { ALT5(RS, RX, HQ, SC, 1, 7); break; }                                                \
+      if (l.lean == 6) { ALT5(RS, RX, HQ, SC, 1, 6); break; }                                                \
+      if (l.lean == 5) { ALT5(RS, RX, HQ, SC, 1, 5); break; }                                                \
+      if (l.lean == 4) { ALT5(RS, RX, HQ, SC, 1, 4); break; }                                                \
+    }                                                                                                        \
     if constexpr (!(RS) && !(RX)) {                                                                          \
       if (l.xfree == 2) ALT4(RS, RX, HQ, SC, 2); else if (l.xfree == 1) ALT4(RS, RX, HQ, SC, 1); else ALT4(RS, RX, HQ, SC, 0); \
     } else if constexpr ((RS) && !(RX) && NX + NU >= 12) {   /* residual form with the state rows' shortcut: fp64-issue-bound blocks only */ \
@@ -93,6 +101,7 @@ void launch_dim(const XLaunch& l, XKernel k, bool a, bool b) {
 #undef ALT2
 #undef ALT3
 #undef ALT4
+#undef ALT5
 #undef ALT1
       }
       break;

@@ -13,6 +13,8 @@ struct XLaunch {
   int batch;                    // QPs really present (columns batch .. pitch-1 are padding)
   int xfree;                    // every state row is unbounded at every stage: z = v, y = 0 there (XFREE kernel forms):
                                 // 1 = their v is not read, 2 = nor written (the next iteration does not read it either)
+  int lean;                     // lean residual form of XFZE / XBZE (ALT_LEAN_* bits, admm_kernels_alt.hpp), 0 = the full forms
+  double *wu, *xbnd;            // ... its side data: w_u of the last iterate (m rows per stage), end-of-segment states (n rows per segment)
   bool has_q;
   bool has_soc;                 // thrust-magnitude bound on some stage: SOC kernel forms
   double rho, alpha;
@@ -30,6 +32,10 @@ struct XLaunch {
   const unsigned char *recMF, *recMB;
   int mfma_mode;
 };
+
+// lean residual forms of XFZE / XBZE (admm_kernels_alt.hpp): the bits of XLaunch::lean and the shapes they are compiled for
+constexpr int ALT_LEAN_NR = 1, ALT_LEAN_NW = 2, ALT_LEAN_SD = 4;
+constexpr bool alt_lean_dims(int nx, int nu) { return (nx == 6 && nu == 3) || (nx == 12 && nu == 6); }
 
 enum class XKernel { XB, XF, XFZ, XSCAN_CHAIN, XFZE, XBZE };
 

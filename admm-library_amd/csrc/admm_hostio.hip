@@ -349,6 +349,7 @@ void set_mixed_form(admm_handle* h, bool fp32) {
   if (h->opt.precision_mode != ADMM_PRECISION_MIXED) return;
   h->mfma_on = fp32;
   h->mfma_refine = !fp32;
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
 }
 
@@ -389,11 +390,11 @@ void release(admm_handle* h) {
   // the big per-stage arrays are held as pointers biased by the stage window (admm_runtime.hpp): undo that before freeing
   for (double** b : {&h->w, &h->z, &h->y, &h->v, &h->q})
     if (*b) *b += win_bias(h);
-  for (double** b : {&h->dbuf, &h->mvec})
+  for (double** b : {&h->dbuf, &h->mvec, &h->wu})
     if (*b) *b += win_bias_m(h);
   double** bufs[] = {&h->w, &h->z, &h->y, &h->v, &h->q, &h->dbuf, &h->scan_in, &h->scan_out, &h->scanWp,
                      &h->part, &h->resid, &h->lo, &h->hi, &h->ub, &h->kap, &h->recB, &h->recF, &h->recS, &h->stage,
-                     &h->recFE, &h->recBE, &h->mvec, &h->scanWpB};
+                     &h->recFE, &h->recBE, &h->mvec, &h->scanWpB, &h->wu, &h->xbnd};
   for (auto b : bufs)
     if (*b) { (void)hipFree(*b); *b = nullptr; }
   {
@@ -462,6 +463,7 @@ int upload_factor(admm_handle* h) {
   if (!h->scan_gemv) HIP_TRY(hipMemcpy(h->scan_range, h->fac.scanRange.data(), sizeof(int32_t) * h->fac.scanRange.size(), hipMemcpyHostToDevice));
   int rc;
   if (h->scan_gemv && (rc = upload_scan_dense(h->fac.scanW, h->fac.scanM, h->fac.scanK, h->scanWd, h->scan_rows))) return rc;
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
   if (!h->fac.alt_ok) {                                             // the forward-elimination form did not survive the refactor
     if (h->alt_allowed) warn_alt_gate(h->fac, h->fac.rho, "refactor");

@@ -15,6 +15,8 @@
 //     xfze: d read 2.67 + v read 8 + v+ written 8 + db written 2.67 = 21.33   (+8 with a linear term q)
 //     xbze: db read 2.67 + v read 8 + v+ written 8 + d written 2.67 = 21.33   (+8 with q)
 // against 29.33 for xb + xfz (each elimination leaves only its m-row feed-forward term per stage).
+//     lean residual form (LEAN = NR | NW | SD, consecutive residual iterations, unbounded state rows):
+//           d / db read 2.67 + v_u read 2.67 + w_u,old read 2.67 + v_u+ written 2.67 + w_u written 2.67 + db / d written 2.67 = 16
 // Same layout, staging and addressing as admm_kernels.hpp.
 #pragma once
 
@@ -99,6 +101,17 @@ constexpr int alt_min_waves(int nb, bool hasq, bool soc) {
 // the alternating kernels are compiled for every (n, m) pair of admm_dims_g*.hip
 constexpr bool alt_dims(int nx, int nu) { return nx >= 1 && nu >= 1; }
 
+// LEAN residual forms (DESIGN.md §4.8 "lean residual iterations"; last template parameter of the two kernels).  On a handle
+// whose state rows are unbounded everywhere (XFREE) the only thing a residual iteration needs v_old of those rows for is the
+// dual residual, sum_k |x+_{k+1} - x_old,{k+1}|^2.  The difference obeys the rollout's own recursion,
+//     forward:   dx_{k+1} = A_k dx_k + B_k (u+_k - u_old,k)          backward:   dx_k = AI_k dx_{k+1} + AIB_k (u+_k - u_old,k)
+// so it is rolled out beside x from the m control rows of the last iterate (the side buffer w_u, updated in place) and from
+// the state the last iterate's kernel ended its segment with (xbnd, n rows per segment) -- the stored state rows themselves
+// are neither read (NR) nor, when the next iteration is NR too, written (NW).  Every lean form writes the side data (SD).
+// Only the sum s differs from the full forms (rounding of the recursion); every other output is bit-identical.
+// Compiled for the headline shapes without q and without the thrust bound; anything else runs the full forms.
+// (ALT_LEAN_NR / _NW / _SD and alt_lean_dims(): admm_dispatch.hpp, shared with the runtime.)
+
 // Sum of the (<= 8) split-K slabs of one scan output row (see xf_kernel).
 __device__ __forceinline__ double scan_row(const double* base, size_t o, int nsplit, size_t split_stride) {
   double p[8];
@@ -121,13 +134,14 @@ __device__ __forceinline__ double scan_row(const double* base, size_t o, int nsp
 //     mu  = FM_k mu + GA_k g^u + PI_k g^x
 // and on exit mu -> mseg[s], eb -> ebseg[s].
 // ---------------------------------------------------------------------------
-template <int NX, int NU, bool RESID, bool RELAX, bool HASQ, bool SOC, int XFREE = 0>
+template <int NX, int NU, bool RESID, bool RELAX, bool HASQ, bool SOC, int XFREE = 0, int LEAN = 0>
 __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) void xfze_kernel(
     const double* __restrict__ dbuf, const double* __restrict__ tin, const double* __restrict__ xin,
     const double* __restrict__ recFE, const int* __restrict__ seg_start_, const double* __restrict__ q,
     double* __restrict__ v,
     double* __restrict__ dbb, double* __restrict__ mseg, double* __restrict__ epsseg,
-    double* __restrict__ part, double alpha, double rho, int pitch, int nsplit, size_t split_stride) {
+    double* __restrict__ part, double alpha, double rho, int pitch, int nsplit, size_t split_stride,
+    double* wu, double* xbnd) {
   constexpr int NB = NX + NU;
   constexpr RecFELayout LF = rec_fe_layout(NX, NU);
   constexpr int RF = LF.SIZE;
@@ -169,11 +183,16 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   // bound by fp64 issue rather than HBM (n + m >= 12).
   static_assert(!XFREE || !RELAX, "XFREE needs no over-relaxation");
   static_assert(!(XFREE == 2 && RESID), "the residuals need v of every row");
+  // LEAN residual forms (see alt_lean_dims above): NR = v of the state rows is not read, NW = nor written, SD = side data written
+  constexpr bool L_NR = (LEAN & ALT_LEAN_NR) != 0, L_NW = (LEAN & ALT_LEAN_NW) != 0, L_SD = (LEAN & ALT_LEAN_SD) != 0;
+  static_assert(!LEAN || (L_SD && RESID && XFREE == 1 && !RELAX && !HASQ && !SOC && alt_lean_dims(NX, NU)), "lean residual forms");
   const RowView vv(v, (size_t)k0 * NB * P, (size_t)(k1 - k0) * NB * P * 8);
   const RowView vd(dbuf, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);
   const RowView vm(dbb, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);
   const RowView vq(HASQ ? q : v, (size_t)k0 * NB * P, (size_t)(k1 - k0) * NB * P * 8);
+  const RowView vw(LEAN ? wu : v, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);      // w_u of the last iterate (m rows per stage)
   double t[NX], x[NX], mu[NX], eps[NX];
+  [[maybe_unused]] double dx[NX], a_sx = 0.0;
   {
     const size_t o = (size_t)s * NX * P + col;
 #pragma unroll
@@ -182,19 +201,24 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
       x[i] = scan_row(xin, o + i * P, nsplit, split_stride);
       mu[i] = 0.0;
       eps[i] = 0.0;
+      // dx = x+ - x_old at the segment's first stage: the previous (backward) iterate left its rolled-out x there
+      if (L_NR) dx[i] = x[i] - xbnd[o + i * P];
     }
   }
-  double ld[PF][NU], l0[PF][NB], lq[PF][NB];
+  double ld[PF][NU], l0[PF][NB], lq[PF][NB], lw[PF][NU];
 #pragma unroll
   for (int j = 0; j < PF; ++j) {
     const int kj = (k0 + j < k1) ? k0 + j : k1 - 1;
     const unsigned d0 = (unsigned)(kj - k0) * NU * PB;
 #pragma unroll
-    for (int jj = 0; jj < NU; ++jj) ld[j][jj] = vd.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+    for (int jj = 0; jj < NU; ++jj) {
+      ld[j][jj] = vd.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+      if (L_NR) lw[j][jj] = vw.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+    }
     const unsigned r0 = (unsigned)(kj - k0) * NB * PB;
 #pragma unroll
     for (int r = 0; r < NB; ++r) {
-      l0[j][r] = (XFREE && !RESID && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
+      l0[j][r] = (XFREE && (!RESID || L_NR) && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
       if (HASQ) lq[j][r] = vq.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
     }
   }
@@ -215,8 +239,12 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         const double* rf16 = rec16 + (k - kc) * RF;
         const double* rn16 = rec16 + ((k < khi ? k + 1 : khi) - kc) * RF;      // the next stage's record (clamped: re-read, unused)
         double d[NU], c0[NB], cq[NB];
+        [[maybe_unused]] double wo[NU];
 #pragma unroll
-        for (int jj = 0; jj < NU; ++jj) d[jj] = ld[j][jj];
+        for (int jj = 0; jj < NU; ++jj) {
+          d[jj] = ld[j][jj];
+          if (L_NR) wo[jj] = lw[j][jj];
+        }
 #pragma unroll
         for (int r = 0; r < NB; ++r) {
           c0[r] = l0[j][r];
@@ -226,11 +254,14 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           const int kn = (k + PF < k1) ? k + PF : k1 - 1;
           const unsigned d0 = (unsigned)(kn - k0) * NU * PB;
 #pragma unroll
-          for (int jj = 0; jj < NU; ++jj) ld[j][jj] = vd.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+          for (int jj = 0; jj < NU; ++jj) {
+            ld[j][jj] = vd.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+            if (L_NR) lw[j][jj] = vw.load<ADMM_ALT_LOAD_AUX>(lb, d0 + jj * PB);
+          }
           const unsigned r0 = (unsigned)(kn - k0) * NB * PB;
 #pragma unroll
           for (int r = 0; r < NB; ++r) {
-            l0[j][r] = (XFREE && !RESID && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
+            l0[j][r] = (XFREE && (!RESID || L_NR) && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
             if (HASQ) lq[j][r] = vq.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
           }
         }
@@ -255,6 +286,19 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           ADMM_MV(NX, NU, false, B, uu, xn);
 #pragma unroll
           for (int i = 0; i < NX; ++i) { wv[NU + i] = xn[i]; x[i] = xn[i]; }
+          if constexpr (L_NR) {
+            // the same rollout of the DIFFERENCE to the last iterate, while A_k, B_k sit in the operand registers:
+            // dx_{k+1} = A_k dx_k + B_k (u+ - u_old); block k stores x_{k+1}, so its dual-residual term is |dx_{k+1}|^2
+            double du[NU], dxn[NX];
+#pragma unroll
+            for (int jj = 0; jj < NU; ++jj) du[jj] = uu[jj] - wo[jj];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) dxn[i] = 0.0;
+            ADMM_MV(NX, NX, false, A, dx, dxn);
+            ADMM_MV(NX, NU, false, B, du, dxn);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { dx[i] = dxn[i]; a_sx = fma(dxn[i], dxn[i], a_sx); }
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- z-update, dual ascent, residual partials; g = linear term of the next x-update ----
@@ -298,12 +342,14 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
             // an unbounded state row: z = v, y = 0 identically, so v+ = w^ = w (no relaxation here), z+ = v+, y+ = 0 and
             // g = -rho z+ -- the clip / dual arithmetic of the general row (2 max, 2 min, 4 adds) would reproduce exactly
             // these values (up to the sign of a zero); the kernels without residuals are bound by fp64 issue, not by HBM
-            if (XFREE != 2) vv.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, r0 + r * PB);
+            if (XFREE != 2 && !L_NW) vv.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, r0 + r * PB);
             g[r] = -rho * wv[r];
             if (HASQ) g[r] += cq[r];
-            if (RESID) {          // w - z+ = 0 and y+ = 0 on this row; z+ = w, z_old = v_old
-              const double ds = wv[r] - c0[r];
-              a_s = fma(ds, ds, a_s);
+            if (RESID) {          // w - z+ = 0 and y+ = 0 on this row; z+ = w, z_old = v_old (L_NR: summed from dx above)
+              if (!L_NR) {
+                const double ds = wv[r] - c0[r];
+                a_s = fma(ds, ds, a_s);
+              }
               a_w = fma(wv[r], wv[r], a_w);
               a_z = fma(wv[r], wv[r], a_z);
             }
@@ -318,6 +364,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           const double vn = wh + yo;
           if (!(XFREE == 2 && r >= NU))      // XFREE = 2: the next iteration does not read these rows either
             vv.store<ADMM_ALT_STORE_AUX>(vn, lb_st, r0 + r * PB);
+          if (L_SD && r < NU) vw.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, (unsigned)(k - k0) * NU * PB + r * PB);
           const double zn = fmin(fmax(ball ? vn * cs_new : vn, lo_r), hi_r);
           const double yn = vn - zn;
           g[r] = -rho * (zn - yn);
@@ -377,11 +424,12 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
     for (int i = 0; i < NX; ++i) {
       mseg[o + i * P] = mu[i];
       epsseg[o + i * P] = eps[i];
+      if (L_SD) xbnd[o + i * P] = x[i];      // the rolled-out state at the segment's end: where the next (backward) form starts its dx
     }
     if (RESID) {
       const size_t op = (size_t)s * 5 * P + col;
       part[op + 0 * P] = a_r;
-      part[op + 1 * P] = a_s;
+      part[op + 1 * P] = L_NR ? a_s + a_sx : a_s;
       part[op + 2 * P] = a_w;
       part[op + 3 * P] = a_z;
       part[op + 4 * P] = a_y;
@@ -403,13 +451,14 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
 //     p = g^x + t;  h = BT_k p + g^u;  d0_k = SI_k h -> dbuf;  t = AT_k p - KT_k h;  e += OM_k d0_k
 // and on exit t -> tseg[s], e -> eseg[s]: exactly what xb_kernel leaves for the plain scan.
 // ---------------------------------------------------------------------------
-template <int NX, int NU, bool RESID, bool RELAX, bool HASQ, bool SOC, int XFREE = 0>
+template <int NX, int NU, bool RESID, bool RELAX, bool HASQ, bool SOC, int XFREE = 0, int LEAN = 0>
 __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) void xbze_kernel(
     const double* __restrict__ dbb, const double* __restrict__ min_, const double* __restrict__ xend,
     const double* __restrict__ recBE, const int* __restrict__ seg_start_, const double* __restrict__ q,
     double* __restrict__ v,
     double* __restrict__ dbuf, double* __restrict__ tseg, double* __restrict__ eseg,
-    double* __restrict__ part, double alpha, double rho, int pitch, int nsplit, size_t split_stride) {
+    double* __restrict__ part, double alpha, double rho, int pitch, int nsplit, size_t split_stride,
+    double* wu, double* xbnd) {
   constexpr int NB = NX + NU;
   constexpr RecBELayout LB = rec_be_layout(NX, NU);
   constexpr int RB = LB.SIZE;
@@ -451,16 +500,21 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   // bound by fp64 issue rather than HBM (n + m >= 12).
   static_assert(!XFREE || !RELAX, "XFREE needs no over-relaxation");
   static_assert(!(XFREE == 2 && RESID), "the residuals need v of every row");
+  // LEAN residual forms (see alt_lean_dims above): NR = v of the state rows is not read, NW = nor written, SD = side data written
+  constexpr bool L_NR = (LEAN & ALT_LEAN_NR) != 0, L_NW = (LEAN & ALT_LEAN_NW) != 0, L_SD = (LEAN & ALT_LEAN_SD) != 0;
+  static_assert(!LEAN || (L_SD && RESID && XFREE == 1 && !RELAX && !HASQ && !SOC && alt_lean_dims(NX, NU)), "lean residual forms");
   const RowView vv(v, (size_t)k0 * NB * P, (size_t)(k1 - k0) * NB * P * 8);
   const RowView vd(dbuf, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);
   const RowView vm(dbb, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);
   const RowView vq(HASQ ? q : v, (size_t)k0 * NB * P, (size_t)(k1 - k0) * NB * P * 8);
+  const RowView vw(LEAN ? wu : v, (size_t)k0 * NU * P, (size_t)(k1 - k0) * NU * P * 8);      // w_u of the last iterate (m rows per stage)
 #ifdef ADMM_ABLATE_REVERSE   // timing-only diagnostic: the backward sweep walks ASCENDING addresses (wrong results)
 #define SIDX(kk) (k1 - 1 - (kk))
 #else
 #define SIDX(kk) ((kk) - k0)
 #endif
   double t[NX], e[NX], x[NX], mi[NX];
+  [[maybe_unused]] double dx[NX], a_sx = 0.0;
   {
     const size_t o = (size_t)s * NX * P + col;
 #pragma unroll
@@ -469,19 +523,24 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
       x[i] = scan_row(xend, o + i * P, nsplit, split_stride);
       t[i] = 0.0;
       e[i] = 0.0;
+      // dx = x+ - x_old at the segment's end: the previous (forward) iterate left its rolled-out x there (= what it stored)
+      if (L_NR) dx[i] = x[i] - xbnd[o + i * P];
     }
   }
-  double lm[PF][NU], l0[PF][NB], lq[PF][NB];
+  double lm[PF][NU], l0[PF][NB], lq[PF][NB], lw[PF][NU];
 #pragma unroll
   for (int j = 0; j < PF; ++j) {
     const int kj = (k1 - 1 - j > k0) ? k1 - 1 - j : k0;
     const unsigned m0 = (unsigned)SIDX(kj) * NU * PB;
 #pragma unroll
-    for (int i = 0; i < NU; ++i) lm[j][i] = vm.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+    for (int i = 0; i < NU; ++i) {
+      lm[j][i] = vm.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+      if (L_NR) lw[j][i] = vw.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+    }
     const unsigned r0 = (unsigned)SIDX(kj) * NB * PB;
 #pragma unroll
     for (int r = 0; r < NB; ++r) {
-      l0[j][r] = (XFREE && !RESID && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
+      l0[j][r] = (XFREE && (!RESID || L_NR) && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
       if (HASQ) lq[j][r] = vq.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
     }
   }
@@ -502,23 +561,30 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         const double* rb16 = rec16 + (k - klo) * RB;
         const double* rn16 = rec16 + ((k > klo ? k - 1 : klo) - klo) * RB;     // the next stage's record (clamped)
         double c0[NB], d[NU], cq[NB];
+        [[maybe_unused]] double wo[NU];
 #pragma unroll
         for (int r = 0; r < NB; ++r) {
           c0[r] = l0[j][r];
           if (HASQ) cq[r] = lq[j][r];
         }
 #pragma unroll
-        for (int jj = 0; jj < NU; ++jj) d[jj] = lm[j][jj];
+        for (int jj = 0; jj < NU; ++jj) {
+          d[jj] = lm[j][jj];
+          if (L_NR) wo[jj] = lw[j][jj];
+        }
         {  // refill this slot with stage k - PF (clamped: the re-read rows near the segment start
            // are overwritten by this lane only later, in program order, and the values are unused)
           const int kn = (k - PF > k0) ? k - PF : k0;
           const unsigned m0 = (unsigned)SIDX(kn) * NU * PB;
 #pragma unroll
-          for (int i = 0; i < NU; ++i) lm[j][i] = vm.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+          for (int i = 0; i < NU; ++i) {
+            lm[j][i] = vm.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+            if (L_NR) lw[j][i] = vw.load<ADMM_ALT_LOAD_AUX>(lb, m0 + i * PB);
+          }
           const unsigned r0 = (unsigned)SIDX(kn) * NB * PB;
 #pragma unroll
           for (int r = 0; r < NB; ++r) {
-            l0[j][r] = (XFREE && !RESID && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
+            l0[j][r] = (XFREE && (!RESID || L_NR) && r >= NU) ? 0.0 : vv.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
             if (HASQ) lq[j][r] = vq.load<ADMM_ALT_LOAD_AUX>(lb, r0 + r * PB);
           }
         }
@@ -543,6 +609,19 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           ADMM_MV(NX, NU, false, AIB, uu, xk);      //       + AIB u
 #pragma unroll
           for (int i = 0; i < NX; ++i) x[i] = xk[i];
+          if constexpr (L_NR) {
+            // block k stores x_{k+1}: its dual-residual term is |dx_{k+1}|^2, then the mirror recursion
+            // dx_k = AI_k dx_{k+1} + AIB_k (u+ - u_old) while AI_k, AIB_k sit in the operand registers
+            double du[NU], dxk[NX];
+#pragma unroll
+            for (int jj = 0; jj < NU; ++jj) du[jj] = uu[jj] - wo[jj];
+#pragma unroll
+            for (int i = 0; i < NX; ++i) { a_sx = fma(dx[i], dx[i], a_sx); dxk[i] = 0.0; }
+            ADMM_MV(NX, NX, false, AI, dx, dxk);
+            ADMM_MV(NX, NU, false, AIB, du, dxk);
+#pragma unroll
+            for (int i = 0; i < NX; ++i) dx[i] = dxk[i];
+          }
         }
         __builtin_amdgcn_sched_barrier(0);
         // ---- z-update, dual ascent, residual partials ----
@@ -571,12 +650,14 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
 #pragma unroll
           for (int r = r3; r < r3 + 3 && r < NB; ++r) {
             if (XFREE && r >= NU) {             // unbounded state row: see xfze_kernel
-              if (XFREE != 2) vv.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, r0 + r * PB);
+              if (XFREE != 2 && !L_NW) vv.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, r0 + r * PB);
               g[r] = -rho * wv[r];
               if (HASQ) g[r] += cq[r];
               if (RESID) {
-                const double ds = wv[r] - c0[r];
-                a_s = fma(ds, ds, a_s);
+                if (!L_NR) {
+                  const double ds = wv[r] - c0[r];
+                  a_s = fma(ds, ds, a_s);
+                }
                 a_w = fma(wv[r], wv[r], a_w);
                 a_z = fma(wv[r], wv[r], a_z);
               }
@@ -591,6 +672,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
             const double vn = wh + yo;
             if (!(XFREE == 2 && r >= NU))
               vv.store<ADMM_ALT_STORE_AUX>(vn, lb_st, r0 + r * PB);
+            if (L_SD && r < NU) vw.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, (unsigned)SIDX(k) * NU * PB + r * PB);
             const double zn = fmin(fmax(ball ? vn * cs_new : vn, lo), hi);
             const double yn = vn - zn;
             g[r] = -rho * (zn - yn);
@@ -646,11 +728,12 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
     for (int i = 0; i < NX; ++i) {
       tseg[o + i * P] = t[i];
       eseg[o + i * P] = e[i];
+      if (L_SD) xbnd[o + i * P] = x[i];      // the rolled-out state at the segment's start: where the next (forward) form starts its dx
     }
     if (RESID) {
       const size_t op = (size_t)s * 5 * P + col;
       part[op + 0 * P] = a_r;
-      part[op + 1 * P] = a_s;
+      part[op + 1 * P] = L_NR ? a_s + a_sx : a_s;
       part[op + 2 * P] = a_w;
       part[op + 3 * P] = a_z;
       part[op + 4 * P] = a_y;

@@ -17,12 +17,14 @@ admm::XLaunch xlaunch_of(const admm_handle* h) {
   l.n = h->n; l.m = h->m; l.S = h->S; l.pitch = h->pitch; l.batch = h->batch; l.xfree = h->xfree ? h->xfree_mode : 0;
   l.has_q = h->has_q;
   l.has_soc = h->has_soc;
+  l.lean = h->lean_mode; l.wu = h->wu; l.xbnd = h->xbnd;
   l.rho = h->opt.rho; l.alpha = h->opt.alpha;
   l.z = h->z; l.y = h->y; l.q = h->q; l.v = h->v; l.w = h->w;
   l.recB = h->recB; l.recF = h->recF; l.recS = h->recS; l.seg_start = h->seg_start;
   l.recFE = h->recFE; l.recBE = h->recBE; l.mvec = h->mvec;
   l.dbuf = h->dbuf; l.tseg = h->tseg; l.eseg = h->eseg; l.tin = h->tin; l.xin = h->xin; l.part = h->part;
   l.x0 = h->x0;
+  if (h->ts_n) l.lean = 0;
   if (h->ts_n) {        // time shard: the kernels see this rank's segments only (per-segment arrays start at its first one)
     const size_t o = (size_t)h->ts_s0 * h->n * h->pitch;
     l.S = h->ts_sl;
@@ -255,6 +257,14 @@ IterForm next_form(const admm_handle* h, int remaining) {
   return remaining >= 2 ? IT_FWD_START : IT_PLAIN;
 }
 
+// Lean residual forms (admm_kernels_alt.hpp): a one-lane fp64 alternating handle of a compiled shape whose state rows are
+// unbounded everywhere, without q, thrust bound, over-relaxation or time shards.  ADMM_NO_LEAN_RESID=1 restores the full forms.
+bool lean_capable(const admm_handle* h) {
+  const bool off = std::getenv("ADMM_NO_LEAN_RESID") != nullptr;      // (read per call: tests and A/B runs toggle it in one process)
+  return !off && h->alt && h->xfree && h->wu && h->xbnd && !h->has_q && !h->has_soc && !h->pinst && !h->ts_n &&
+         h->opt.alpha == 1.0 && !h->mfma_on && !h->mfma_refine && admm::alt_lean_dims(h->n, h->m);
+}
+
 // fin_prev: the previous iteration evaluated residuals and left their finalise to this scan launch
 int enqueue_form(admm_handle* h, IterForm f, bool resid, bool fin_prev) {
   int rc;
@@ -264,6 +274,8 @@ int enqueue_form(admm_handle* h, IterForm f, bool resid, bool fin_prev) {
 }
 
 void after_form(admm_handle* h, IterForm f) {
+  h->side_valid = h->lean_mode != 0;         // (0 on every path but enqueue_one's direct launches)
+  h->side_dir = f == IT_BWD ? admm_handle::ALT_BWD : admm_handle::ALT_FWD;
   h->v_valid = true; h->zy_valid = false; h->w_stale = true;
   h->alt_state = f == IT_PLAIN ? admm_handle::ALT_NONE : (f == IT_BWD ? admm_handle::ALT_BWD : admm_handle::ALT_FWD);
 }
@@ -288,6 +300,7 @@ int enqueue_iteration(admm_handle* h, bool resid, bool use_v) {
 // bookkeeping after `count` enqueued iterations
 void after_iterations(admm_handle* h, int count) {
   if (count <= 0) return;
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
   if (fused(h)) { h->v_valid = true; h->zy_valid = false; h->w_stale = true; }
   else          { h->zy_valid = true; h->v_valid = false; h->w_stale = false; }
@@ -305,6 +318,7 @@ int ensure_w(admm_handle* h) {
 
 int step_x(admm_handle* h) {
   int rc;
+  drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;     // xb and the scan overwrite what a fused elimination left
   if ((rc = launch_xb(h, h->v_valid))) return rc;
   if ((rc = launch_xscan(h))) return rc;
@@ -340,9 +354,11 @@ int capture_iterations(admm_handle* h) {
 // it selects the iteration form (next_form).  it_number > 0: a checked iteration of admm_solve
 // (residuals + finalise with that iteration number, launched directly).
 // next_plain: another iteration follows in this call and evaluates no residuals (admm_run / admm_solve_step know).
-int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int it_number, bool next_plain) {
+// next_resid: another iteration follows in this call and evaluates residuals (admm_run knows).
+int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int it_number, bool next_plain, bool next_resid) {
   int rc;
   h->xfree_mode = 1;                       // (never inherited: an error path of admm_profile could have left it set)
+  h->lean_mode = 0;
   const bool steady = fused(h) ? h->v_valid : h->zy_valid;
   if (!fused(h) && !h->zy_valid && (rc = ensure_zy(h))) return rc;
   const IterForm form = next_form(h, remaining);
@@ -357,11 +373,31 @@ int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int i
       const bool next_alternates = form == IT_BWD || (remaining - 1 >= 1 && (remaining - 1) % 2 == 0);
       static const bool no_skip_store = std::getenv("ADMM_NO_SKIPV_STORE") != nullptr;
       h->xfree_mode = (next_plain && !resid && next_alternates && h->opt.alpha == 1.0 && !no_skip_store) ? 2 : 1;
+      // Lean residual forms: consecutive residual iterations of admm_run.
+      //   SD: a residual iteration leaves w_u and its end-of-segment states when its successor can use them -- the next
+      //       iteration of this call evaluates residuals, or the call ends here (the next call may resume lean);
+      //   NR: v of the state rows is not read when the PREDECESSOR was a residual alternating iteration of the OPPOSITE
+      //       direction that left valid side data, and nothing has dropped it since (drop_side_data).  An iteration after
+      //       one without residuals is never lean -- it would pay at check_interval 10, but s then differs in the last
+      //       bits where test_skipping_v_of_unbounded_state_rows_is_exact compares it bit for bit -- and neither is a
+      //       start form (xb + xfze after a forward form) nor a checked iteration of the stepwise admm_solve path;
+      //   NW: v of the state rows is not written when the successor IN THIS CALL is such an NR iteration.  The last
+      //       iteration of a call therefore always writes the full state.
+      const int dir = form == IT_BWD ? admm_handle::ALT_BWD : admm_handle::ALT_FWD;
+      const bool cap = resid && it_number == 0 && lean_capable(h);
+      const bool nr = cap && form != IT_FWD_START && h->side_valid && h->side_dir != dir;
+      const bool sd = cap && (next_resid || remaining == 1);
+      const bool nw = sd && next_resid && next_alternates;
+      if (h->v_rows_stale && !nr) return fail(ADMM_ERR_INVALID, "internal: a full-read iteration after one that did not write v of the state rows");
+      if (nr || sd) h->lean_mode = admm::ALT_LEAN_SD | (nr ? admm::ALT_LEAN_NR : 0) | (nw ? admm::ALT_LEAN_NW : 0);
       rc = enqueue_form(h, form, resid, fin_prev);
       h->xfree_mode = 1;
-      if (rc) return rc;
+      if (rc) { h->lean_mode = 0; return rc; }
+      h->v_rows_stale = nw;
+      if (nr) ++h->lean_count;
     }
     after_form(h, form);
+    h->lean_mode = 0;
     h->fin_pending = resid;                 // carried by the next scan launch, or flushed by the caller
     if (resid) h->resid_valid = true;
     if (it_number > 0) return flush_finalize(h, it_number);

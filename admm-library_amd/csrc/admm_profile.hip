@@ -12,9 +12,10 @@ int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused
   if (h->pinst && fused_path != 1) return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: per-instance dynamics run the plain fused path only (fused_path = 1)");
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_profile is not available on a time-sharded handle");
   h->xfree_mode = 1;
+  drop_side_data(h);                          // modes 0 .. 3 time the full-read / full-write forms; none leaves side data
   HIP_TRY(hipSetDevice(h->device));
   constexpr int NE = 6;     // events per iteration
-  if ((fused_path == 2 || fused_path == 3) && !h->alt) return fail(ADMM_ERR_UNSUPPORTED, "the alternating-direction kernels are not enabled for this handle");
+  if ((fused_path == 2 || fused_path == 3 || fused_path == 4) && !h->alt) return fail(ADMM_ERR_UNSUPPORTED, "the alternating-direction kernels are not enabled for this handle");
   if (fused_path == 3) {
     // Back-to-back mode: a cross-check of mode 2 that records NO event between launches.  The two fused kernels are
     // launched as `iters` consecutive (xfze, xbze) pairs with no scan in between -- same bytes, same instructions and
@@ -81,6 +82,10 @@ int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused
   int rc = ADMM_OK;
   const bool res = residuals != 0;
   h->alt_state = admm_handle::ALT_NONE;       // the plain kernels are profiled; they overwrite the scan operands
+  const bool lean4 = fused_path == 4;          // mode 4 = mode 2 with the lean residual forms (admm_kernels_alt.hpp, LEAN)
+  if (lean4 && !(residuals && lean_capable(h)))
+    return fail(ADMM_ERR_UNSUPPORTED, "admm_profile mode 4: the lean residual forms do not apply to this handle (or residuals = 0)");
+  if (lean4) fused_path = 2;
   if (fused_path == 2) {
     // `iters` PAIRS of alternating iterations (forward form, backward form); ms[] = scan, xfze,
     // scan, xbze, 0, whole pair (with residuals each scan launch also finalises the iteration before
@@ -98,18 +103,23 @@ int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused
       HIP_TRY(hipEventRecord(e[0], h->stream));
       rc = launch_xscan_mfma(h, false, res && it > 0);
       HIP_TRY(hipEventRecord(e[1], h->stream));
+      // (lean: the very first kernel follows xb_kernel and reads the full state; every later one is NR | NW | SD)
+      if (lean4) h->lean_mode = it == 0 ? (admm::ALT_LEAN_SD | admm::ALT_LEAN_NW) : (admm::ALT_LEAN_SD | admm::ALT_LEAN_NW | admm::ALT_LEAN_NR);
       if (!rc) rc = launch_x(h, admm::XKernel::XFZE, false, res);
       HIP_TRY(hipEventRecord(e[2], h->stream));
       if (!rc) rc = launch_xscan_mfma(h, true, res);
       HIP_TRY(hipEventRecord(e[3], h->stream));
+      if (lean4) h->lean_mode = admm::ALT_LEAN_SD | admm::ALT_LEAN_NW | admm::ALT_LEAN_NR;
       if (!rc) rc = launch_x(h, admm::XKernel::XBZE, false, res);
       HIP_TRY(hipEventRecord(e[4], h->stream));
       HIP_TRY(hipEventRecord(e[5], h->stream));
     }
     h->xfree_mode = 1;
+    if (lean4) h->lean_mode = admm::ALT_LEAN_SD | admm::ALT_LEAN_NR;      // the closing form writes the full state again
     if (!rc) rc = enqueue_form(h, IT_FWD, res, res);      // never stop after the backward form
     if (!rc && res) rc = launch_finalize(h, 0, h->S);
     if (!rc) after_form(h, IT_FWD);
+    h->lean_mode = 0;
   }
   for (int it = 0; it < iters && !rc && fused_path != 2; ++it) {
     hipEvent_t* e = &ev[(size_t)it * NE];

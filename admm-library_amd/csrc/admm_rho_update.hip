@@ -182,6 +182,7 @@ int set_rho_internal(admm_handle* h, double rho_new) {
   }
   h->zy_valid = true;
   h->v_valid = false;
+  drop_side_data(h);
   HIP_TRY(hipStreamSynchronize(h->stream));                // kernels of the old rho are done before the records change
   lap("state to (z, y), sync");
   if (spec_enabled(h)) {                                   // the rule may come back to the rho it leaves: keep that factor
@@ -302,6 +303,7 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
   if ((rc = ensure_zy(h))) return rc;          // the state is kept as the (z, y) pair it was under the old box
   h->zy_valid = true;
   h->v_valid = false;
+  drop_side_data(h);
   HIP_TRY(hipStreamSynchronize(h->stream));    // kernels of the old records are done before they change
   h->spec.clear();                             // background factorisations read the problem copy that changes now
   h->spec_stale.clear();

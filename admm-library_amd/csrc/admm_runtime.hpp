@@ -47,6 +47,13 @@ struct admm_handle {
   int num_cus = 256;             // hipDeviceProp_t::multiProcessorCount of the handle's device
   bool xfree = false;            // every state row is unbounded at every stage (XFREE kernel forms, see xfze_kernel)
   int xfree_mode = 1;            // 2 while enqueue_one launches an iteration whose successor will not read those rows' v
+  // Lean residual iterations (admm_kernels_alt.hpp, LEAN forms): side data of the last iterate and its validity
+  double *wu = nullptr, *xbnd = nullptr;   // w_u [stage][m][pitch] (window and bias of mvec); end-of-segment states [S][n][pitch]
+  int lean_mode = 0;             // ALT_LEAN_* bits while enqueue_one launches a lean form, else 0 (the full forms)
+  bool side_valid = false;       // wu / xbnd describe the iterate in h->v: the last iteration was a residual alternating one that wrote them
+  int side_dir = 0;              // ... and ran in this direction (ALT_FWD / ALT_BWD): a lean read needs the opposite one
+  bool v_rows_stale = false;     // the last launch was an NW form: the next one must be NR (same call, enqueue_one)
+  long long lean_count = 0;      // iterations launched with the no-read form since setup (admm_get_lean_iterations)
   bool auto_segments = false;    // the segment count was chosen by admm_setup (and is guarded by scan_growth)
   bool has_q = false;
   bool has_soc = false;          // some stage has a finite thrust-magnitude bound, or the handle has a fuel term
@@ -250,7 +257,8 @@ void after_iterations(admm_handle* h, int count);
 int ensure_w(admm_handle* h);
 int step_x(admm_handle* h);
 int capture_iterations(admm_handle* h);
-int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int it_number = 0, bool next_plain = false);
+int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int it_number = 0, bool next_plain = false,
+                bool next_resid = false);
 
 // ---- host <-> device transfers, validation, uploads of the factor, handle lifetime (admm_hostio.hip)
 int upload_h2d(admm_handle* h, void* dst, const void* src, size_t bytes);
@@ -337,6 +345,9 @@ inline int launch_xf(admm_handle* h) { return launch_x(h, admm::XKernel::XF, fal
 // vin: previous state read from h->v, otherwise from h->z / h->y.
 inline int launch_xfz(admm_handle* h, bool resid, bool vin) { return launch_x(h, admm::XKernel::XFZ, vin, resid); }
 inline bool fused(const admm_handle* h) { return !(h->opt.flags & ADMM_FLAG_UNFUSED); }
+// whatever changes the state, the factor or the instance data outside enqueue_one drops the lean forms' side data
+inline void drop_side_data(admm_handle* h) { h->side_valid = false; h->lean_mode = 0; }
+bool lean_capable(const admm_handle* h);
 inline int chunks_of_iteration(const admm_handle* h) { return fused(h) ? h->S : h->zchunks; }
 
 }  // namespace rt

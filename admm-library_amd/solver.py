@@ -52,6 +52,7 @@ _SIGNATURES = {
     "admm_solve_end": (C.c_int, [C.c_void_p, C.POINTER(CInfo)]),
     "admm_iterate": (C.c_int, [C.c_void_p, C.c_int32]),
     "admm_run": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "admm_get_lean_iterations": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "admm_sync": (C.c_int, [C.c_void_p]),
     "admm_step_x": (C.c_int, [C.c_void_p]),
     "admm_step_z": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -424,6 +425,12 @@ class Solver:
         if sync:
             self.sync()
 
+    def lean_iterations(self) -> int:
+        """admm_get_lean_iterations: iterations launched so far in the lean residual form."""
+        n = C.c_int64(0)
+        _check(self._lib, self._lib.admm_get_lean_iterations(self._h, C.byref(n)))
+        return int(n.value)
+
     def sync(self):
         _check(self._lib, self._lib.admm_sync(self._h))
 
@@ -453,13 +460,14 @@ class Solver:
         return tuple(outs)
 
     def profile(self, iters: int, residuals: bool = True, fused: bool = True, alternating: bool = False,
-                back_to_back: bool = False):
+                back_to_back: bool = False, lean: bool = False):
         """Per-kernel HIP-event timings (ms).  alternating: `iters` PAIRS of the alternating-direction
         iteration (forward form, backward form) instead of the plain kernels; with
         back_to_back each of the pair's kernels is launched `iters` times in a row between two events
-        (admm_profile mode 3: no event-record bubble inside the averages)."""
+        (admm_profile mode 3: no event-record bubble inside the averages); with lean the pairs run in the lean
+        residual forms (mode 4; raises where they do not apply)."""
         ms = np.zeros(6)
-        mode = (3 if back_to_back else 2) if alternating else int(bool(fused))
+        mode = (4 if lean else 3 if back_to_back else 2) if alternating else int(bool(fused))
         _check(self._lib, self._lib.admm_profile(self._h, int(iters), int(bool(residuals)), mode, dptr(ms)))
         if alternating:
             return {"xscan_ms": ms[0], "xfze_ms": ms[1], "finalize_xscan_ms": ms[2], "xbze_ms": ms[3],

@@ -257,6 +257,10 @@ int admm_iterate(admm_handle* h, int32_t iters);
  * residual_every = 1 is the benchmark's "step": x-update + fused
  * z/dual/residual-partials + finalise, every iteration. */
 int admm_run(admm_handle* h, int32_t iters, int32_t residual_every);
+/* Iterations launched since setup in the lean residual form: consecutive residual-evaluating iterations of admm_run on a
+ * handle whose state rows are unbounded at every stage neither read nor write v of those rows.
+ * Diagnostic: 0 on every handle the form does not apply to, and with ADMM_NO_LEAN_RESID=1 in the environment. */
+int admm_get_lean_iterations(admm_handle* h, int64_t* count);
 int admm_sync(admm_handle* h);
 
 /* Single steps, for kernel-level parity tests. */
@@ -310,6 +314,8 @@ int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, do
  * (xfze, xbze) pairs without the scans, then each scan form `iters` times in a row,
  *   ms = {xscan (W), mean of xfze and xbze, xscan (WB) (+ finalise role), the same mean, 0, sum of the four}
  * (not ADMM iterates: the state is parked, restored, and ONE plain iteration is applied to leave the handle consistent).
+ * fused_path == 4: as 2, with the pair in its lean residual forms (admm_get_lean_iterations; residuals must be set;
+ * ADMM_ERR_UNSUPPORTED where the forms do not apply).  Modes 2 and 3 always time the full-read / full-write forms.
  * xb = x-update backward sweep, xscan = segment scan, xf = forward rollout,
  * zdual = standalone fused z/dual/residual kernel, xfz = forward rollout fused
  * with z/dual/residual.  `residuals` selects the residual-evaluating kernel
