@@ -2,6 +2,7 @@
 // admm_launch.hip, admm_hostio.hip, admm_rho_update.hip, admm_pinst_rt.hip, admm_profile.hip (admm_runtime.hpp).  No CPU fallback: without a HIP device
 // every compute entry point returns ADMM_ERR_NO_DEVICE.
 #include "admm_runtime.hpp"
+#include "admm_cert.hpp"
 
 
 using namespace admm::rt;
@@ -1015,6 +1016,133 @@ int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_s
   HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
   HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
   return ADMM_OK;
+}
+
+// ---- certificate (kernels in admm_cert_kernels.hpp) ----
+
+// Device copies of the raw problem (A_k | B_k per stage, Q | QN | R symmetrised, the segment products Phi_s) and the work
+// buffers, on the first call and after admm_update_problem; the fuel weights whenever they differ from the copy on the device.
+static int cert_prepare(admm_handle* h, bool want_nu) {
+  int rc;
+  const int n = h->n, m = h->m, N = h->N, S = h->S;
+  const size_t P = h->pitch, rab = (size_t)n * (n + m);
+  if (!h->certAB) {
+    if ((rc = dalloc(&h->certAB, (size_t)N * rab)) || (rc = dalloc(&h->certQR, (size_t)2 * n * n + (size_t)m * m)) ||
+        (rc = dalloc(&h->certPhi, (size_t)S * n * n)) || (rc = dalloc(&h->cert_fuel, (size_t)N)) ||
+        (rc = dalloc(&h->cert_cseg, (size_t)S * n * P)) || (rc = dalloc(&h->cert_cin, (size_t)S * n * P)) ||
+        (rc = dalloc(&h->cert_part, (size_t)S * 3 * P)) || (rc = dalloc(&h->cert_out, 3 * P)))
+      return rc;
+    h->cert_valid = false;
+    h->cert_fuel_h.clear();
+  }
+  if (want_nu && !h->cert_nu && (rc = dalloc(&h->cert_nu, (size_t)N * n * P))) return rc;
+  bool uploaded = false;
+  std::vector<double> ab, qr, phi;          // (alive until the synchronisation below)
+  if (!h->cert_valid) {
+    ab.resize((size_t)N * rab);
+    for (int k = 0; k < N; ++k) {
+      const double* A = h->pA.data() + (h->time_varying ? (size_t)k * n * n : 0);
+      const double* B = h->pB.data() + (h->time_varying ? (size_t)k * n * m : 0);
+      std::copy(A, A + (size_t)n * n, ab.begin() + (size_t)k * rab);
+      std::copy(B, B + (size_t)n * m, ab.begin() + (size_t)k * rab + (size_t)n * n);
+    }
+    qr.resize((size_t)2 * n * n + (size_t)m * m);
+    auto sym = [](const std::vector<double>& a, int d, double* out) {      // as admm_setup symmetrises the weights
+      for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) out[(size_t)i * d + j] = 0.5 * (a[(size_t)i * d + j] + a[(size_t)j * d + i]);
+    };
+    sym(h->pQ, n, qr.data());
+    sym(h->pQN, n, qr.data() + (size_t)n * n);
+    sym(h->pR, m, qr.data() + (size_t)2 * n * n);
+    // Phi_s = A_k0' A_k0+1' ... A_k1-1' (row-major), built from the segment's last stage down
+    phi.assign((size_t)S * n * n, 0.0);
+    std::vector<double> t((size_t)n * n);
+    for (int s = 0; s < S; ++s) {
+      double* F = phi.data() + (size_t)s * n * n;
+      for (int i = 0; i < n; ++i) F[(size_t)i * n + i] = 1.0;
+      for (int k = h->fac.seg_start[s + 1] - 1; k >= h->fac.seg_start[s]; --k) {
+        const double* A = ab.data() + (size_t)k * rab;                      // column-major: A'(i, l) = A[l + i n]
+        for (int i = 0; i < n; ++i)
+          for (int j = 0; j < n; ++j) {
+            double a = 0.0;
+            for (int l = 0; l < n; ++l) a += A[(size_t)l + (size_t)i * n] * F[(size_t)l * n + j];
+            t[(size_t)i * n + j] = a;
+          }
+        std::copy(t.begin(), t.end(), F);
+      }
+    }
+    HIP_TRY(hipMemcpyAsync(h->certAB, ab.data(), sizeof(double) * ab.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->certQR, qr.data(), sizeof(double) * qr.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->certPhi, phi.data(), sizeof(double) * phi.size(), hipMemcpyHostToDevice, h->stream));
+    uploaded = true;
+  }
+  std::vector<double> fu(N, 0.0);
+  if (h->has_fuel) fu = h->fuel;
+  if (fu != h->cert_fuel_h) {
+    HIP_TRY(hipMemcpyAsync(h->cert_fuel, fu.data(), sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
+    uploaded = true;
+  }
+  if (uploaded) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->cert_valid = true;
+    h->cert_fuel_h = fu;
+  }
+  return ADMM_OK;
+}
+
+static int certificate_common(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, bool dev, void* hip_stream) {
+  const char* fn = dev ? "admm_get_certificate_device" : "admm_get_certificate";
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (h->pinst) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2)");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  const size_t bsz = sizeof(double) * (size_t)h->batch, nusz = bsz * (size_t)h->N * h->n;
+  if (dev && ((obj && (rc = check_device_ptr(h->device, obj, bsz, fn, "obj"))) ||
+              (feas_dyn && (rc = check_device_ptr(h->device, feas_dyn, bsz, fn, "feas_dyn"))) ||
+              (stat && (rc = check_device_ptr(h->device, stat, bsz, fn, "stat"))) ||
+              (nu && (rc = check_device_ptr(h->device, nu, nusz, fn, "nu")))))
+    return rc;
+  admm::CertLaunch l{};
+  l.n = h->n; l.m = h->m;
+  if (!admm::launch_cert(l, /*query_only=*/true))
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": no certificate kernel for this (n, m)");
+  if ((rc = ensure_zy(h))) return rc;                   // the state as the (z, y) pair, as admm_get reads it
+  if ((rc = cert_prepare(h, nu != nullptr))) return rc;
+  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
+  l.stream = h->stream;
+  l.N = h->N; l.S = h->S; l.pitch = h->pitch;
+  l.has_q = h->has_q;
+  l.rho = h->opt.rho;
+  l.z = h->z; l.y = h->y; l.q = h->q; l.x0 = h->x0;
+  l.AB = h->certAB; l.QR = h->certQR; l.Phi = h->certPhi; l.fuel = h->cert_fuel;
+  l.seg_start = h->seg_start;
+  l.cseg = h->cert_cseg; l.cin = h->cert_cin; l.part = h->cert_part; l.out = h->cert_out;
+  l.nu = nu ? h->cert_nu : nullptr;
+  admm::launch_cert(l, false);
+  HIP_TRY(hipGetLastError());
+  double* dst[3] = {obj, feas_dyn, stat};
+  for (int v = 0; v < 3; ++v)
+    if (dst[v])
+      HIP_TRY(hipMemcpyAsync(dst[v], h->cert_out + (size_t)v * h->pitch, bsz, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  if (nu && (rc = download_transposed(h, h->cert_nu, nu, h->N * h->n, dev))) return rc;
+  if (!dev || !hip_stream) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
+  return ADMM_OK;
+}
+
+int admm_get_certificate(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu) {
+  return certificate_common(h, obj, feas_dyn, stat, nu, false, nullptr);
+}
+
+// The device-memory form: the rules of admm_get_device (pointer checks, ordering against hip_stream, no host synchronisation
+// once the operands are on the device).
+int admm_get_certificate_device(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, void* hip_stream) {
+  return certificate_common(h, obj, feas_dyn, stat, nu, true, hip_stream);
 }
 
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s) {

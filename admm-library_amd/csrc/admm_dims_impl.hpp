@@ -2,9 +2,11 @@
 //   ADMM_GROUP_FN    launch_groupK
 //   ADMM_GROUP_LIST  dims_groupK
 //   ADMM_GROUP_DIMS(X)   X(n, m) X(n, m) ...
+//   ADMM_CERT_FN     launch_cert_groupK   (certificate kernels of the group's pairs, admm_cert_kernels.hpp)
 #include "admm_dispatch.hpp"
 #include "admm_kernels.hpp"
 #include "admm_kernels_alt.hpp"
+#include "admm_cert_kernels.hpp"
 
 namespace admm {
 
@@ -116,6 +118,17 @@ bool ADMM_GROUP_FN(const XLaunch& l, XKernel k, bool a, bool b, bool query_only)
     if ((k == XKernel::XFZE || k == XKernel::XBZE) && !alt_dims(NX, NU)) return false; \
     if (!query_only) launch_dim<NX, NU>(l, k, a, b); \
     return true;                                \
+  }
+  ADMM_GROUP_DIMS(X)
+#undef X
+  return false;
+}
+
+bool ADMM_CERT_FN(const CertLaunch& l, bool query_only) {
+#define X(NX, NU)                                \
+  if (l.n == NX && l.m == NU) {                  \
+    if (!query_only) launch_cert_dim<NX, NU>(l); \
+    return true;                                 \
   }
   ADMM_GROUP_DIMS(X)
 #undef X

@@ -433,6 +433,9 @@ void release(admm_handle* h) {
   }
   if (h->ext_ev) { (void)hipEventDestroy(h->ext_ev); h->ext_ev = nullptr; }
   if (h->chk_d) { (void)hipFree(h->chk_d); h->chk_d = nullptr; }
+  for (double** b : {&h->certAB, &h->certQR, &h->certPhi, &h->cert_fuel, &h->cert_cseg, &h->cert_cin, &h->cert_part, &h->cert_out,
+                     &h->cert_nu})
+    if (*b) { (void)hipFree(*b); *b = nullptr; }
   if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
   delete h;
 }
@@ -533,6 +536,7 @@ void keep_shared(admm_handle* h, const admm_problem* p) {
   if (p->unorm) h->pun.assign(p->unorm, p->unorm + (p->stage_bounds ? p->N : 1));
   h->time_varying = p->time_varying;
   h->stage_bounds = p->stage_bounds;
+  h->cert_valid = false;           // the certificate's device copy of A, B, Q, R, QN is of the old problem
   // every STATE row unbounded at EVERY stage: its dual is identically zero, which lets the non-residual kernel forms
   // skip reading its v (XFREE, xfze_kernel)
   bool open = std::getenv("ADMM_NO_SKIPV") == nullptr;

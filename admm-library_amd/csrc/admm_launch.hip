@@ -1,7 +1,15 @@
 // admm_launch.hip -- solver runtime: kernel launches, the time-shard exchange, iteration forms and their schedule, graph capture (admm_runtime.hpp)
 #include "admm_runtime.hpp"
+#include "admm_cert.hpp"
 
 namespace admm {
+
+// certificate kernels (admm_cert_kernels.hpp): instantiated group by group beside the one-lane family
+bool launch_cert(const CertLaunch& l, bool query_only) {
+  return launch_cert_group0(l, query_only) || launch_cert_group1(l, query_only) || launch_cert_group2(l, query_only) ||
+         launch_cert_group3(l, query_only);
+}
+
 namespace rt {
 
 thread_local std::string g_err;

@@ -151,6 +151,12 @@ struct admm_handle {
   // the *_device entry points (ABI v9): ordering against the caller's stream, result slots of the device-side checks
   hipEvent_t ext_ev = nullptr;
   unsigned long long* chk_d = nullptr;
+  // certificate (admm_cert_kernels.hpp): raw problem operands and work buffers, allocated and uploaded on the first
+  // admm_get_certificate* call; keep_shared() (admm_setup, admm_update_problem) invalidates the operands
+  double *certAB = nullptr, *certQR = nullptr, *certPhi = nullptr, *cert_fuel = nullptr;
+  double *cert_cseg = nullptr, *cert_cin = nullptr, *cert_part = nullptr, *cert_out = nullptr, *cert_nu = nullptr;
+  bool cert_valid = false;       // certAB / certQR / certPhi describe the handle's current problem
+  std::vector<double> cert_fuel_h;   // the weights cert_fuel holds (compared with h->fuel at call time)
   int iters_run = 0;
   bool resid_valid = false;
   // A residual-evaluating alternating iteration leaves its finalise to the NEXT scan launch (finalise

@@ -90,6 +90,9 @@ _SIGNATURES = {
     "admm_update_instances_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_void_p]),
     "admm_set_state_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "admm_get_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    # certificate: costates, objective, optimality measures (ADMM_HIP_HAS_CERTIFICATE)
+    "admm_get_certificate": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "admm_get_certificate_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),
@@ -195,6 +198,17 @@ class SolveInfo:
     status: np.ndarray
     r: np.ndarray
     s: np.ndarray
+
+
+@dataclasses.dataclass
+class Certificate:
+    """Solver.certificate(): per-QP objective, dynamics defect and stationarity defect of the handle's current (z, y) pair
+    (DESIGN.md §2.9), and the costates nu_1 .. nu_N as (batch, N, n) if asked for.  NumPy arrays, or CUDA tensors on a solver
+    built from a DeviceProblem."""
+    obj: object
+    feas_dyn: object
+    stat: object
+    nu: object = None
 
 
 class Solver:
@@ -449,6 +463,24 @@ class Solver:
         outs = [np.empty((self.batch, self.L)) if f else None for f in (w, z, y)]
         _check(self._lib, self._lib.admm_get(self._h, *[dptr(o) for o in outs]))
         return tuple(outs)
+
+    def certificate(self, costates: bool = False) -> Certificate:
+        """admm_get_certificate: objective (fuel term included), max dynamics defect and max stationarity defect of every QP at
+        the current (z, y) pair with mu = rho y, computed on the device; costates=True adds the multipliers nu_{k+1} of the
+        dynamics rows, (batch, N, n) -- B_k' nu_{k+1} is the primer vector.  A solver built from a DeviceProblem returns CUDA
+        tensors through admm_get_certificate_device, ordered on torch's current stream."""
+        N, n = self.problem.N, self.problem.n
+        if isinstance(self.problem, DeviceProblem):
+            import torch
+            dev = f"cuda:{self._device()}"
+            outs = [torch.empty(self.batch, dtype=torch.float64, device=dev) for _ in range(3)]
+            nu = torch.empty((self.batch, N, n), dtype=torch.float64, device=dev) if costates else None
+            _check(self._lib, self._lib.admm_get_certificate_device(self._h, *[_tptr(o) for o in outs], _tptr(nu), _stream(dev)))
+            return Certificate(outs[0], outs[1], outs[2], nu)
+        outs = [np.empty(self.batch) for _ in range(3)]
+        nu = np.empty((self.batch, N, n)) if costates else None
+        _check(self._lib, self._lib.admm_get_certificate(self._h, *[dptr(o) for o in outs], dptr(nu)))
+        return Certificate(outs[0], outs[1], outs[2], nu)
 
     def get_device(self, w=True, z=True, y=True):
         """The state as (batch, L) fp64 tensors on the handle's GPU (None where not asked for), written by admm_get_device and

@@ -297,6 +297,25 @@ int admm_update_instances_device(admm_handle* h, const double* x0, const double*
 int admm_set_state_device(admm_handle* h, const double* w, const double* z, const double* y, void* hip_stream);
 int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_stream);
 
+/* Certificate of a handle's current point (new symbols, announced by ADMM_HIP_HAS_CERTIFICATE -- no struct or
+ * signature changed): costates of the dynamics, objective and optimality measures of every QP, computed on the device from the
+ * (z, y) pair with mu = rho y (rho: the value in force) and g = P z + q + mu:
+ *   nu        nu_N = -g^x_N,  nu_k = A_k' nu_{k+1} - g^x_k  (k = N-1 .. 1): nu_{k+1} is the multiplier of stage k's dynamics row, and
+ *             the state rows of g + G'nu are zero by construction; B_k' nu_{k+1} is the primer vector
+ *   stat      max_k |g^u_k - B_k' nu_{k+1}|_inf: the whole stationarity defect of the original QP (not of the ADMM splitting)
+ *   feas_dyn  max_k |x_{k+1} - A_k x_k - B_k u_k|_inf on z
+ *   obj       1/2 z'Pz + q'z + sum_k fuel_k ||z_u,k||_2  (the weights of admm_get_fuel)
+ * Any output pointer may be NULL; obj, feas_dyn, stat: batch entries; nu: N*n*batch, QP b at [b*N*n, (b+1)*N*n), stage-major
+ * (nu_1 .. nu_N).  The call brings the state into the (z, y) pair exactly as admm_get does and changes nothing else: iterating
+ * on gives the same bits as after admm_get.  Only what was asked for is copied out (batch doubles per scalar output).
+ * admm_get_certificate_device: the outputs are device memory of the handle's GPU, under the rules of admm_get_device (pointer
+ * checks naming the argument, hip_stream ordering, no host synchronisation, 8-byte alignment).
+ * Batch-shared dynamics (time_varying 0 or 1) on every iteration path; ADMM_ERR_UNSUPPORTED, before anything is launched, with
+ * per-instance dynamics (time_varying = 2) and on time-sharded handles. */
+#define ADMM_HIP_HAS_CERTIFICATE 1
+int admm_get_certificate(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu);
+int admm_get_certificate_device(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, void* hip_stream);
+
 /* Per-QP results of the last admm_solve: first checked iteration at which the
  * rule held (max_iter if never), status (1 converged / 0 not), last r and s. */
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s);
