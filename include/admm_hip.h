@@ -338,7 +338,13 @@ int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, do
  * xb = x-update backward sweep, xscan = segment scan, xf = forward rollout,
  * zdual = standalone fused z/dual/residual kernel, xfz = forward rollout fused
  * with z/dual/residual.  `residuals` selects the residual-evaluating kernel
- * forms (+ the finalise kernel). */
+ * forms (+ the finalise kernel).
+ * The call ADVANCES the state, by ordinary ADMM iterations: `iters` of them in modes 0 and 1, 2 iters + 1 in modes 2 and 4 (the
+ * pairs, then one forward form: a call never returns after a backward form), one in mode 3.  Modes 2, 3 and 4 start from the
+ * state as v = z + y: when the handle holds it as the (z, y) pair -- after admm_setup, admm_set_state with z or y, admm_set_rho,
+ * admm_update_problem, admm_set_fuel, admm_step_z, a rho change of admm_solve_adapt, or iterations of an ADMM_FLAG_UNFUSED
+ * handle or of mode 0 -- ONE plain iteration is applied first (2 iters + 2, or 2, in all).  With `residuals` the last iteration
+ * applied leaves its norms for admm_get_residuals. */
 int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused_path, double ms[6]);
 
 /* Residual history of the last admm_solve (ADMM_FLAG_HISTORY; ABI v5): one entry per stopping test, oldest first.  *count =

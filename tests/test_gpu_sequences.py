@@ -1,0 +1,207 @@
+"""Random call sequences on solver handles against the host model (tests/_handle_model.py, tests/_op_sequences.py).
+
+One test per (kind, seed): the sequence runs on a Solver and on the model; at every read-out op of the sequence, and once at
+the end, whatever was read is compared.  Nothing is compared after the other ops: a read-out brings the handle's hidden state
+(v against (z, y), stale w, elimination direction, side data of the lean forms, a deferred finalise) into its normal form, and
+the point of the sequences is what the library does when nothing has.
+
+Tolerance: 1e-10 x max(1, |ref|_inf) on iterates and residual norms, that of every fp64 path of the suite (1e-5 on the mixed
+kind, the file header of test_gpu_mfma.py); the certificate as in test_gpu_cert.py; iteration counts, status, rho exactly.  The
+host tests keep every stopping-rule and adaptive-rule comparison of these sequences a relative 1e-6 away from its threshold, so
+rounding on the GPU cannot flip one.  A set_rho / update_problem refused with ADMM_ERR_NUMERIC (conditioning bound) and a
+fall-back to the plain kernels with a warning are legal outcomes; the iterates must match either way.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import admm_library_amd as pkg
+from admm_library_amd import _abi
+from admm_library_amd.solver import AdmmError
+
+import _op_sequences as ops
+from _handle_model import NUMERIC, Refused
+
+pytestmark = pytest.mark.gpu
+_LEAN = {}          # seed -> lean_iterations() of the lean kind's sequence
+
+
+def _tensor(a):
+    import torch
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def _apply_gpu(s, name, args, c):
+    """One op on the Solver; returns what a read-out op reads.  Raises AdmmError (ValueError from the wrapper's own checks)."""
+    lib = s._lib
+    if name == "iterate":
+        return s.iterate(args[0])
+    if name == "run":
+        return s.run(*args)
+    if name == "step_x":
+        return s.step_x()
+    if name == "step_z":
+        return s.step_z(args[0])
+    if name == "profile":
+        iters, res, mode = args
+        return s.profile(iters, residuals=res, fused=mode == 1, alternating=mode in (2, 3), back_to_back=mode == 3) and None
+    if name == "solve":
+        return dict(info=s.solve())
+    if name == "solve_pieces":
+        s.solve_begin()
+        steps = 0
+        while True:
+            it, nconv, R, S = s.solve_step(sums=True)
+            steps += 1
+            if nconv >= s.batch or it >= s.options.max_iter or (args[0] and steps >= args[0]):
+                break
+            s.solve_adapt(R, S)
+        return dict(info=s.solve_end())
+    if name == "set_rho":
+        return s.set_rho(c["rho"])
+    if name in ("set_state", "refuse_set_state_nan"):
+        return s.set_state(**c)
+    if name == "set_state_device":
+        return s.set_state(**{k: _tensor(a) for k, a in c.items()})
+    if name == "update_instances":
+        return s.update_instances(**c)
+    if name in ("update_problem", "refuse_update_N"):
+        return s.update_problem(c["problem"])
+    if name == "refuse_update_lohi":          # Problem.validate would stop it in the wrapper: hand the box to the library itself
+        good = c["problem"]
+        import dataclasses
+        cp, keep = _abi.marshal_problem(dataclasses.replace(good, lo=np.minimum(good.lo, good.hi)), s._row_major)
+        keep["lo"][...] = good.lo
+        rc = lib.admm_update_problem(s._h, C.byref(cp))
+        if rc:
+            raise AdmmError(rc, lib.admm_last_error().decode())
+        return None
+    if name == "set_fuel":
+        return s.set_fuel(c["fuel"])
+    if name == "refuse_set_fuel_neg":         # (likewise)
+        rc = lib.admm_set_fuel(s._h, _abi.dptr(np.ascontiguousarray(c["fuel"], np.float64)))
+        if rc:
+            raise AdmmError(rc, lib.admm_last_error().decode())
+        return None
+    if name == "certificate":
+        return dict(cert=s.certificate(costates=args[0]))
+    if name == "get":
+        got = s.get(*[bool(args[0] >> i & 1) for i in range(3)])
+        return {k: a for k, a in zip(("w", "z", "y"), got) if a is not None}
+    if name == "get_device":
+        import torch
+        got = s.get_device(*[bool(args[0] >> i & 1) for i in range(3)])
+        torch.cuda.synchronize()
+        return {k: a.cpu().numpy() for k, a in zip(("w", "z", "y"), got) if a is not None}
+    if name == "residuals":
+        return dict(resid=s.residuals())
+    if name == "rho_per_qp":
+        return dict(rho_per_qp=s.rho_per_qp())
+    raise KeyError(name)
+
+
+def _close(what, got, ref, tol):
+    err = np.abs(np.asarray(got) - np.asarray(ref)).max()
+    bound = tol * max(1.0, np.abs(ref).max())
+    print(f"    {what}: |gpu - model| = {err:.3e} (bound {bound:.1e})")
+    assert err <= bound, (what, err, bound)
+
+
+def _compare(got, ref, model, tol):
+    for k in ("w", "z", "y"):
+        if k in ref:
+            _close(k, got[k], ref[k], tol)
+    if "resid" in ref:
+        for k, g, r in zip(("r", "s", "nw", "nz", "ny"), got["resid"], ref["resid"]):
+            _close("residuals." + k, g, r, tol)
+    if "rho_per_qp" in ref:
+        assert np.array_equal(got["rho_per_qp"], ref["rho_per_qp"]), (got["rho_per_qp"], ref["rho_per_qp"])
+    if "info" in ref:
+        g, r = got["info"], ref["info"]
+        assert (g.iters_run, g.n_converged, g.rho, g.rho_updates) == (r["iters_run"], r["n_converged"], r["rho"], r["rho_updates"]), (g, r)
+        assert np.array_equal(g.iters, r["iters"]) and np.array_equal(g.status, r["status"]), (g.iters, r["iters"], g.status, r["status"])
+        _close("info.r", g.r, r["r"], tol)
+        _close("info.s", g.s, r["s"], tol)
+    if "cert" in ref:               # the scales of test_gpu_cert.py
+        g, r = got["cert"], ref["cert"]
+        b = model.p.batch
+        s_nu = np.maximum(1.0, np.abs(r["nu"]).reshape(b, -1).max(axis=1))
+        s_obj = np.maximum(1.0, r["obj_abs"])
+        s_z = np.maximum(1.0, np.abs(model.z).reshape(b, -1).max(axis=1))
+        ratios = {"stat": (np.abs(g.stat - r["stat"]) / (tol * s_nu)).max(), "obj": (np.abs(g.obj - r["obj"]) / (tol * s_obj)).max(),
+                  "feas_dyn": (np.abs(g.feas_dyn - r["feas_dyn"]) / (tol * s_z)).max()}
+        if g.nu is not None:
+            ratios["nu"] = (np.abs(g.nu - r["nu"]).reshape(b, -1).max(axis=1) / (tol * s_nu)).max()
+        print("    certificate, error / tolerance:", {k: float(f"{v:.3g}") for k, v in ratios.items()})
+        assert all(v <= 1.0 for v in ratios.values()), ratios
+
+
+def _run(kind, seed, monkeypatch, compare=True):
+    cfg = ops.KINDS[kind]
+    for var in ("ADMM_PI_LANE_PER_QP", "ADMM_PI_ROWS", "ADMM_PI_ROWS_FACTOR", "ADMM_NO_LEAN_RESID", "ADMM_NO_SKIPV_STORE"):
+        monkeypatch.delenv(var, raising=False)
+    for k, v in cfg.get("env", {}).items():
+        monkeypatch.setenv(k, v)
+    tol = cfg.get("tol", 1e-10)
+    seq = ops.sequence(kind, seed)
+    snap = ops.initial_snapshot(kind, seed)
+    final = [("get", (7,)), ("residuals", ()), ("rho_per_qp", ())]
+    last_ok = -1
+    with pkg.Solver(ops.problem(kind), ops.options(kind)) as s:
+        path = s.path()
+        print(kind, seed, path)
+        if "family" in cfg:
+            assert path["kernel_family"] == cfg["family"], path
+        assert path["per_instance"] == bool(cfg.get("pinst", False))
+        model = ops.new_model(kind, alternating=path["alternating"])
+        for i, (name, args) in enumerate(seq + final):
+            if name == "profile":
+                model.alternating = s.path()["alternating"]          # (a refactor may have left the alternating kernels)
+            c = ops.materialise(kind, name, args, model, snap)
+            got = exc = None
+            try:
+                got = _apply_gpu(s, name, args, c)
+            except (AdmmError, ValueError) as e:
+                exc = e
+            if isinstance(exc, AdmmError) and exc.code == NUMERIC and name in ("set_rho", "update_problem"):
+                print(f"  op {i} {name}{args}: refused by the conditioning bound, the model stays as it was")
+                continue
+            try:
+                ref = ops.apply_model(model, name, args, c)
+            except Refused as r:
+                ok = (isinstance(exc, AdmmError) and exc.code == r.code) or \
+                     (isinstance(exc, ValueError) and name == "refuse_update_N" and cfg.get("fuel"))
+                assert ok, f"op {i} {name}{args}: the model refuses it with code {r.code}, the library answered {exc!r}\n{seq[:i + 1]}"
+                continue
+            assert exc is None, f"op {i} {name}{args}: the library refused what the model accepts: {exc!r}\n{seq[:i + 1]}"
+            if name in ("get", "get_device"):
+                snap = tuple(a.copy() for a in model.get())
+            if ref is None or not compare:
+                continue
+            print(f"  op {i} {name}{args}")
+            try:
+                _compare(got, ref, model, tol)
+            except AssertionError as e:
+                raise AssertionError(f"{kind} seed {seed}: read-out {i} {name}{args} differs from the model: {e}\n"
+                                     f"first op after the last passing read-out: {last_ok + 1}\nops so far: {(seq + final)[:i + 1]}") from e
+            last_ok = i
+        return s.lean_iterations(), model
+
+
+@pytest.mark.parametrize("kind,seed", ops.CASES)
+def test_sequence_matches_the_host_model(gpu, kind, seed, monkeypatch):
+    lean, model = _run(kind, seed, monkeypatch)
+    print(f"{kind} seed {seed}: {model.iterations} iterations, lean {lean}")
+    if ops.KINDS[kind].get("lean"):
+        _LEAN[seed] = lean
+
+
+def test_the_lean_kind_runs_lean_iterations(gpu, monkeypatch):
+    """Coverage guard: over its seeds the lean kind's sequences launch iterations in the lean residual form."""
+    kind = next(k for k, c in ops.KINDS.items() if c.get("lean"))
+    for seed in ops.seeds(kind):
+        if seed not in _LEAN:                 # (this test run on its own)
+            _LEAN[seed] = _run(kind, seed, monkeypatch, compare=False)[0]
+    print("lean iterations per seed:", _LEAN)
+    assert sum(_LEAN.values()) > 0
