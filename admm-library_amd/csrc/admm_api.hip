@@ -77,6 +77,31 @@ int admm_host_scan_matrix(const admm_problem* p, double rho, int32_t segments, d
   return ADMM_OK;
 }
 
+int admm_host_scan_packed(const admm_problem* p, double rho, int32_t segments, int32_t backward, double* Wp, int32_t* range,
+                          int32_t* sizes) {
+  if (!p) return fail(ADMM_ERR_INVALID, "NULL problem");
+  admm::Factor f;
+  std::string err;
+  int rc = admm::factorise(*p, rho, segments, f, err);
+  if (rc) return fail(rc, err);
+  const bool ok = !backward || f.alt_ok;
+  if (sizes) {
+    sizes[0] = f.scanM;
+    sizes[1] = f.scanK;
+    sizes[2] = f.scanM / 16 / admm::SCAN_MT;
+    sizes[3] = ok ? 1 : 0;
+  }
+  if (!ok) {                       // (without `sizes` nothing would tell the caller that Wp / range were left alone)
+    if (!sizes) return fail(ADMM_ERR_NUMERIC, "admm_host_scan_packed: the forward-elimination form could not be built for this problem");
+    return ADMM_OK;
+  }
+  const std::vector<double>& wp = backward ? f.scanWpB : f.scanWp;
+  const std::vector<int32_t>& rg = backward ? f.scanRangeB : f.scanRange;
+  if (Wp) std::memcpy(Wp, wp.data(), sizeof(double) * wp.size());
+  if (range) std::memcpy(range, rg.data(), sizeof(int32_t) * rg.size());
+  return ADMM_OK;
+}
+
 int admm_host_scan_matrices_timeshard(const admm_problem* p, double rho, int32_t segments, int32_t nranks, double* W, double* WB,
                                       int32_t* ok) {
   if (!p || nranks < 1 || segments < 1 || segments % nranks != 0) return fail(ADMM_ERR_INVALID, "need segments >= 1, a multiple of nranks >= 1");
@@ -1175,6 +1200,15 @@ int admm_get_geometry(admm_handle* h, int32_t* pitch, int32_t* segs, int32_t* zr
   if (segs) *segs = h->S;
   if (zrows) *zrows = h->zrows;
   if (zchunks) *zchunks = h->zchunks;
+  return ADMM_OK;
+}
+
+int admm_get_scan_geometry(admm_handle* h, int32_t* split, int32_t* M, int32_t* K, int32_t* groups) {
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (split) *split = h->pinst ? 1 : h->scan_split;
+  if (M) *M = h->pinst ? 0 : h->fac.scanM;
+  if (K) *K = h->pinst ? 0 : h->fac.scanK;
+  if (groups) *groups = h->pinst ? 0 : h->fac.scanM / 16 / admm::SCAN_MT;
   return ADMM_OK;
 }
 

@@ -184,6 +184,8 @@ int setup_pinst(admm_handle* h, const admm_problem* p, bool dev) {
   h->auto_segments = o.segments == 0;
   {
     int S = o.segments;
+    // (the REQUEST is checked: a short horizon would otherwise cap 65 to N and accept it)
+    if (S > 64) return fail(ADMM_ERR_INVALID, "options.segments: at most 64 with per-instance dynamics");
     if (S == 0 && wide) {
       // a wave serves QPW QPs: enough (wave, segment) pairs for one wave per SIMD, segments of at least 8 stages
       const int qpw = p->n <= 2 ? 32 : (p->n <= 4 ? 16 : (p->n <= 8 ? 8 : 4));
@@ -205,7 +207,6 @@ int setup_pinst(admm_handle* h, const admm_problem* p, bool dev) {
     }
     if (S > h->N) S = h->N;
     if (S < 1) S = 1;
-    if (S > 64) return fail(ADMM_ERR_INVALID, "options.segments: at most 64 with per-instance dynamics");
     h->S = S;
     // few QPs: a lane per (QP, row) instead of a lane per QP (ADMM_PI_LANE_PER_QP=1 / ADMM_PI_ROWS=1 force either form)
     // (measured, N = 1000: 64 QPs 29 -> 23 us per sweep, N = 200: 15 -> 9 us; from 128 QPs the 8-QP waves' 64-byte accesses lose:

@@ -64,6 +64,7 @@ _SIGNATURES = {
     "admm_get_rho": (C.c_int, [C.c_void_p, c_double_p]),
     "admm_get_history": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, c_int32_p, c_int32_p, c_double_p, c_double_p, c_double_p]),
     "admm_get_path": (C.c_int, [C.c_void_p, C.POINTER(_abi.CPathInfo)]),
+    "admm_get_scan_geometry": (C.c_int, [C.c_void_p] + [c_int32_p] * 4),
     "admm_setup_timeshard": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_int32, C.c_int32,
                                       _abi.EXCHANGE_FN, C.c_void_p]),
     "admm_get_window": (C.c_int, [C.c_void_p] + [c_int32_p] * 5),
@@ -75,6 +76,7 @@ _SIGNATURES = {
     "admm_record_sizes": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p, c_int32_p]),
     "admm_host_scan_matrix": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_int32_p,
                                         c_int32_p, c_int32_p]),
+    "admm_host_scan_packed": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, C.c_int32, c_double_p, c_int32_p, c_int32_p]),
     "admm_host_factor": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_int32_p]),
     "admm_host_scan_matrices_timeshard": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, C.c_int32, c_double_p, c_double_p,
@@ -537,6 +539,13 @@ class Solver:
         _check(self._lib, self._lib.admm_get_window(self._h, *[C.byref(x) for x in v]))
         return {"stage_lo": v[0].value, "stage_hi": v[1].value, "seg_lo": v[2].value, "segs_local": v[3].value, "segs_total": v[4].value}
 
+    def scan_geometry(self) -> dict:
+        """admm_get_scan_geometry: split-K factor, padded shape and row groups of the segment scan as a dense product (split 1 and
+        zeros with per-instance dynamics)."""
+        v = [C.c_int32() for _ in range(4)]
+        _check(self._lib, self._lib.admm_get_scan_geometry(self._h, *[C.byref(x) for x in v]))
+        return {"split": v[0].value, "M": v[1].value, "K": v[2].value, "groups": v[3].value}
+
     def path(self) -> dict:
         """admm_get_path: which kernels this handle runs and the measured margin of the default path."""
         pi = _abi.CPathInfo()
@@ -597,6 +606,24 @@ def host_factor(problem: Problem, rho: float, segments: int):
         out.update(alt_ok=True, recFE=recFE, recBE=recBE, scanWB=WB)
     del keep
     return out
+
+
+def host_scan_packed(problem: Problem, rho: float, segments: int, backward: bool = False):
+    """Host-only: the segment-scan matrix in the fragment order xscan_mfma_kernel reads (flat, M * K doubles) and the k-step range
+    [begin, end) of every row group, as (Wp, range (groups, 2), M, K); backward: the pair of the forward-elimination form (None,
+    None, M, K when that form cannot be built)."""
+    lib = load_library()
+    cp, keep = _abi.marshal_problem(problem)
+    sizes = np.zeros(4, np.int32)
+    _check(lib, lib.admm_host_scan_packed(C.byref(cp), float(rho), int(segments), int(backward), None, None, iptr(sizes)))
+    M, K, groups, ok = (int(v) for v in sizes)
+    if not ok:
+        return None, None, M, K
+    Wp = np.empty(M * K)
+    rng = np.empty((groups, 2), np.int32)
+    _check(lib, lib.admm_host_scan_packed(C.byref(cp), float(rho), int(segments), int(backward), dptr(Wp), iptr(rng), None))
+    del keep
+    return Wp, rng, M, K
 
 
 def host_factor_mfma(problem: Problem, rho: float, segments: int, mode: int):

@@ -386,6 +386,14 @@ typedef struct admm_path_info {
 } admm_path_info;
 int admm_get_path(admm_handle* h, admm_path_info* info);
 
+/* Geometry of the segment scan as a dense product: the split-K factor the handle runs (1, 2, 4 or 8; chosen at
+ * admm_setup from the grid size, 1 on the matrix-vector form), the padded shape M x K of the scan matrix and the number of row
+ * groups of xscan_mfma_kernel (M / 64), each with its own k-step range.  Handles with per-instance dynamics scan per QP: they
+ * report split 1 and M = K = groups = 0.  Any output pointer may be NULL.  (New symbols of ABI v9 -- this one and
+ * admm_host_scan_packed --, announced by ADMM_HIP_HAS_SCAN_GEOMETRY: no struct or signature changed.) */
+#define ADMM_HIP_HAS_SCAN_GEOMETRY 1
+int admm_get_scan_geometry(admm_handle* h, int32_t* split, int32_t* M, int32_t* K, int32_t* groups);
+
 /* Thread-local diagnostic of the last admm_setup / admm_set_rho / admm_update_problem / admm_solve* call on this thread that
  * SUCCEEDED but changed the kernels a handle runs (the forward-elimination gate above; the adaptive rule refused a rho); ""
  * if there was nothing to report.  Cleared at the start of each of those calls. */
@@ -438,6 +446,15 @@ int admm_host_factor(const admm_problem* p, double rho, int32_t segments, double
  * Call with W = NULL to query M, Mt, K first. */
 int admm_host_scan_matrix(const admm_problem* p, double rho, int32_t segments, double* W, int32_t* M,
                           int32_t* Mt, int32_t* K);
+/* The same matrix as xscan_mfma_kernel reads it: Wp = W in MFMA fragment order (k-step-major, M / 16 tiles of 64 doubles per
+ * k-step, element `lane` of a tile = W[16 tile + (lane & 15)][4 kstep + (lane >> 4)]; M * K doubles) and range = the k-step range
+ * [begin, end) of each group of 4 tiles (2 * groups entries) outside which the group's rows of W are zero.  backward != 0: the
+ * pack and ranges of WB, the scan matrix of the forward-elimination form (admm_host_factor_alt).  sizes[4] = {M, K, groups, ok};
+ * ok = 0: backward was asked for and that form could not be built (Wp and range are then untouched;
+ * with sizes = NULL the call returns ADMM_ERR_NUMERIC instead, so that it cannot go unnoticed).  Call with Wp = range = NULL
+ * to query the sizes first.  Any output pointer may be NULL. */
+int admm_host_scan_packed(const admm_problem* p, double rho, int32_t segments, int32_t backward, double* Wp, int32_t* range,
+                          int32_t* sizes);
 
 /* The same two dense scan matrices (W, and WB if *ok) with their INPUT columns in the rank-by-rank layout of time-sharded handles
  * (admm_setup_timeshard): [rank 0: tseg of its segments | eseg of them][rank 1: ...] ... | x0 | pad.  Shapes as above. */

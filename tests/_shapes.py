@@ -52,3 +52,49 @@ ALT_TABLE = {      # (n, m): (seed, rho)
 }
 # pairs without a reasonable problem that passes the probe: they run the plain kernels, and the sweep asserts the warning
 PLAIN_ONLY = {}
+
+
+# The segment-scan geometry sweep (tests/test_scan_pack_host.py on the CPU, tests/test_gpu_scan_geometry.py on the GPU): the scan
+# GEMM's shape -- row groups, padded M and K, per-group k-step ranges, double-buffer rounds, split-K -- follows from S n, not from
+# (n, m).  Entries (n, m, N, S, seed, rho): pkg.random_ltv(N, n, m, batch, seed) at rho with S segments REQUESTED (the library caps
+# S at N).  Chosen as ALT_TABLE is: seed 2000 + 16 n + m, or the next + 100 that passes.  Each passes the forward-elimination
+# probe and keeps max|W|, max|WB| <= 100 (the conditioning bound admm_setup applies to automatic segment counts only: an explicit
+# count outside it would miss 1e-10 for reasons that are no kernel's fault); tests/test_shapes.py checks both on the CPU.
+#   widths   n in {1, 2, 5, 6, 7, 12}: S n no multiple of 16 at n = 5, 7; the 64-row padding of each half is mostly padding at n = 1, 2
+#   counts   S in {1, 2, 3, 11, 21, 43, 64}: one to 24 row groups, K up to 1568 (196 double-buffer rounds at most), ranges that
+#            differ from group to group;  N = S k + r with r != 0 (unequal segments) except S = 1, S = N and S > N
+SCAN_GEOMETRIES = [
+    (1, 1, 7, 1, 2017, 0.3), (1, 1, 70, 64, 2017, 0.3),
+    (2, 1, 11, 2, 2033, 0.3), (2, 1, 50, 43, 2033, 0.3),
+    (5, 2, 10, 3, 2082, 0.3), (5, 2, 25, 11, 2082, 0.3),
+    (5, 2, 21, 21, 2082, 0.3),                 # S = N: one stage per segment
+    (6, 3, 9, 2, 2099, 0.3), (6, 3, 10, 3, 2099, 0.3),
+    (6, 3, 50, 21, 2199, 0.3),                 # (seed 2099 fails the probe)
+    (6, 3, 90, 43, 2099, 0.3), (6, 3, 130, 64, 2099, 0.3),
+    (7, 3, 12, 11, 2115, 0.3),
+    (7, 3, 7, 11, 2115, 0.3),                  # S > N requested: capped to 7 one-stage segments
+    (7, 3, 87, 43, 2115, 0.3),
+    (12, 6, 7, 1, 2198, 0.3), (12, 6, 5, 2, 2198, 0.3), (12, 6, 25, 11, 2198, 0.3),
+    (12, 6, 45, 21, 2298, 0.3),                # (seed 2198 fails the probe)
+    (12, 6, 130, 64, 2198, 0.3),
+]
+# Split-K classes of the table, by the k-step ranges of W (in batches of SCAN_U k-steps; tests/test_shapes.py derives both lists
+# from the packed ranges): SLICEABLE -- the widest row group has >= 8 batches, so a split of 8 gives at least five slices work;
+# EMPTY_SLICE -- S <= 4 and the widest group has fewer batches than a split of 4 has slices, so a forced split leaves slices empty.
+SCAN_SLICEABLE = [g for g in SCAN_GEOMETRIES if g[:4] in ((6, 3, 50, 21), (6, 3, 90, 43), (6, 3, 130, 64), (7, 3, 87, 43),
+                                                          (12, 6, 25, 11), (12, 6, 45, 21), (12, 6, 130, 64))]
+SCAN_EMPTY_SLICE = [g for g in SCAN_GEOMETRIES if g[3] <= 4]
+# the refactor test: admm_set_rho to SCAN_REFACTOR_RHO, then admm_update_problem to SCAN_REFACTOR_SEED, on the first sliceable entry
+SCAN_REFACTOR_RHO, SCAN_REFACTOR_SEED = 0.5, 2299
+
+
+def gid(g) -> str:
+    return f"n{g[0]}m{g[1]}N{g[2]}S{g[3]}"
+
+
+def scan_shape(n: int, N: int, S: int):
+    """(segments in force, M, K, row groups) of the scan product, restated from DESIGN.md §4.6: both halves of the output padded to
+    64 rows (4 tiles of 16), the input to 32 rows (SCAN_U = 8 k-steps of 4)."""
+    S = min(S, N)
+    M = 2 * ((S * n + 63) // 64 * 64)
+    return S, M, ((2 * S + 1) * n + 31) // 32 * 32, M // 64

@@ -16,28 +16,10 @@ import admm_library_amd as pkg
 import oracle_c as oc
 from admm_library_amd import _abi
 from _shapes import ALT_TABLE, MFMA, PER_INSTANCE, PLAIN_ONLY, SHARED, SWEEP_N, SWEEP_SEGMENTS, WIDE, sid
+from _sweep import TOL, close as _close, schedule as _schedule
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("error:.*forward-elimination form failed:RuntimeWarning")]
-TOL = 1e-10
 UNSUPPORTED = {v: k for k, v in _abi.STATUS_NAMES.items()}["ADMM_ERR_UNSUPPORTED"]
-
-
-def _close(got, ref, tol=TOL):
-    return all(np.abs(a - ref[k]).max() <= tol * max(1.0, np.abs(ref[k]).max()) for a, k in zip(got, ("w", "z", "y")))
-
-
-def _schedule(s, z0, y0, first_residuals):
-    """39 iterations: the (z, y)-form first sweep from a caller's state, residual / non-residual kernels, calls of both
-    parities (a forward or a backward kernel before a residual one) -- RESID 0 / 1 and XFREE 0 / 1 / 2 on one handle."""
-    s.set_state(z=z0, y=y0)
-    s.run(1, residual_every=1 if first_residuals else 0)
-    s.run(8, residual_every=4)
-    s.iterate(5)
-    s.iterate(2)
-    s.run(6, residual_every=1)
-    s.run(10, residual_every=3)
-    s.run(7, residual_every=2)
-    return s.get()
 
 
 def test_an_uncompiled_pair_is_refused_with_the_compiled_list(gpu):
