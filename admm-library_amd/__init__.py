@@ -10,12 +10,12 @@ built library or without a GPU the solver raises.
 """
 from .problems import (Problem, DeviceProblem, double_integrator, cw_rendezvous, cw_rendezvous_fuel, cw_formation, cw_matrices,
                        random_ltv, random_instances, cw_rendezvous_instances, cw_formation_instances, mean_motion, SEED0)
-from .solver import (AdmmError, Certificate, Options, Solver, admm_setup, admm_solve,
+from .solver import (AdmmError, Certificate, Infeasibility, Options, Solver, admm_setup, admm_solve,
                      library_path, load_library, device_count, last_warning)
 from .sharding import (shard_bounds, shard_problem, gather_batch, global_residual_max, solve_sharded, TimeShardedSolver,
                        make_exchange, device_tensor)
 
 __all__ = ["DeviceProblem", "TimeShardedSolver", "make_exchange", "device_tensor", "last_warning", "Problem", "double_integrator", "cw_rendezvous", "cw_rendezvous_fuel", "cw_formation", "cw_matrices", "random_ltv", "random_instances", "cw_rendezvous_instances", "cw_formation_instances",
-           "mean_motion", "SEED0", "AdmmError", "Certificate", "Options", "Solver", "admm_setup",
+           "mean_motion", "SEED0", "AdmmError", "Certificate", "Infeasibility", "Options", "Solver", "admm_setup",
            "admm_solve", "library_path", "load_library", "device_count",
            "shard_bounds", "shard_problem", "gather_batch", "global_residual_max", "solve_sharded"]

@@ -3,6 +3,7 @@
 // every compute entry point returns ADMM_ERR_NO_DEVICE.
 #include "admm_runtime.hpp"
 #include "admm_cert.hpp"
+#include "admm_infeas.hpp"
 
 
 using namespace admm::rt;
@@ -1168,6 +1169,109 @@ int admm_get_certificate(admm_handle* h, double* obj, double* feas_dyn, double* 
 // once the operands are on the device).
 int admm_get_certificate_device(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, void* hip_stream) {
   return certificate_common(h, obj, feas_dyn, stat, nu, true, hip_stream);
+}
+
+// ---- infeasibility probe (kernels in admm_infeas_kernels.hpp) ----
+
+// The snapshot and work buffers on the first call; the box and thrust bound of every stage ([N][2 nb + 1]: lo | hi | unorm, from the
+// handle's host copy of the problem) on the first call and after admm_update_problem.  A_k | B_k and Phi_s are the certificate's.
+static int infeas_prepare(admm_handle* h, bool want_nu, bool want_flag) {
+  int rc;
+  const int nb = h->nb, N = h->N, S = h->S, rbd = 2 * nb + 1;
+  const size_t P = h->pitch;
+  if ((rc = cert_prepare(h, want_nu))) return rc;
+  if (!h->infeas_y0) {
+    if ((rc = dalloc(&h->infeas_y0, (size_t)h->L * P)) || (rc = dalloc(&h->infeas_bnd, (size_t)N * rbd)) ||
+        (rc = dalloc(&h->infeas_part, (size_t)S * 5 * P)) || (rc = dalloc(&h->infeas_out, 5 * P)))
+      return rc;
+    h->infeas_valid = false;
+  }
+  if (want_flag && !h->infeas_flag && (rc = dalloc(&h->infeas_flag, P))) return rc;
+  if (!h->infeas_valid) {
+    std::vector<double> bd((size_t)N * rbd);
+    for (int k = 0; k < N; ++k) {
+      const size_t o = h->stage_bounds ? (size_t)k * nb : 0;
+      std::copy(h->plo.begin() + o, h->plo.begin() + o + nb, bd.begin() + (size_t)k * rbd);
+      std::copy(h->phi.begin() + o, h->phi.begin() + o + nb, bd.begin() + (size_t)k * rbd + nb);
+      bd[(size_t)k * rbd + 2 * nb] = h->pun.empty() ? INFINITY : h->pun[h->stage_bounds ? k : 0];
+    }
+    HIP_TRY(hipMemcpyAsync(h->infeas_bnd, bd.data(), sizeof(double) * bd.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->infeas_valid = true;
+  }
+  return ADMM_OK;
+}
+
+static int infeasibility_common(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
+                                int32_t* infeasible, double* nu, bool dev, void* hip_stream) {
+  const char* fn = dev ? "admm_probe_infeasibility_device" : "admm_probe_infeasibility";
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (span < 1) return fail(ADMM_ERR_INVALID, std::string(fn) + ": span must be >= 1");
+  if (!std::isfinite(eps) || eps < 0.0) return fail(ADMM_ERR_INVALID, std::string(fn) + ": eps must be finite and >= 0");
+  if (h->pinst) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2)");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle");
+  if (h->opt.precision_mode == ADMM_PRECISION_MIXED)
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with precision_mode MIXED (the fp32 phase would put rounding "
+                "noise into the dual's difference)");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  const size_t bsz = sizeof(double) * (size_t)h->batch, nusz = bsz * (size_t)h->N * h->n;
+  if (dev && ((sep && (rc = check_device_ptr(h->device, sep, bsz, fn, "sep"))) ||
+              (drift && (rc = check_device_ptr(h->device, drift, bsz, fn, "drift"))) ||
+              (defect && (rc = check_device_ptr(h->device, defect, bsz, fn, "defect"))) ||
+              (infeasible && (rc = check_device_ptr(h->device, infeasible, sizeof(int32_t) * (size_t)h->batch, fn, "infeasible",
+                                                    sizeof(int32_t), "int32 entries"))) ||
+              (nu && (rc = check_device_ptr(h->device, nu, nusz, fn, "nu")))))
+    return rc;
+  admm::InfeasLaunch l{};
+  l.n = h->n; l.m = h->m;
+  if (!admm::launch_infeas(l, /*query_only=*/true))
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": no infeasibility kernel for this (n, m)");
+  if ((rc = infeas_prepare(h, nu != nullptr, infeasible != nullptr))) return rc;
+  // the state as the (z, y) pair, as admm_get reads it; y kept; span iterations as admm_run(h, span, 0) runs them; (z, y) again
+  if ((rc = ensure_zy(h))) return rc;
+  HIP_TRY(hipMemcpyAsync(h->infeas_y0, h->y, sizeof(double) * (size_t)h->L * h->pitch, hipMemcpyDeviceToDevice, h->stream));
+  if ((rc = admm_run(h, span, 0))) return rc;
+  if ((rc = ensure_zy(h))) return rc;
+  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
+  l.stream = h->stream;
+  l.N = h->N; l.S = h->S; l.pitch = h->pitch;
+  l.span = (double)span; l.eps = eps;
+  l.y = h->y; l.y0 = h->infeas_y0; l.x0 = h->x0;
+  l.AB = h->certAB; l.Phi = h->certPhi; l.bnd = h->infeas_bnd;
+  l.seg_start = h->seg_start;
+  l.cseg = h->cert_cseg; l.cin = h->cert_cin; l.part = h->infeas_part; l.out = h->infeas_out;
+  l.nu = nu ? h->cert_nu : nullptr;
+  admm::launch_infeas(l, false);
+  HIP_TRY(hipGetLastError());
+  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  double* dst[3] = {sep, drift, defect};
+  for (int v = 0; v < 3; ++v)
+    if (dst[v]) HIP_TRY(hipMemcpyAsync(dst[v], h->infeas_out + (size_t)v * h->pitch, bsz, kind, h->stream));
+  if (infeasible) {                                     // the flag as int32
+    admm::launch_infeas_flags(h->stream, h->infeas_out + (size_t)3 * h->pitch, h->infeas_flag, h->batch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(infeasible, h->infeas_flag, sizeof(int32_t) * (size_t)h->batch, kind, h->stream));
+  }
+  if (nu && (rc = download_transposed(h, h->cert_nu, nu, h->N * h->n, dev))) return rc;
+  if (!dev || !hip_stream) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
+  return ADMM_OK;
+}
+
+int admm_probe_infeasibility(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
+                             int32_t* infeasible, double* nu) {
+  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, false, nullptr);
+}
+
+// The device-memory form: the rules of admm_get_certificate_device.
+int admm_probe_infeasibility_device(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
+                                    int32_t* infeasible, double* nu, void* hip_stream) {
+  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, true, hip_stream);
 }
 
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s) {

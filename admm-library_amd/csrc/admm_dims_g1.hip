@@ -2,6 +2,7 @@
 #define ADMM_GROUP_FN launch_group1
 #define ADMM_GROUP_LIST dims_group1
 #define ADMM_CERT_FN launch_cert_group1
+#define ADMM_INFEAS_FN launch_infeas_group1
 #ifdef ADMM_DEV_DIMS      // development builds (tools/dev_variant.sh): one pair per group, seconds to compile
 #define ADMM_GROUP_DIMS(X) X(6, 3)
 #else

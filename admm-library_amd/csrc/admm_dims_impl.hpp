@@ -3,10 +3,12 @@
 //   ADMM_GROUP_LIST  dims_groupK
 //   ADMM_GROUP_DIMS(X)   X(n, m) X(n, m) ...
 //   ADMM_CERT_FN     launch_cert_groupK   (certificate kernels of the group's pairs, admm_cert_kernels.hpp)
+//   ADMM_INFEAS_FN   launch_infeas_groupK (infeasibility kernels of the group's pairs, admm_infeas_kernels.hpp)
 #include "admm_dispatch.hpp"
 #include "admm_kernels.hpp"
 #include "admm_kernels_alt.hpp"
 #include "admm_cert_kernels.hpp"
+#include "admm_infeas_kernels.hpp"
 
 namespace admm {
 
@@ -129,6 +131,17 @@ bool ADMM_CERT_FN(const CertLaunch& l, bool query_only) {
   if (l.n == NX && l.m == NU) {                  \
     if (!query_only) launch_cert_dim<NX, NU>(l); \
     return true;                                 \
+  }
+  ADMM_GROUP_DIMS(X)
+#undef X
+  return false;
+}
+
+bool ADMM_INFEAS_FN(const InfeasLaunch& l, bool query_only) {
+#define X(NX, NU)                                  \
+  if (l.n == NX && l.m == NU) {                    \
+    if (!query_only) launch_infeas_dim<NX, NU>(l); \
+    return true;                                   \
   }
   ADMM_GROUP_DIMS(X)
 #undef X

@@ -243,19 +243,19 @@ int validate_problem(const admm_problem* p, const DeviceScan* d) {
 
 // `ptr` must be device memory of `device` (not pageable or pinned host memory, not another GPU's), holding at least `bytes`
 // where the runtime reports the allocation's extent.  `fn` / `name` name the entry point and the argument in the message.
-int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name) {
+int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name, size_t elem, const char* unit) {
   hipPointerAttribute_t a{};
   const hipError_t e = hipPointerGetAttributes(&a, ptr);
   if (e != hipSuccess) (void)hipGetLastError();          // (pageable host memory: some ROCm versions fail the query itself)
   if (e != hipSuccess || a.type != hipMemoryTypeDevice || a.device != device)
     return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " is not device memory of the handle's GPU (device " + std::to_string(device) + ")");
-  if (reinterpret_cast<uintptr_t>(ptr) % sizeof(double))
-    return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " is not 8-byte aligned");
+  if (reinterpret_cast<uintptr_t>(ptr) % elem)
+    return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " is not " + std::to_string(elem) + "-byte aligned");
   hipDeviceptr_t base = nullptr;
   size_t size = 0;
   if (hipMemGetAddressRange(&base, &size, const_cast<void*>(ptr)) == hipSuccess) {
     if (static_cast<const char*>(ptr) + bytes > static_cast<const char*>(base) + size)
-      return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " ends before its " + std::to_string(bytes / sizeof(double)) + " doubles");
+      return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + name + " ends before its " + std::to_string(bytes / elem) + " " + unit);
   } else {
     (void)hipGetLastError();
   }
@@ -434,8 +434,9 @@ void release(admm_handle* h) {
   if (h->ext_ev) { (void)hipEventDestroy(h->ext_ev); h->ext_ev = nullptr; }
   if (h->chk_d) { (void)hipFree(h->chk_d); h->chk_d = nullptr; }
   for (double** b : {&h->certAB, &h->certQR, &h->certPhi, &h->cert_fuel, &h->cert_cseg, &h->cert_cin, &h->cert_part, &h->cert_out,
-                     &h->cert_nu})
+                     &h->cert_nu, &h->infeas_y0, &h->infeas_bnd, &h->infeas_part, &h->infeas_out})
     if (*b) { (void)hipFree(*b); *b = nullptr; }
+  if (h->infeas_flag) { (void)hipFree(h->infeas_flag); h->infeas_flag = nullptr; }
   if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
   delete h;
 }
@@ -537,6 +538,7 @@ void keep_shared(admm_handle* h, const admm_problem* p) {
   h->time_varying = p->time_varying;
   h->stage_bounds = p->stage_bounds;
   h->cert_valid = false;           // the certificate's device copy of A, B, Q, R, QN is of the old problem
+  h->infeas_valid = false;         // ... and the infeasibility probe's copy of the box and the thrust bounds
   // every STATE row unbounded at EVERY stage: its dual is identically zero, which lets the non-residual kernel forms
   // skip reading its v (XFREE, xfze_kernel)
   bool open = std::getenv("ADMM_NO_SKIPV") == nullptr;

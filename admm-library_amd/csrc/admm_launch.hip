@@ -1,6 +1,7 @@
 // admm_launch.hip -- solver runtime: kernel launches, the time-shard exchange, iteration forms and their schedule, graph capture (admm_runtime.hpp)
 #include "admm_runtime.hpp"
 #include "admm_cert.hpp"
+#include "admm_infeas.hpp"
 
 namespace admm {
 
@@ -8,6 +9,21 @@ namespace admm {
 bool launch_cert(const CertLaunch& l, bool query_only) {
   return launch_cert_group0(l, query_only) || launch_cert_group1(l, query_only) || launch_cert_group2(l, query_only) ||
          launch_cert_group3(l, query_only);
+}
+
+// infeasibility kernels (admm_infeas_kernels.hpp): instantiated beside the certificate's
+bool launch_infeas(const InfeasLaunch& l, bool query_only) {
+  return launch_infeas_group0(l, query_only) || launch_infeas_group1(l, query_only) || launch_infeas_group2(l, query_only) ||
+         launch_infeas_group3(l, query_only);
+}
+
+static __global__ __launch_bounds__(64) void infeas_flags_kernel(const double* __restrict__ flag_row, int* __restrict__ dst, int count) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b < count) dst[b] = flag_row[b] != 0.0 ? 1 : 0;
+}
+
+void launch_infeas_flags(hipStream_t stream, const double* flag_row, int* dst, int count) {
+  hipLaunchKernelGGL(infeas_flags_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, flag_row, dst, count);
 }
 
 namespace rt {

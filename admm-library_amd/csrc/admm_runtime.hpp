@@ -157,6 +157,11 @@ struct admm_handle {
   double *cert_cseg = nullptr, *cert_cin = nullptr, *cert_part = nullptr, *cert_out = nullptr, *cert_nu = nullptr;
   bool cert_valid = false;       // certAB / certQR / certPhi describe the handle's current problem
   std::vector<double> cert_fuel_h;   // the weights cert_fuel holds (compared with h->fuel at call time)
+  // infeasibility probe (admm_infeas_kernels.hpp): snapshot of y, the box and thrust bounds per stage, work buffers,
+  // allocated on the first admm_probe_infeasibility* call; the probe shares certAB, certPhi, cert_cseg, cert_cin and cert_nu
+  double *infeas_y0 = nullptr, *infeas_bnd = nullptr, *infeas_part = nullptr, *infeas_out = nullptr;
+  int* infeas_flag = nullptr;    // [pitch] the flag row of infeas_out as int32 (read-out)
+  bool infeas_valid = false;     // infeas_bnd describes the handle's current problem (keep_shared() invalidates it)
   int iters_run = 0;
   bool resid_valid = false;
   // A residual-evaluating alternating iteration leaves its finalise to the NEXT scan launch (finalise
@@ -294,7 +299,8 @@ struct DeviceProblem {
 };
 int validate_dims(const admm_problem* p);
 int validate_problem(const admm_problem* p, const DeviceScan* d = nullptr);
-int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name);
+int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name, size_t elem = sizeof(double),
+                     const char* unit = "doubles");   // elem, unit: the array's element (alignment, the count the message names)
 int scan_finite(hipStream_t s, const double* a, size_t count, unsigned long long* slot);
 int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, const char* fn, unsigned long long* scratch,
                            DeviceProblem& d);

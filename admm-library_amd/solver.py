@@ -95,6 +95,11 @@ _SIGNATURES = {
     # certificate: costates, objective, optimality measures (ADMM_HIP_HAS_CERTIFICATE)
     "admm_get_certificate": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "admm_get_certificate_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    # infeasibility probe: a Farkas certificate per QP (ADMM_HIP_HAS_INFEASIBILITY)
+    "admm_probe_infeasibility": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                          c_double_p]),
+    "admm_probe_infeasibility_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_int32_p,
+                                                 c_double_p, C.c_void_p]),
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),
@@ -210,6 +215,18 @@ class Certificate:
     obj: object
     feas_dyn: object
     stat: object
+    nu: object = None
+
+
+@dataclasses.dataclass
+class Infeasibility:
+    """Solver.infeasibility(): per-QP Farkas certificate from the drift of the scaled dual -- sep (negative
+    beyond eps: proven infeasible; +inf: no ray), drift, defect, the flags (int32), and the ray costates nu_1 .. nu_N as
+    (batch, N, n) if asked for.  NumPy arrays, or CUDA tensors on a solver built from a DeviceProblem."""
+    sep: object
+    drift: object
+    defect: object
+    infeasible: object
     nu: object = None
 
 
@@ -483,6 +500,30 @@ class Solver:
         nu = np.empty((self.batch, N, n)) if costates else None
         _check(self._lib, self._lib.admm_get_certificate(self._h, *[dptr(o) for o in outs], dptr(nu)))
         return Certificate(outs[0], outs[1], outs[2], nu)
+
+    def infeasibility(self, span: int = 10, eps: float = 1e-6, costates: bool = False) -> Infeasibility:
+        """admm_probe_infeasibility: runs `span` iterations (as run(span) does) and turns the drift of the scaled dual over them
+        into a Farkas certificate per QP, on the device: infeasible[b] = 1 proves -- up to rounding and `eps` -- that QP b has no
+        point meeting its dynamics, box and thrust bounds; a feasible QP is never flagged, converged or not.  costates=True adds
+        the ray costates, (batch, N, n).  A solver built from a DeviceProblem returns CUDA tensors through
+        admm_probe_infeasibility_device, ordered on torch's current stream."""
+        N, n = self.problem.N, self.problem.n
+        if isinstance(self.problem, DeviceProblem):
+            import torch
+            dev = f"cuda:{self._device()}"
+            outs = [torch.empty(self.batch, dtype=torch.float64, device=dev) for _ in range(3)]
+            flag = torch.empty(self.batch, dtype=torch.int32, device=dev)
+            nu = torch.empty((self.batch, N, n), dtype=torch.float64, device=dev) if costates else None
+            _check(self._lib, self._lib.admm_probe_infeasibility_device(
+                self._h, int(span), float(eps), *[_tptr(o) for o in outs], C.cast(C.c_void_p(flag.data_ptr()), c_int32_p),
+                _tptr(nu), _stream(dev)))
+            return Infeasibility(outs[0], outs[1], outs[2], flag, nu)
+        outs = [np.empty(self.batch) for _ in range(3)]
+        flag = np.empty(self.batch, np.int32)
+        nu = np.empty((self.batch, N, n)) if costates else None
+        _check(self._lib, self._lib.admm_probe_infeasibility(self._h, int(span), float(eps), *[dptr(o) for o in outs], iptr(flag),
+                                                            dptr(nu)))
+        return Infeasibility(outs[0], outs[1], outs[2], flag, nu)
 
     def get_device(self, w=True, z=True, y=True):
         """The state as (batch, L) fp64 tensors on the handle's GPU (None where not asked for), written by admm_get_device and

@@ -316,6 +316,32 @@ int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_s
 int admm_get_certificate(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu);
 int admm_get_certificate_device(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, void* hip_stream);
 
+/* Infeasibility probe (new symbols, announced by ADMM_HIP_HAS_INFEASIBILITY -- no struct or signature
+ * changed): a Farkas certificate of every QP from the drift of the scaled dual.  The call brings the state into the (z, y) pair as
+ * admm_get does, keeps y, runs `span` iterations as admm_run(h, span, 0) does and brings the state into (z, y) again; the state
+ * afterwards is, bit for bit, that of admm_get; admm_run(span, 0); admm_get, and per-QP iters and status are untouched.  With
+ * lambda = (y_after - y_before) / span in block order (u_k, x_{k+1}), on the device:
+ *   nu          nu_N = -lambda^x_N,  nu_k = A_k' nu_{k+1} - lambda^x_k  (k = N-1 .. 1): the ray costates
+ *   mu          -G'nu: the state rows are lambda's by construction, the control rows are REPLACED by B_k' nu_{k+1}
+ *   drift       |lambda|_inf (tends to 0 on a feasible QP)
+ *   defect      |mu - lambda|_inf / |mu|_inf (diagnostic: how far the drift is from a pure ray)
+ *   sep         (x0' A_0' nu_1 + sigma_C(mu)) / |mu|_inf, sigma_C the support function of the box (the ball ||u_k|| <= unorm_k on
+ *               the control rows of a stage with a finite thrust bound); +inf if mu = 0 or if a row whose needed bound is infinite
+ *               has |mu_i| > eps |mu|_inf.  A feasible QP has sep >= 0 in exact arithmetic whatever the iterates are.
+ *   infeasible  1 iff sep < -eps: a proof, up to rounding and the eps of the open rule, that no w meets the dynamics and the bounds
+ * Any output pointer may be NULL; sep, drift, defect, infeasible: batch entries; nu: N*n*batch, laid out as admm_get_certificate's.
+ * admm_probe_infeasibility_device: the outputs are device memory of the handle's GPU, under the rules of
+ * admm_get_certificate_device (infeasible: 4-byte aligned).
+ * ADMM_ERR_INVALID: span < 1, eps not finite or negative.  ADMM_ERR_UNSUPPORTED: per-instance dynamics (time_varying = 2),
+ * time-sharded handles, precision_mode MIXED, an (n, m) without a compiled kernel.  Everything is checked before anything is
+ * launched or allocated: a refused call leaves the handle as it was.  Fuel weights change the cost, not feasibility: they do not
+ * enter. */
+#define ADMM_HIP_HAS_INFEASIBILITY 1
+int admm_probe_infeasibility(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
+                             int32_t* infeasible, double* nu);
+int admm_probe_infeasibility_device(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
+                                    int32_t* infeasible, double* nu, void* hip_stream);
+
 /* Per-QP results of the last admm_solve: first checked iteration at which the
  * rule held (max_iter if never), status (1 converged / 0 not), last r and s. */
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s);

@@ -1,0 +1,104 @@
+"""Reference of the on-device infeasibility probe for the tests: the table of §2.10 as a plain sequential fp64
+recursion with a single segment, in NumPy, and a dense restatement of the Farkas inequality that shares nothing with it.
+
+With lambda = (y_after - y_before) / span in block order (u_k, x_{k+1}):
+  nu      nu_N = -lambda^x_N,  nu_k = A_k' nu_{k+1} - lambda^x_k  (k = N-1 .. 1); nu[:, k] holds nu_{k+1}, the multiplier of stage k's row
+  mu      state rows lambda^x, control rows B_k' nu_{k+1}  (= -G' nu)
+  drift   |lambda|_inf;   defect  |mu - lambda|_inf / |mu|_inf
+  sigma   the support function of C at mu: hi mu (mu > 0), lo mu (mu < 0) per box row -- a row whose needed bound is infinite adds
+          nothing and |mu| enters `open` --, unorm_k ||mu^u_k||_2 for the control rows of a stage with a finite thrust bound
+  sep     (x0' A_0' nu_1 + sigma) / |mu|_inf  if |mu|_inf > 0 and open <= eps |mu|_inf, else +inf;   infeasible = sep < -eps
+  sep_abs the sum of the absolute values of sep's terms over |mu|_inf (tolerance scale of a comparison in another summation order)
+"""
+import numpy as np
+
+from _indep import stage_bounds, stage_dynamics
+
+
+def stage_unorm(p):
+    if p.unorm is None:
+        return np.full(p.N, np.inf)
+    return np.broadcast_to(np.asarray(p.unorm, np.float64), (p.N,)).copy()
+
+
+def probe(p, y_before, y_after, span, eps):
+    """dict(sep, drift, defect, sep_abs, mu_max: (batch,); infeasible: (batch,) int32; nu: (batch, N, n))."""
+    Bt, N, n, m, nb = p.batch, p.N, p.n, p.m, p.nb
+    A, B = stage_dynamics(p)
+    lo, hi = stage_bounds(p)
+    un = stage_unorm(p)
+    lam = ((np.asarray(y_after, np.float64) - np.asarray(y_before, np.float64)) / float(span)).reshape(Bt, N, nb)
+    nu = np.zeros((Bt, N, n))
+    mu = lam.copy()
+    sig = np.zeros(Bt)
+    sig_abs = np.zeros(Bt)
+    opn = np.zeros(Bt)
+    c = np.zeros((Bt, n))
+
+    def box_row(v, l, h):
+        nonlocal sig, sig_abs, opn
+        b = np.where(v > 0.0, h, l)
+        fin = np.isfinite(b)
+        t = np.where(fin, b, 0.0) * v
+        sig = sig + t
+        sig_abs = sig_abs + np.abs(t)
+        opn = np.maximum(opn, np.where(fin, 0.0, np.abs(v)))
+
+    for k in range(N - 1, -1, -1):
+        nu[:, k] = c - lam[:, k, m:]
+        mu[:, k, :m] = nu[:, k] @ B[k]                # rows: B_k' nu_{k+1}
+        for i in range(n):
+            box_row(mu[:, k, m + i], lo[k, m + i], hi[k, m + i])
+        if np.isfinite(un[k]):
+            t = un[k] * np.sqrt(np.sum(mu[:, k, :m] ** 2, axis=1))
+            sig = sig + t
+            sig_abs = sig_abs + t
+        else:
+            for j in range(m):
+                box_row(mu[:, k, j], lo[k, j], hi[k, j])
+        c = nu[:, k] @ A[k]                           # rows: A_k' nu_{k+1}
+    terms = np.atleast_2d(p.x0) * c                   # h' nu = x0' (A_0' nu_1)
+    sig = sig + terms.sum(axis=1)
+    sig_abs = sig_abs + np.abs(terms).sum(axis=1)
+    mu_max = np.abs(mu).reshape(Bt, -1).max(axis=1)
+    d_max = np.abs(mu - lam).reshape(Bt, -1).max(axis=1)
+    drift = np.abs(lam).reshape(Bt, -1).max(axis=1)
+    ray = (mu_max > 0.0) & (opn <= eps * mu_max)
+    safe = np.where(mu_max > 0.0, mu_max, 1.0)
+    sep = np.where(ray, sig / safe, np.inf)
+    defect = np.where(mu_max > 0.0, d_max / safe, np.where(d_max > 0.0, np.inf, 0.0))
+    return dict(sep=sep, drift=drift, defect=defect, infeasible=(sep < -eps).astype(np.int32), nu=nu,
+                sep_abs=np.where(ray, sig_abs / safe, 0.0), mu_max=mu_max)
+
+
+def dense_farkas(p, b, nu, open_tol=0.0):
+    """h' nu + sigma_C(-G' nu) of QP b for the costates nu ((N, n): nu_1 .. nu_N), from the dense G, h of oracle/admm_ref.dense_qp,
+    row by row; normalised by |G' nu|_inf like sep.  +inf if a row that needs an infinite bound has |mu_i| > open_tol |mu|_inf.
+    Negative: no w has G w = h and w in C."""
+    import admm_ref
+    N, m, nb = p.N, p.m, p.nb
+    _, _, G, h = admm_ref.dense_qp(p.A, p.B, p.Q, p.R, p.QN, p.x0[b], N)
+    v = np.asarray(nu, np.float64).reshape(-1)
+    mu = -(G.T @ v)
+    lo, hi = stage_bounds(p)
+    lo, hi = lo.reshape(-1), hi.reshape(-1)
+    un = stage_unorm(p)
+    mu_max = np.abs(mu).max()
+    if not mu_max > 0.0:
+        return np.inf
+    total = float(h @ v)
+    for i in range(N * nb):
+        k, r = divmod(i, nb)
+        if r < m and np.isfinite(un[k]):
+            if r == 0:
+                total += un[k] * np.linalg.norm(mu[i:i + m])
+            continue
+        if mu[i] == 0.0:
+            continue
+        bound = hi[i] if mu[i] > 0.0 else lo[i]
+        if not np.isfinite(bound):
+            if abs(mu[i]) > open_tol * mu_max:
+                return np.inf
+            continue
+        total += bound * mu[i]
+    return total / mu_max
