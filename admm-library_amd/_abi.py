@@ -66,6 +66,25 @@ class CPathInfo(C.Structure):
                 ("alt_check", C.c_double), ("alt_gate", C.c_double), ("scan_growth", C.c_double)]
 
 
+class CScvxModel(C.Structure):          # admm_scvx_model
+    _fields_ = [("N", C.c_int32), ("batch", C.c_int32), ("substeps", C.c_int32), ("dt", C.c_double), ("rc", C.c_double)]
+
+
+class CScvxParams(C.Structure):         # admm_scvx_params (Q, R, QN row-major)
+    _fields_ = [("Q", C.c_double * 36), ("R", C.c_double * 9), ("QN", C.c_double * 36), ("u_lo", C.c_double * 3),
+                ("u_hi", C.c_double * 3), ("fd_eps", C.c_double), ("tol", C.c_double), ("rho_reject", C.c_double),
+                ("rho_expand", C.c_double)]
+
+
+class CScvxState(C.Structure):          # admm_scvx_state: device pointers
+    _fields_ = [(k, c_double_p) for k in ("ub", "xb", "u_cand", "x_cand", "J", "tr_u", "tr_x")] + \
+               [(k, c_int32_p) for k in ("active", "converged", "accepted", "outer", "take")] + \
+               [("history", c_double_p), ("history_capacity", C.c_int32)]
+
+
+SCVX_HISTORY_FIELDS = ("cost", "cost_candidate", "predicted", "actual", "ratio", "tr_u", "tr_x", "du_max", "accepted")
+
+
 EXCHANGE_ALLGATHER = 0
 # int (*admm_exchange_fn)(void* ctx, void* hip_stream, int32_t op, double* buf, int64_t count)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64)

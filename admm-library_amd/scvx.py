@@ -175,13 +175,16 @@ def correction_qp(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, 
                    name=f"scvx_correction_N{N}")
 
 
-def gpu_qp_solver(qp_data_on_device: bool = False, **options) -> Callable[[Problem], Tuple[np.ndarray, int]]:
+def gpu_qp_solver(qp_data_on_device: bool = False, z_on_device: bool = False, **options
+                  ) -> Callable[[Problem], Tuple[np.ndarray, int]]:
     """QP solver for scvx(): the HIP solver (raises without a device: no CPU fallback).  One handle
     serves every outer iteration: admm_update_problem refactors in place (same N, n, m, batch), each
     solve starts cold (z = y = 0), like a fresh handle.  A DeviceProblem (correction_qp_batch(..., qp_data_on_device=True))
-    goes in through the device-memory entry points; qp_data_on_device: z comes back through admm_get_device as well."""
+    goes in through the device-memory entry points; qp_data_on_device: z comes back through admm_get_device as well.
+    z_on_device (DeviceProblems only; scvx_batch(outer_on_device=True)): z is returned as the CUDA tensor admm_get_device wrote,
+    and the cold start is set from a zero tensor on the device (admm_set_state_device) -- nothing of size batch x L crosses PCIe."""
     from .solver import Options, Solver
-    state = {"solver": None, "shape": None}
+    state = {"solver": None, "shape": None, "zero": None}
 
     def solve(p: Problem):
         shape = (p.N, p.n, p.m, p.batch, p.q is not None, p.unorm is not None)
@@ -192,6 +195,13 @@ def gpu_qp_solver(qp_data_on_device: bool = False, **options) -> Callable[[Probl
         else:
             state["solver"].update_problem(p)
         s = state["solver"]
+        if z_on_device:
+            import torch
+            if state["zero"] is None or tuple(state["zero"].shape) != (p.batch, p.L):
+                state["zero"] = torch.zeros((p.batch, p.L), dtype=torch.float64, device=p.device)
+            s.set_state(z=state["zero"], y=state["zero"])
+            info = s.solve()
+            return s.get_device(w=False, y=False)[1], int(info.iters_run)
         zero = np.zeros((p.batch, p.L))
         info = s.solve(z0=zero, y0=zero)
         if qp_data_on_device:
@@ -302,25 +312,83 @@ def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: floa
     return DeviceProblem(N=N, A=A, B=B, Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(lo), hi=t(hi), q=t(p.q), name=p.name)
 
 
+def outer_update(J: np.ndarray, J_lin: np.ndarray, J_new: np.ndarray, du_max: np.ndarray, tru: np.ndarray, trx: np.ndarray,
+                 active: np.ndarray, converged: np.ndarray, accepted: np.ndarray, tol: float, rho_reject: float, rho_expand: float):
+    """The decision of one outer iteration of scvx_batch for every ACTIVE trajectory, from the reference cost J, the cost J_lin the
+    QP's model predicts for its solution, the cost J_new of the re-propagated candidate and du_max = |du|_inf (all (B,)): stop if
+    the model sees nothing left to gain; otherwise accept when actual / predicted >= rho_reject (radii doubled above rho_expand),
+    else halve the radii; stop after an accepted step below tol.  J, tru, trx, active, converged, accepted are UPDATED IN PLACE.
+    Returns (take, records): take (B,) bool -- the candidate replaces the reference --, records {b: history record of b} for the
+    trajectories that were active (the caller adds `iteration` and `admm_iterations`).  The host reference of the device kernel
+    scvx_advance_kernel."""
+    take = np.zeros(J.shape[0], bool)
+    records = {}
+    predicted, actual = J - J_lin, J - J_new
+    for b in np.flatnonzero(active):
+        ratio = actual[b] / predicted[b] if predicted[b] > 0 else -np.inf
+        step_norm = float(du_max[b])
+        rec = dict(cost=float(J[b]), cost_candidate=float(J_new[b]), predicted=float(predicted[b]),
+                   actual=float(actual[b]), ratio=float(ratio), tr_u=float(tru[b]), tr_x=float(trx[b]), du_max=step_norm,
+                   accepted=False)
+        records[int(b)] = rec
+        if predicted[b] <= tol * max(1.0, abs(J[b])):
+            converged[b], active[b] = True, False
+            continue
+        if ratio >= rho_reject:
+            take[b] = True
+            J[b] = J_new[b]
+            accepted[b] += 1
+            rec["accepted"] = True
+            if ratio >= rho_expand:
+                tru[b], trx[b] = 2.0 * tru[b], 2.0 * trx[b]
+        else:
+            tru[b], trx[b] = 0.5 * tru[b], 0.5 * trx[b]
+        if rec["accepted"] and step_norm <= tol:
+            converged[b], active[b] = True, False
+    return take, records
+
+
 def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
                qp_solver: Optional[Callable[[Problem], Tuple[np.ndarray, int]]] = None,
                tr_u: float = 0.1, tr_x: float = 20.0, max_outer: int = 20, tol: float = 1e-6,
                rho_reject: float = 0.1, rho_expand: float = 0.7, step=rk4_step,
                qp_options: Optional[dict] = None, linearise_on: Optional[str] = None,
-               qp_data_on_device: bool = False) -> List[ScvxResult]:
+               qp_data_on_device: bool = False, outer_on_device: bool = False) -> List[ScvxResult]:
     """scvx() for B initial conditions x0 (B, n) at once: the same trust-region loop per trajectory (own trust radii,
     own accept / reject decisions, own stop), but ONE batched QP solve per outer iteration -- per-instance dynamics,
     bounds and linear term (correction_qp_batch).  A trajectory that has stopped keeps its place in the batch with a
     zero-width box (its correction is then exactly zero) until the last one stops.
     linearise_on = "cuda:0": the central differences of the shipped model run as torch tensors on that device (linearise_device).
     qp_data_on_device (with linearise_on): the QP data go to the solver as a DeviceProblem -- A, B never leave the GPU -- and z
-    comes back through admm_get_device; the QPs, and so every decision, are those of the default path bit for bit."""
+    comes back through admm_get_device; the QPs, and so every decision, are those of the default path bit for bit.
+    outer_on_device (with linearise_on, the shipped rk4_step): everything between two QP solves -- rollout, linearisation, QP
+    assembly, costs, decisions -- runs in the HIP kernels of DeviceOuterStep on the tensors the solver reads and writes; the host
+    reads one integer per outer iteration.  Same scheme, same formulas; the roundings differ (device sqrt / fma), so the result
+    agrees with the host loop to the QP tolerance, not bit for bit."""
     x0 = np.atleast_2d(np.asarray(x0, np.float64))
     Bn = x0.shape[0]
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
     n, m = Q.shape[0], R.shape[0]
     u_lo = np.broadcast_to(np.asarray(u_lo, np.float64), (m,))
     u_hi = np.broadcast_to(np.asarray(u_hi, np.float64), (m,))
+    if outer_on_device:
+        if linearise_on is None or step is not rk4_step:
+            raise ValueError("outer_on_device needs linearise_on = 'cuda:k' and the shipped rk4_step")
+        if qp_solver is None:
+            qp_solver = gpu_qp_solver(True, z_on_device=True, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8,
+                                                                                    max_iter=20000, check_interval=25)))
+        loop = DeviceOuterStep(x0, N, dt, Q, R, QN, u_lo, u_hi, device=linearise_on, tol=tol, rho_reject=rho_reject,
+                               rho_expand=rho_expand, max_outer=max_outer)
+        loop.init(tr_u, tr_x)
+        admm_iters: List[int] = []
+        n_active = Bn
+        for _ in range(max_outer):
+            if n_active == 0:
+                break
+            z, iters = qp_solver(loop.prepare())
+            admm_iters.append(iters)
+            n_active = loop.advance(z)
+        return loop.results(admm_iters)
     if qp_solver is None:
         qp_solver = gpu_qp_solver(qp_data_on_device, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
                                                                            check_interval=25)))
@@ -345,27 +413,128 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         u_new = np.clip(ub + du, u_lo, u_hi)
         x_new = rollout(x0, u_new, dt, step)
         J_new = trajectory_cost(x_new, u_new, Q, R, QN)
-        predicted, actual = J - J_lin, J - J_new
-        for b in np.flatnonzero(active):
-            ratio = actual[b] / predicted[b] if predicted[b] > 0 else -np.inf
-            step_norm = float(np.abs(du[b]).max())
-            rec = dict(iteration=it, cost=float(J[b]), cost_candidate=float(J_new[b]), predicted=float(predicted[b]),
-                       actual=float(actual[b]), ratio=float(ratio), tr_u=float(tru[b]), tr_x=float(trx[b]), du_max=step_norm,
-                       admm_iterations=admm_iters, accepted=False)
-            if predicted[b] <= tol * max(1.0, abs(J[b])):
-                hist[b].append(rec)
-                converged[b], active[b] = True, False
-                continue
-            if ratio >= rho_reject:
-                ub[b], xb[b], J[b] = u_new[b], x_new[b], J_new[b]
-                accepted[b] += 1
-                rec["accepted"] = True
-                if ratio >= rho_expand:
-                    tru[b], trx[b] = 2.0 * tru[b], 2.0 * trx[b]
-            else:
-                tru[b], trx[b] = 0.5 * tru[b], 0.5 * trx[b]
-            hist[b].append(rec)
-            if rec["accepted"] and step_norm <= tol:
-                converged[b], active[b] = True, False
+        take, records = outer_update(J, J_lin, J_new, np.abs(du).max(axis=(1, 2)), tru, trx, active, converged, accepted,
+                                     tol, rho_reject, rho_expand)
+        ub[take], xb[take] = u_new[take], x_new[take]
+        for b, rec in records.items():
+            hist[b].append(dict(iteration=it, admm_iterations=admm_iters, **rec))
     return [ScvxResult(u=ub[b], x=xb[b], cost=float(J[b]), outer_iterations=len(hist[b]), accepted=int(accepted[b]),
                        converged=bool(converged[b]), history=hist[b]) for b in range(Bn)]
+
+
+class DeviceOuterStep:
+    """The state of scvx_batch(outer_on_device=True) as torch tensors on one GPU, and the four device entry points on it
+    (ADMM_HIP_HAS_SCVX): rollout / init / prepare / advance.  Shipped model only (relative_motion_rhs, rk4_step).
+    Every call is queued on torch's current stream; advance() alone waits -- for the count of trajectories still active."""
+
+    STATE_F64 = ("ub", "xb", "u_cand", "x_cand", "J", "tr_u", "tr_x")
+    STATE_I32 = ("active", "converged", "accepted", "outer", "take")
+
+    def __init__(self, x0, N: int, dt: float, Q, R, QN, u_lo, u_hi, device: str = "cuda:0", substeps: int = 4, rc: float = RC_KM,
+                 eps: float = 1e-6, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7, max_outer: int = 20):
+        import torch
+
+        from . import _abi
+        from .solver import load_library
+        self._lib = load_library()
+        self.device = torch.device(device)
+        x0 = np.atleast_2d(np.asarray(x0, np.float64))
+        Bn = x0.shape[0]
+        self.batch, self.N = Bn, int(N)
+        self.model = _abi.CScvxModel(N=int(N), batch=Bn, substeps=int(substeps), dt=float(dt), rc=float(rc))
+        self.params = _abi.CScvxParams(fd_eps=float(eps), tol=float(tol), rho_reject=float(rho_reject), rho_expand=float(rho_expand))
+        for name, a, shape in (("Q", Q, (6, 6)), ("R", R, (3, 3)), ("QN", QN, (6, 6)), ("u_lo", np.broadcast_to(u_lo, (3,)), (3,)),
+                               ("u_hi", np.broadcast_to(u_hi, (3,)), (3,))):
+            a = np.ascontiguousarray(a, np.float64)
+            if a.shape != shape:
+                raise ValueError(f"{name}: shape {a.shape}, expected {shape} (the shipped model has n = 6, m = 3)")
+            getattr(self.params, name)[:] = a.reshape(-1).tolist()
+
+        def f64(*shape):
+            return torch.zeros(shape, dtype=torch.float64, device=self.device)
+        self.x0 = torch.as_tensor(np.array(x0), device=self.device)
+        self.t = {"ub": f64(Bn, N, 3), "xb": f64(Bn, N, 6), "u_cand": f64(Bn, N, 3), "x_cand": f64(Bn, N, 6),
+                  "J": f64(Bn), "tr_u": f64(Bn), "tr_x": f64(Bn), "history": f64(max(int(max_outer), 1), Bn, 9)}
+        for k in self.STATE_I32:
+            self.t[k] = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        # the QP of one outer iteration, filled by prepare(): A, B row-major blocks, box and linear term; its x0 is zero (dx_0 = 0)
+        self.A, self.B = f64(Bn, N, 6, 6), f64(Bn, N, 6, 3)
+        self.lo, self.hi, self.q = f64(Bn, N, 9), f64(Bn, N, 9), f64(Bn, N * 9)
+        self.Qt, self.Rt, self.QNt = (torch.as_tensor(np.ascontiguousarray(a, np.float64), device=self.device) for a in (Q, R, QN))
+        self.dx0 = f64(Bn, 6)
+        self.state = self.c_state()
+
+    @staticmethod
+    def ptr(t):
+        """double* / int32_t* of a CUDA tensor."""
+        import ctypes as C
+
+        import torch
+
+        from ._abi import c_double_p, c_int32_p
+        return C.cast(C.c_void_p(t.data_ptr()), c_int32_p if t.dtype == torch.int32 else c_double_p)
+
+    def c_state(self, **override):
+        """admm_scvx_state over the tensors (override: other tensors by field name, or history_capacity)."""
+        from . import _abi
+        t = dict(self.t, **{k: v for k, v in override.items() if k != "history_capacity"})
+        return _abi.CScvxState(history_capacity=override.get("history_capacity", self.t["history"].shape[0]),
+                               **{k: self.ptr(t[k]) for k in self.STATE_F64 + self.STATE_I32 + ("history",)})
+
+    def _call(self, name, *args):
+        import ctypes as C
+
+        from .solver import _check, _stream
+        fn = getattr(self._lib, name)
+        _check(self._lib, fn(self.device.index or 0, C.byref(self.model), *args, _stream(self.device)))
+
+    def rollout(self, u):
+        """x_1 .. x_N (B, N, 6) of the nonlinear dynamics under the controls u (B, N, 3), a CUDA tensor."""
+        import torch
+        x = torch.empty((self.batch, self.N, 6), dtype=torch.float64, device=self.device)
+        self._call("admm_scvx_rollout_device", self.ptr(self.x0), self.ptr(u), self.ptr(x))
+        return x
+
+    def init(self, tr_u: float, tr_x: float):
+        import ctypes as C
+        self._call("admm_scvx_init_device", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), float(tr_u), float(tr_x))
+
+    def prepare(self):
+        """The correction QPs about the current reference as a DeviceProblem over this object's tensors (rewritten by each call)."""
+        import ctypes as C
+
+        from .problems import DeviceProblem
+        self._call("admm_scvx_prepare_device", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), self.ptr(self.A),
+                   self.ptr(self.B), self.ptr(self.lo), self.ptr(self.hi), self.ptr(self.q))
+        return DeviceProblem(N=self.N, A=self.A, B=self.B, Q=self.Qt, R=self.Rt, QN=self.QNt, x0=self.dx0, lo=self.lo, hi=self.hi,
+                             q=self.q, name=f"scvx_correction_batch{self.batch}_N{self.N}")
+
+    def advance(self, z) -> int:
+        """Candidate, costs and decisions from the QP solutions z (B, N * 9): a CUDA tensor (or a NumPy array, uploaded).  Returns the
+        number of trajectories still active."""
+        import ctypes as C
+
+        import torch
+        if not torch.is_tensor(z):
+            z = torch.as_tensor(np.ascontiguousarray(z, np.float64), device=self.device)
+        if tuple(z.shape) != (self.batch, self.N * 9) or z.dtype != torch.float64 or not z.is_contiguous() or z.device != self.x0.device:
+            raise ValueError(f"z: expected a contiguous fp64 ({self.batch}, {self.N * 9}) tensor on {self.x0.device}")
+        n_active = C.c_int32(-1)
+        self._call("admm_scvx_advance_device", C.byref(self.params), self.ptr(self.x0), self.ptr(z), C.byref(self.state),
+                   C.byref(n_active))
+        return int(n_active.value)
+
+    def results(self, admm_iterations) -> List[ScvxResult]:
+        """The loop's state as scvx_batch returns it (one copy of each tensor to the host)."""
+        from ._abi import SCVX_HISTORY_FIELDS
+        h = {k: v.cpu().numpy() for k, v in self.t.items()}
+        out = []
+        for b in range(self.batch):
+            hist = []
+            for it in range(int(h["outer"][b])):
+                rec = dict(zip(SCVX_HISTORY_FIELDS, (float(v) for v in h["history"][it, b])))
+                rec["accepted"] = bool(rec["accepted"])
+                hist.append(dict(iteration=it + 1, admm_iterations=int(admm_iterations[it]), **rec))
+            out.append(ScvxResult(u=h["ub"][b], x=h["xb"][b], cost=float(h["J"][b]), outer_iterations=len(hist),
+                                  accepted=int(h["accepted"][b]), converged=bool(h["converged"][b]), history=hist))
+        return out

@@ -100,6 +100,14 @@ _SIGNATURES = {
                                           c_double_p]),
     "admm_probe_infeasibility_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_int32_p,
                                                  c_double_p, C.c_void_p]),
+    # outer step of the batched SCvx loop on the device (ADMM_HIP_HAS_SCVX): device ordinal first, the caller's hipStream_t last
+    "admm_scvx_rollout_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_scvx_init_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), C.POINTER(_abi.CScvxParams), c_double_p,
+                                        C.POINTER(_abi.CScvxState), C.c_double, C.c_double, C.c_void_p]),
+    "admm_scvx_prepare_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), C.POINTER(_abi.CScvxParams), c_double_p,
+                                           C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
+    "admm_scvx_advance_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
+                                           C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),

@@ -342,6 +342,50 @@ int admm_probe_infeasibility(admm_handle* h, int32_t span, double eps, double* s
 int admm_probe_infeasibility_device(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
                                     int32_t* infeasible, double* nu, void* hip_stream);
 
+/* Outer step of the batched successive-convexification loop on the device (new symbols, announced by
+ * ADMM_HIP_HAS_SCVX -- no struct or signature changed): the device counterparts of scvx.rollout, scvx.linearise,
+ * scvx.correction_qp_batch and the decision block of scvx.scvx_batch for the shipped model (exact relative motion about a circular
+ * orbit, classical RK4 with `substeps` sub-intervals per stage; n = 6, m = 3).  The calls need no solver handle: they take a device
+ * ordinal and the caller's stream (a hipStream_t; NULL: the null stream), on which all their work is queued -- ordered after what
+ * the caller queued there, before what it queues next.  Every array is device memory of `device` in QP-major C order:
+ *   x0 (batch, 6);  u, ub, u_cand (batch, N, 3);  x, xb, x_cand (batch, N, 6): x_1 .. x_N
+ *   A (batch, N, 6, 6), B (batch, N, 6, 3): ROW-major blocks (what ADMM_FLAG_ROW_MAJOR takes)
+ *   lo, hi, q, z (batch, N, 9) in block order (u_k, x_{k+1});  J, tr_u, tr_x, active, converged, accepted, outer, take: (batch)
+ *   history (history_capacity, batch, 9): cost, cost_candidate, predicted, actual, ratio, tr_u, tr_x, du_max, accepted of the
+ *   outer iteration a trajectory was active in (record outer[b] of trajectory b)
+ * Q, R, QN of admm_scvx_params are row-major (symmetric in use).
+ *   admm_scvx_rollout_device  x = the nonlinear trajectory from x0 under u
+ *   admm_scvx_init_device     the loop's start: ub = 0, xb = rollout, J = its cost, radii (tr_u, tr_x), active = 1, the rest 0
+ *   admm_scvx_prepare_device  the correction QPs about (ub, xb): A, B by central differences (step fd_eps), q = (R ub_k, Q xb_k)
+ *                             (QN at the last stage), lo = max(u_lo - ub, -tr_u) | -tr_x, hi = min(u_hi - ub, tr_u) | tr_x; a
+ *                             trajectory that is not active gets radii 0 (a zero-width box)
+ *   admm_scvx_advance_device  from the QPs' solutions z: the candidate (u_cand = clip(ub + du), x_cand = its rollout), predicted and
+ *                             actual decrease, and per ACTIVE trajectory the decision of scvx.scvx_batch -- stop if predicted <=
+ *                             tol max(1, |J|); else accept if ratio >= rho_reject (radii doubled if ratio >= rho_expand), else radii
+ *                             halved; stop if accepted and |du|_inf <= tol --, one history record, and the accepted candidates
+ *                             copied into (ub, xb).  A trajectory that is not active on entry is left as it is (take = 0).
+ *                             *n_active (host): trajectories still active; the call returns once it is there -- the loop's one
+ *                             synchronisation per outer iteration.
+ * ADMM_ERR_INVALID, naming the argument, before anything is launched: N, batch or substeps < 1; dt, rc or fd_eps not finite or not
+ * positive; a NULL pointer; a pointer that is not device memory of `device`, or whose allocation ends before the array does; an
+ * active trajectory whose record would not fit in history_capacity. */
+#define ADMM_HIP_HAS_SCVX 1
+typedef struct { int32_t N, batch, substeps; double dt, rc; } admm_scvx_model;
+typedef struct { double Q[36], R[9], QN[36], u_lo[3], u_hi[3], fd_eps, tol, rho_reject, rho_expand; } admm_scvx_params;
+typedef struct {   /* device pointers */
+  double *ub, *xb, *u_cand, *x_cand, *J, *tr_u, *tr_x;
+  int32_t *active, *converged, *accepted, *outer, *take;
+  double* history;
+  int32_t history_capacity;
+} admm_scvx_state;
+int admm_scvx_rollout_device(int32_t device, const admm_scvx_model* model, const double* x0, const double* u, double* x, void* hip_stream);
+int admm_scvx_init_device(int32_t device, const admm_scvx_model* model, const admm_scvx_params* params, const double* x0,
+                          admm_scvx_state* state, double tr_u, double tr_x, void* hip_stream);
+int admm_scvx_prepare_device(int32_t device, const admm_scvx_model* model, const admm_scvx_params* params, const double* x0,
+                             const admm_scvx_state* state, double* A, double* B, double* lo, double* hi, double* q, void* hip_stream);
+int admm_scvx_advance_device(int32_t device, const admm_scvx_model* model, const admm_scvx_params* params, const double* x0,
+                             const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
+
 /* Per-QP results of the last admm_solve: first checked iteration at which the
  * rule held (max_iter if never), status (1 converged / 0 not), last r and s. */
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s);
