@@ -1,5 +1,7 @@
 """Reference of the on-device infeasibility probe for the tests: the table of §2.10 as a plain sequential fp64
-recursion with a single segment, in NumPy, and a dense restatement of the Farkas inequality that shares nothing with it.
+recursion with a single segment, in NumPy, and a dense restatement of the Farkas inequality that shares nothing with it.  With dtype=np.longdouble
+the table is evaluated in extended precision (every operand converted first): the measure of the rounding error of the fp64 form and
+of the kernels.
 
 With lambda = (y_after - y_before) / span in block order (u_k, x_{k+1}):
   nu      nu_N = -lambda^x_N,  nu_k = A_k' nu_{k+1} - lambda^x_k  (k = N-1 .. 1); nu[:, k] holds nu_{k+1}, the multiplier of stage k's row
@@ -21,28 +23,33 @@ def stage_unorm(p):
     return np.broadcast_to(np.asarray(p.unorm, np.float64), (p.N,)).copy()
 
 
-def probe(p, y_before, y_after, span, eps):
-    """dict(sep, drift, defect, sep_abs, mu_max: (batch,); infeasible: (batch,) int32; nu: (batch, N, n))."""
+def probe(p, y_before, y_after, span, eps, dtype=np.float64):
+    """dict(sep, drift, defect, sep_abs, mu_max: (batch,); infeasible: (batch,) int32; nu: (batch, N, n)), as arrays of `dtype`.
+
+    dtype=np.longdouble: the same table with every operand (the fp64 data of the problem, both y, span, eps) converted first and
+    every operation in extended precision -- what a faithful evaluation is measured against."""
     Bt, N, n, m, nb = p.batch, p.N, p.n, p.m, p.nb
-    A, B = stage_dynamics(p)
-    lo, hi = stage_bounds(p)
-    un = stage_unorm(p)
-    lam = ((np.asarray(y_after, np.float64) - np.asarray(y_before, np.float64)) / float(span)).reshape(Bt, N, nb)
-    nu = np.zeros((Bt, N, n))
+    A, B = (np.asarray(a, dtype) for a in stage_dynamics(p))
+    lo, hi = (np.asarray(a, dtype) for a in stage_bounds(p))
+    un = stage_unorm(p).astype(dtype)
+    eps = dtype(eps)
+    lam = ((np.asarray(y_after, dtype) - np.asarray(y_before, dtype)) / dtype(span)).reshape(Bt, N, nb)
+    nu = np.zeros((Bt, N, n), dtype)
     mu = lam.copy()
-    sig = np.zeros(Bt)
-    sig_abs = np.zeros(Bt)
-    opn = np.zeros(Bt)
-    c = np.zeros((Bt, n))
+    sig = np.zeros(Bt, dtype)
+    sig_abs = np.zeros(Bt, dtype)
+    opn = np.zeros(Bt, dtype)
+    c = np.zeros((Bt, n), dtype)
+    zero, one, inf = dtype(0.0), dtype(1.0), dtype(np.inf)
 
     def box_row(v, l, h):
         nonlocal sig, sig_abs, opn
-        b = np.where(v > 0.0, h, l)
+        b = np.where(v > zero, h, l)
         fin = np.isfinite(b)
-        t = np.where(fin, b, 0.0) * v
+        t = np.where(fin, b, zero) * v
         sig = sig + t
         sig_abs = sig_abs + np.abs(t)
-        opn = np.maximum(opn, np.where(fin, 0.0, np.abs(v)))
+        opn = np.maximum(opn, np.where(fin, zero, np.abs(v)))
 
     for k in range(N - 1, -1, -1):
         nu[:, k] = c - lam[:, k, m:]
@@ -57,18 +64,18 @@ def probe(p, y_before, y_after, span, eps):
             for j in range(m):
                 box_row(mu[:, k, j], lo[k, j], hi[k, j])
         c = nu[:, k] @ A[k]                           # rows: A_k' nu_{k+1}
-    terms = np.atleast_2d(p.x0) * c                   # h' nu = x0' (A_0' nu_1)
+    terms = np.atleast_2d(np.asarray(p.x0, dtype)) * c    # h' nu = x0' (A_0' nu_1)
     sig = sig + terms.sum(axis=1)
     sig_abs = sig_abs + np.abs(terms).sum(axis=1)
     mu_max = np.abs(mu).reshape(Bt, -1).max(axis=1)
     d_max = np.abs(mu - lam).reshape(Bt, -1).max(axis=1)
     drift = np.abs(lam).reshape(Bt, -1).max(axis=1)
-    ray = (mu_max > 0.0) & (opn <= eps * mu_max)
-    safe = np.where(mu_max > 0.0, mu_max, 1.0)
-    sep = np.where(ray, sig / safe, np.inf)
-    defect = np.where(mu_max > 0.0, d_max / safe, np.where(d_max > 0.0, np.inf, 0.0))
+    ray = (mu_max > zero) & (opn <= eps * mu_max)
+    safe = np.where(mu_max > zero, mu_max, one)
+    sep = np.where(ray, sig / safe, inf)
+    defect = np.where(mu_max > zero, d_max / safe, np.where(d_max > zero, inf, zero))
     return dict(sep=sep, drift=drift, defect=defect, infeasible=(sep < -eps).astype(np.int32), nu=nu,
-                sep_abs=np.where(ray, sig_abs / safe, 0.0), mu_max=mu_max)
+                sep_abs=np.where(ray, sig_abs / safe, zero), mu_max=mu_max)
 
 
 def dense_farkas(p, b, nu, open_tol=0.0):

@@ -98,3 +98,28 @@ def scan_shape(n: int, N: int, S: int):
     S = min(S, N)
     M = 2 * ((S * n + 63) // 64 * 64)
     return S, M, ((2 * S + 1) * n + 31) // 32 * 32, M // 64
+
+
+# The read-out kernels (certificate, infeasibility probe) stage CH stages of A_k | B_k -- and of the box -- in LDS at a time and
+# refill when a segment is longer.  Restated from csrc/admm_cert_kernels.hpp (cert_rec, cert_chunk), the source of truth:
+# tests/test_shapes.py reads the two constants out of the header and fails when they and this restatement part ways.
+CERT_LDS_DOUBLES, CERT_CHUNK_CAP = 4096, 64
+
+
+def cert_chunk(n: int, m: int) -> int:
+    return max(1, min(CERT_CHUNK_CAP, CERT_LDS_DOUBLES // (n * (n + m))))
+
+
+# Three problems per pair of SHARED at the edges of that loop (tests/_readout_cases.py builds them), as (N, segments, batch):
+#   refill  one segment of 2 CH + 1 stages: chunks CH, CH, 1 -- two refills, and stage 0 (which reads x0) alone in the last chunk
+#   fit     2 CH + 1 stages in two segments.  The split rule of csrc/admm_factor.cpp, seg_start[s] = floor(s N / S), gives
+#           seg_start = [0, CH, 2 CH + 1]: segment 0 (stages 0 .. CH - 1, with stage 0) has exactly CH stages, so its loop must end
+#           without a refill; segment 1 (stages CH .. 2 CH, with the terminal stage) has CH + 1.  Batch 261 gives pitch 320: a second
+#           256-thread block with one active wave and three idle ones that must still reach the barriers.
+#   stage   three one-stage segments: k = N - 1 (QN) and k = 0 (x0) in segments of their own; one partly filled wave in a block of four
+CHUNK_EDGE_CASES = ("refill", "fit", "stage")
+
+
+def chunk_edge(n: int, m: int, case: str):
+    ch = cert_chunk(n, m)
+    return {"refill": (2 * ch + 1, 1, 70), "fit": (2 * ch + 1, 2, 261), "stage": (3, 3, 3)}[case]

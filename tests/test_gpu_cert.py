@@ -2,9 +2,11 @@
 tests/_cert_ref.py (one segment, sequential) on the (z, y) the handle returns.
 
 Tolerance: the project's 1e-10, relative to max(1, max |nu|) of the QP for nu and stat, to max(1, sum |terms|)
-for obj and to max(1, max |z|) for feas_dyn: the two sides differ in summation order (and in the segment link) only."""
+for obj and to max(1, max |z|) for feas_dyn: the two sides differ in summation order (and in the segment link) only.
+
+The sweep over every compiled pair at the edges of the LDS refill loop (test 1b) compares with the same definitions in
+np.longdouble and adds a rounding-level bound on the same scales (M_CERT)."""
 import ctypes as C
-import dataclasses
 
 import numpy as np
 import pytest
@@ -14,6 +16,9 @@ import admm_library_amd as pkg
 import _cert_ref as cr
 import _fuel_ref as fr
 import _indep
+import _readout_cases as rc
+from _readout_cases import lti as _lti, stage_fuel as _stage_fuel
+from _shapes import CHUNK_EDGE_CASES, SHARED, sid
 from admm_library_amd import _abi
 
 pytestmark = pytest.mark.gpu
@@ -21,17 +26,6 @@ pytestmark = pytest.mark.gpu
 CODE = {v: k for k, v in _abi.STATUS_NAMES.items()}
 DEV = "cuda:0"
 TOL = 1e-10
-
-
-def _lti(p):
-    """The stage-1 dynamics, box and thrust bound of a random_ltv problem at every stage: time_varying = 0, stage_bounds = 0."""
-    return dataclasses.replace(p, A=p.A[1].copy(), B=p.B[1].copy(), lo=p.lo[1].copy(), hi=p.hi[1].copy(),
-                               unorm=None if p.unorm is None else np.float64(p.unorm[1]))
-
-
-def _stage_fuel(p):
-    """Per-stage weights on a thrust_norm random_ltv problem: positive where the control rows are unbounded."""
-    return dataclasses.replace(p, fuel=np.where(np.isfinite(p.unorm), 0.3, 0.0))
 
 
 # (id, problem factory, options)
@@ -42,6 +36,8 @@ CASES = [
     ("lti_4x2_b70_seg4_noq", lambda: _lti(pkg.random_ltv(13, 4, 2, 70, seed=44, with_q=False)), dict(rho=0.3, segments=4)),
     ("ltv_6x3_b70_seg4", lambda: pkg.random_ltv(50, 6, 3, 70, seed=45), dict(rho=0.3, segments=4)),
     ("ltv_6x3_b300_seg1_unfused", lambda: pkg.random_ltv(50, 6, 3, 300, seed=46), dict(rho=0.3, segments=1, flags=_abi.FLAG_UNFUSED)),
+    # a segment longer than the LDS chunk (75 stages against 64) on the default path: k = 1, 7, 8 cover both parkings of the state
+    ("ltv_6x3_N150_b70_seg2", lambda: pkg.random_ltv(150, 6, 3, 70, seed=55), dict(rho=0.3, segments=2)),
     ("ltv_6x3_b3_segN_noq", lambda: pkg.random_ltv(50, 6, 3, 3, seed=47, with_q=False), dict(rho=0.3, segments=50)),
     ("cw_6x3_b70_seg4", lambda: pkg.cw_rendezvous(N=50, batch=70), dict(rho=0.05, segments=4)),
     ("cw_6x3_b300_auto", lambda: pkg.cw_rendezvous(N=50, batch=300), dict(rho=0.05)),
@@ -95,6 +91,55 @@ def test_matches_reference_after_k_iterations(gpu, case, k):
         _, z, y = s.get()
     assert c.nu.shape == (p.batch, p.N, p.n)
     _compare(p, z, y, kw["rho"], c)
+
+
+# Rounding-level bound of the sweep below, per output: the device's worst error against the np.longdouble reference is at most M
+# times that of the fp64 NumPy reference (floored at 2^-52), both on the scales of _compare.  MEASURED_RATIO is the worst
+# e_dev / max(e_np, 2^-52) over the 87 cells on the MI355X; M is the next power of two at or above 4 x that (the 4 x for a
+# compiler that orders or contracts the chains differently: the arithmetic is deterministic, so there is no run-to-run spread).
+# Worst cells: nu (10, 4) refill, stat (5, 1) refill, obj (5, 1) fit, feas_dyn (12, 6) fit; the device's own worst errors are
+# 1.0e-15, 7.8e-16, 9.6e-16 and 4.8e-16 x scale.
+MEASURED_RATIO = {"nu": 1.87, "stat": 2.18, "obj": 4.33, "feas_dyn": 2.07}
+M_CERT = {"nu": 8.0, "stat": 16.0, "obj": 32.0, "feas_dyn": 16.0}
+LD = np.longdouble
+
+
+@pytest.mark.parametrize("edge", CHUNK_EDGE_CASES)
+@pytest.mark.parametrize("pair", SHARED, ids=sid)
+def test_certificate_at_every_pair_and_chunk_edge(gpu, pair, edge):
+    """1b. Every compiled (n, m) at the edges of the LDS refill loop (tests/_shapes.py: chunk_edge; CH = cert_chunk(n, m)):
+      refill  one segment of 2 CH + 1 stages -- chunks CH, CH, 1: two refills, stage 0 (x0) alone in the last; q, thrust bounds,
+              per-stage fuel weights
+      fit     segments [0, CH) and [CH, 2 CH + 1) (seg_start[s] = floor(s N / S); asserted on the CPU in
+              tests/test_readout_refs_host.py): segment 0, with stage 0, has exactly CH stages and must end without a refill,
+              segment 1, with the terminal stage, has CH + 1; batch 261 = pitch 320, a second block with one active wave and three
+              idle ones that must reach the barriers; LTI data and a shared box, expanded by the host; certificate() without
+              costates must return the same bits
+      stage   three one-stage segments: k = N - 1 (QN) and k = 0 (x0) each on its own
+    on the plain one-lane path with the segment count given, so neither the host probe nor the batch chooses the kernels.
+    All four outputs against the np.longdouble reference at the handle's (z, y): within 1e-10 x scale, and within M_CERT x the
+    error of the fp64 NumPy reference.  Measured on the MI355X, worst ratio e_dev / max(e_np, 2^-52) over the 87 cells: nu 1.87,
+    stat 2.18, obj 4.33, feas_dyn 2.07; hence M = 8, 16, 32, 16 (M_CERT above)."""
+    p, S = rc.problem(pair, edge, probe=False)
+    opt = pkg.Options(rho=rc.RHO, segments=S, flags=_abi.FLAG_NO_ALTERNATE | _abi.FLAG_NO_MFMA)
+    with pkg.Solver(p, opt) as s:
+        assert s.geometry()["segments"] == S and s.path()["kernel_family"] == "one_lane_fp64" and not s.path()["alternating"]
+        s.run(rc.CERT_ITERS)
+        c = s.certificate(costates=True)
+        lean = s.certificate() if edge == "fit" else None
+        _, z, y = s.get()
+    assert c.nu.shape == (p.batch, p.N, p.n)
+    if lean is not None:
+        assert lean.nu is None
+        for name in ("obj", "feas_dyn", "stat"):
+            assert np.array_equal(getattr(lean, name), getattr(c, name)), name
+    ld = cr.certificate(p, z, y, rc.RHO, dtype=LD)
+    e_dev = rc.cert_errors(p, z, c, ld)
+    e_np = rc.cert_errors(p, z, cr.certificate(p, z, y, rc.RHO), ld)
+    print("RATIOS cert", sid(pair), edge, {k: (float(f"{e_dev[k]:.3g}"), float(f"{e_np[k]:.3g}"),
+                                                 float(f"{e_dev[k] / max(e_np[k], rc.EPS64):.3g}")) for k in e_dev})
+    for name in e_dev:
+        rc.two_sided(name, e_dev[name], e_np[name], TOL, M_CERT[name])
 
 
 @pytest.mark.parametrize("case", ["ltv_4x2_b70_seg4", "ltv_6x3_b70_seg4", "ltv_12x6_b70_seg4"])

@@ -3,7 +3,10 @@ reference tests/_infeas_ref.py (one segment, sequential) on the handle's own two
 
 Tolerance: the project's 1e-10, relative to max(1, max |nu|) of the QP for nu, to max(1, sum |terms| / |mu|_inf) for
 sep, to max(1, drift) for drift and to max(1, defect, max |nu| / |mu|_inf) for defect (an absolute error of 1e-10 max |nu| in
-|mu - lambda|_inf, divided by |mu|_inf): the two sides differ in summation order (and in the segment link) only."""
+|mu - lambda|_inf, divided by |mu|_inf): the two sides differ in summation order (and in the segment link) only.
+
+The sweep over every compiled pair at the edges of the LDS refill loop (test 1b) compares with the same table in np.longdouble
+and adds a rounding-level bound on the same scales (M_PROBE)."""
 import ctypes as C
 import dataclasses
 
@@ -14,6 +17,8 @@ import torch
 import admm_library_amd as pkg
 import _infeas_cases as ic
 import _infeas_ref as ir
+import _readout_cases as rc
+from _shapes import CHUNK_EDGE_CASES, SHARED, sid
 from admm_library_amd import _abi
 
 pytestmark = pytest.mark.gpu
@@ -81,6 +86,68 @@ def test_matches_reference(gpu, shape, batch):
     ref = _compare(p, ys[1], ys[2], 5, 1e3, probes[1])
     moving = ref["mu_max"] > 0.0                                     # (not a comparison of zeros)
     assert np.array_equal(np.isfinite(ref["sep"]), moving) and moving.sum() >= (20 if batch >= 70 else 1)
+
+
+# Rounding-level bound of the sweep below, per output: the device's worst error against the np.longdouble reference is at most M
+# times that of the fp64 NumPy reference (floored at 2^-52), both on the scales of _compare.  MEASURED_RATIO is the worst
+# e_dev / max(e_np, 2^-52) over the 87 cells x 2 probes on the MI355X; M is the next power of two at or above 4 x that (the 4 x
+# for a compiler that orders or contracts the chains differently: the arithmetic is deterministic, so there is no run-to-run spread).
+# Worst cells: nu (1, 1) refill, sep (3, 1) fit, drift (12, 4) fit, defect (2, 1) fit; the device's own worst errors are 2.5e-16,
+# 4.7e-16, 8.9e-17 and 2.6e-16 x scale (drift is one subtraction and one division per row: the same bits on both sides).
+MEASURED_RATIO = {"nu": 1.00, "sep": 1.62, "drift": 0.40, "defect": 1.07}
+M_PROBE = {"nu": 4.0, "sep": 8.0, "drift": 2.0, "defect": 8.0}
+LD = np.longdouble
+
+
+@pytest.mark.parametrize("edge", CHUNK_EDGE_CASES)
+@pytest.mark.parametrize("pair", SHARED, ids=sid)
+def test_probe_at_every_pair_and_chunk_edge(gpu, pair, edge):
+    """1b. Every compiled (n, m) at the edges of the LDS refill loop (tests/_shapes.py: chunk_edge; CH = cert_chunk(n, m)):
+      refill  one segment of 2 CH + 1 stages -- chunks CH, CH, 1 of A_k | B_k and of the box: two refills, stage 0 (x0) alone in
+              the last; thrust bounds on most stages
+      fit     segments [0, CH) and [CH, 2 CH + 1) (seg_start[s] = floor(s N / S); asserted on the CPU in
+              tests/test_readout_refs_host.py): segment 0, with stage 0 and the x0 term, has exactly CH stages and must end
+              without a refill, segment 1 has CH + 1; batch 261 = pitch 320, a second block with one active wave and three idle
+              ones that must reach the barriers; LTI data and one shared box, expanded by the host
+      stage   three one-stage segments: k = N - 1 and k = 0 each on its own
+    on the plain one-lane path with the segment count given.  The twin-handle pattern of test_matches_reference: run(20), then
+    probes of span 5 with eps = 1e-6 and eps = 1e3; the state box shrunk to 0.3 of itself.  All five outputs against the
+    np.longdouble reference on the twin's y: +inf as +inf, flags equal (none sits within the tolerance of -eps: a condition
+    tests/test_readout_refs_host.py keeps on the oracle's iterates, and the rule of _compare still applies), the four real outputs
+    within 1e-10 x scale and within M_PROBE x the error of the fp64 NumPy reference.  Measured on the MI355X, worst ratio
+    e_dev / max(e_np, 2^-52) over the 87 cells and both probes: nu 1.00, sep 1.62, drift 0.40, defect 1.07; hence M = 4, 8, 2, 8
+    (M_PROBE above)."""
+    p, S = rc.problem(pair, edge, probe=True)
+    opt = pkg.Options(rho=rc.RHO, segments=S, flags=_abi.FLAG_NO_ALTERNATE | _abi.FLAG_NO_MFMA)
+    with pkg.Solver(p, opt) as s, pkg.Solver(p, opt) as twin:
+        assert s.geometry()["segments"] == S and s.path()["kernel_family"] == "one_lane_fp64" and not s.path()["alternating"]
+        s.run(rc.PROBE_ITERS)
+        twin.run(rc.PROBE_ITERS)
+        ys = [twin.get()[2]]
+        probes = []
+        for eps in rc.PROBE_EPS:
+            probes.append(s.infeasibility(span=rc.PROBE_SPAN, eps=eps, costates=True))
+            twin.run(rc.PROBE_SPAN)
+            ys.append(twin.get()[2])
+        for a, b in zip(s.get(), twin.get()):
+            assert np.array_equal(a, b)
+    assert probes[0].nu.shape == (p.batch, p.N, p.n)
+    for i, (eps, r) in enumerate(zip(rc.PROBE_EPS, probes)):
+        ld = ir.probe(p, ys[i], ys[i + 1], rc.PROBE_SPAN, eps, dtype=LD)
+        f64 = ir.probe(p, ys[i], ys[i + 1], rc.PROBE_SPAN, eps)
+        assert np.array_equal(np.isinf(r.sep), np.isinf(ld["sep"])) and np.all(r.sep[np.isinf(r.sep)] > 0)
+        assert np.array_equal(np.isinf(r.defect), np.isinf(ld["defect"]))
+        fs = np.isfinite(ld["sep"])
+        near = fs & (np.abs(np.where(fs, ld["sep"], 0.0) + LD(eps)) <= TOL * np.maximum(1.0, ld["sep_abs"]))
+        assert r.infeasible.dtype == np.int32 and np.array_equal(r.infeasible[~near], ld["infeasible"][~near])
+        e_dev = rc.probe_errors(p, r, ld)
+        e_np = rc.probe_errors(p, f64, ld)
+        print("RATIOS probe", sid(pair), edge, eps, {k: (float(f"{e_dev[k]:.3g}"), float(f"{e_np[k]:.3g}"),
+                                                          float(f"{e_dev[k] / max(e_np[k], rc.EPS64):.3g}")) for k in e_dev},
+              "mu_max > 0:", int((ld["mu_max"] > 0).sum()), "finite sep:", int(fs.sum()), "flags:", int(ld["infeasible"].sum()))
+        for name in e_dev:
+            rc.two_sided(name, e_dev[name], e_np[name], TOL, M_PROBE[name])
+        assert (ld["mu_max"] > 0).any()                              # (not a comparison of zeros)
 
 
 @pytest.fixture(scope="module")

@@ -1,13 +1,16 @@
 """The compiled shape lists (tests/_shapes.py) and the shape sweep's problem table, on the CPU: a pair added to or dropped from
 the build changes a pinned list here until the sweeps are looked at, and a change of the forward-elimination probe that would
 send a sweep cell to the plain kernels fails here before the GPU suite runs."""
+import os
+import re
+
 import numpy as np
 import pytest
 
 import admm_library_amd as pkg
 from admm_library_amd.solver import host_factor, host_scan_packed
-from _shapes import (ALT_TABLE, MFMA, PER_INSTANCE, PLAIN_ONLY, SCAN_EMPTY_SLICE, SCAN_GEOMETRIES, SCAN_REFACTOR_RHO,
-                     SCAN_REFACTOR_SEED, SCAN_SLICEABLE, SHARED, SWEEP_N, SWEEP_SEGMENTS, WIDE, gid, scan_shape)
+from _shapes import (ALT_TABLE, CERT_CHUNK_CAP, CERT_LDS_DOUBLES, CHUNK_EDGE_CASES, CSRC, MFMA, PER_INSTANCE, PLAIN_ONLY, SCAN_EMPTY_SLICE, SCAN_GEOMETRIES, SCAN_REFACTOR_RHO,
+                     SCAN_REFACTOR_SEED, SCAN_SLICEABLE, SHARED, SWEEP_N, SWEEP_SEGMENTS, WIDE, cert_chunk, chunk_edge, gid, scan_shape)
 
 
 def test_compiled_shape_lists_are_pinned():
@@ -88,3 +91,31 @@ def test_scan_refactor_problems_pass_the_probe_and_the_growth_bound(lib):
     for sd in (seed, SCAN_REFACTOR_SEED):
         hf = host_factor(pkg.random_ltv(N=N, n=n, m=m, batch=67, seed=sd), SCAN_REFACTOR_RHO, S)
         assert hf["alt_ok"] and max(np.abs(hf["scanW"]).max(), np.abs(hf["scanWB"]).max()) <= SCAN_GROWTH_MAX, sd
+
+
+def test_cert_chunk_restates_the_header():
+    """cert_rec and cert_chunk of csrc/admm_cert_kernels.hpp, read from the source: stages of n (n + m) doubles, 4096 doubles of
+    LDS, at most 64 stages, at least 1.  A change of either constant (or of the formula's shape) fails here until
+    tests/_shapes.py follows, and with it the chunk-edge sweeps of the read-out kernels."""
+    src = open(os.path.join(CSRC, "admm_cert_kernels.hpp")).read()
+    assert re.search(r"constexpr int cert_rec\(int nx, int nu\) \{ return nx \* \(nx \+ nu\); \}", src)
+    body = re.search(r"constexpr int cert_chunk\(int nx, int nu\) \{(.*?)\n\}", src, re.S).group(1)
+    lds = re.search(r"int ch = (\d+) / cert_rec\(nx, nu\);", body)
+    cap = re.search(r"return ch > (\d+) \? (\d+) : \(ch < 1 \? 1 : ch\);", body)
+    assert lds and cap and cap.group(1) == cap.group(2)
+    assert (int(lds.group(1)), int(cap.group(1))) == (CERT_LDS_DOUBLES, CERT_CHUNK_CAP) == (4096, 64)
+    # the infeasibility kernels take the same chunk
+    assert "CH = cert_chunk(NX, NU)" in open(os.path.join(CSRC, "admm_infeas_kernels.hpp")).read()
+    assert [cert_chunk(n, m) for n, m in ((1, 1), (6, 3), (6, 4), (8, 4), (12, 6))] == [64, 64, 64, 42, 18]
+    assert {cert_chunk(n, m) for n, m in SHARED} >= {64, 18} and min(cert_chunk(n, m) for n, m in SHARED) == 18
+
+
+def test_chunk_edge_table_puts_every_pair_on_the_edges():
+    """refill: chunks CH, CH, 1; fit: floor(s N / S) splits 2 CH + 1 stages into CH and CH + 1, pitch 320; stage: one stage each."""
+    assert CHUNK_EDGE_CASES == ("refill", "fit", "stage")
+    for n, m in SHARED:
+        ch = cert_chunk(n, m)
+        assert chunk_edge(n, m, "refill") == (2 * ch + 1, 1, 70) and chunk_edge(n, m, "stage") == (3, 3, 3)
+        N, S, batch = chunk_edge(n, m, "fit")
+        assert [s * N // S for s in range(S + 1)] == [0, ch, 2 * ch + 1] and (batch + 63) // 64 * 64 == 320
+        assert N <= 129
