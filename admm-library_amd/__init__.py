@@ -14,8 +14,10 @@ from .solver import (AdmmError, Certificate, Infeasibility, Options, Solver, adm
                      library_path, load_library, device_count, last_warning)
 from .sharding import (shard_bounds, shard_problem, gather_batch, global_residual_max, solve_sharded, TimeShardedSolver,
                        make_exchange, device_tensor)
+from .mpc import MpcResult, mpc_batch, shift_horizon
 
-__all__ = ["DeviceProblem", "TimeShardedSolver", "make_exchange", "device_tensor", "last_warning", "Problem", "double_integrator", "cw_rendezvous", "cw_rendezvous_fuel", "cw_formation", "cw_matrices", "random_ltv", "random_instances", "cw_rendezvous_instances", "cw_formation_instances",
+__all__ = ["MpcResult", "mpc_batch", "shift_horizon",
+"DeviceProblem", "TimeShardedSolver", "make_exchange", "device_tensor", "last_warning", "Problem", "double_integrator", "cw_rendezvous", "cw_rendezvous_fuel", "cw_formation", "cw_matrices", "random_ltv", "random_instances", "cw_rendezvous_instances", "cw_formation_instances",
            "mean_motion", "SEED0", "AdmmError", "Certificate", "Infeasibility", "Options", "Solver", "admm_setup",
            "admm_solve", "library_path", "load_library", "device_count",
            "shard_bounds", "shard_problem", "gather_batch", "global_residual_max", "solve_sharded"]

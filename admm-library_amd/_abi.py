@@ -82,7 +82,16 @@ class CScvxState(C.Structure):          # admm_scvx_state: device pointers
                [("history", c_double_p), ("history_capacity", C.c_int32)]
 
 
-SCVX_HISTORY_FIELDS = ("cost", "cost_candidate", "predicted", "actual", "ratio", "tr_u", "tr_x", "du_max", "accepted")
+class CMpcStep(C.Structure):            # admm_mpc_step (Ap, Bp: host arrays; the rest host or device memory by the entry point)
+    _fields_ = [(k, c_double_p) for k in ("Ap", "Bp", "du", "dx", "x_meas", "q_tail")] + \
+               [("tail", C.c_int32), ("reserved", C.c_int32)]
+
+
+MPC_TAIL_COPY = 0
+MPC_TAIL_ZERO = 1
+MPC_TAILS = {"copy": MPC_TAIL_COPY, "zero": MPC_TAIL_ZERO}
+
+SCVX_HISTORY_FIELDS =("cost", "cost_candidate", "predicted", "actual", "ratio", "tr_u", "tr_x", "du_max", "accepted")
 
 
 EXCHANGE_ALLGATHER = 0

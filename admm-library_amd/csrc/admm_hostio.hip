@@ -434,7 +434,7 @@ void release(admm_handle* h) {
   if (h->ext_ev) { (void)hipEventDestroy(h->ext_ev); h->ext_ev = nullptr; }
   if (h->chk_d) { (void)hipFree(h->chk_d); h->chk_d = nullptr; }
   for (double** b : {&h->certAB, &h->certQR, &h->certPhi, &h->cert_fuel, &h->cert_cseg, &h->cert_cin, &h->cert_part, &h->cert_out,
-                     &h->cert_nu, &h->infeas_y0, &h->infeas_bnd, &h->infeas_part, &h->infeas_out})
+                     &h->cert_nu, &h->infeas_y0, &h->infeas_bnd, &h->infeas_part, &h->infeas_out, &h->mpc_edge, &h->mpc_xn, &h->mpc_io})
     if (*b) { (void)hipFree(*b); *b = nullptr; }
   if (h->infeas_flag) { (void)hipFree(h->infeas_flag); h->infeas_flag = nullptr; }
   if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }

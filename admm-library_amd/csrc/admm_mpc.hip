@@ -1,0 +1,165 @@
+// admm_mpc.hip -- host side of the receding-horizon step (ADMM_HIP_HAS_MPC; kernels: admm_mpc_kernels.hpp):
+// admm_mpc_advance / admm_mpc_advance_device.  Every check -- arguments first, without a HIP call; then the pointers; then the
+// data -- comes before the first launch that changes the handle.
+#include "admm_runtime.hpp"
+#include "admm_mpc_kernels.hpp"
+
+using namespace admm::rt;
+
+namespace {
+
+// The chunk count aims the shift's grid at 3/4 of the compute units (one 256-lane block each): at 4096 x 1000, (6, 3), that is 8
+// chunks, the fastest of the counts 2 .. 128 measured on the MI355X (DESIGN.md §2.11 has the table; 4 blocks per CU, the first
+// guess, was 10 % slower).  A chunk holds at least MPC_MIN_BLOCKS_PER_CHUNK blocks: a horizon of a few blocks is one chunk, with
+// no scratch and no edge copies.
+constexpr int MPC_GRID_CU_NUM = 3, MPC_GRID_CU_DEN = 4;
+constexpr int MPC_MIN_BLOCKS_PER_CHUNK = 4;
+
+int column_blocks(const admm_handle* h) { return (h->pitch / 2 + admm::MPC_THREADS - 1) / admm::MPC_THREADS; }
+
+// ADMM_MPC_CHUNKS (tests and tools/mpc_time.py only) overrides the count; it is read per call and clamped to [1, N].
+int chunk_count(const admm_handle* h, int arrays) {
+  if (const char* e = std::getenv("ADMM_MPC_CHUNKS")) {
+    const int v = std::atoi(e);
+    if (v >= 1) return std::min(v, h->N);
+  }
+  const int per_chunk = column_blocks(h) * arrays;
+  const int want = (h->num_cus * MPC_GRID_CU_NUM / MPC_GRID_CU_DEN + per_chunk - 1) / per_chunk;
+  return std::max(1, std::min(want, h->N / MPC_MIN_BLOCKS_PER_CHUNK));
+}
+
+struct DevArgs { const double *du, *dx, *x_meas, *q_tail; double *u, *x; };
+
+int bad(const char* fn, const std::string& what) { return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + what); }
+
+// what can be checked without a HIP call and without reading a per-QP array
+int check_step(const char* fn, const admm_handle* h, const admm_mpc_step* s) {
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (!s) return bad(fn, "step is NULL");
+  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle (a rank holds a stage window only)");
+  if (h->pinst || h->time_varying == 2)
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2): the per-QP operands and factors would have to shift too");
+  if (h->n > admm::MPC_MAX_N || h->m > admm::MPC_MAX_M) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": (n, m) beyond (12, 6)");
+  if (s->tail != ADMM_MPC_TAIL_COPY && s->tail != ADMM_MPC_TAIL_ZERO) return bad(fn, "step.tail must be ADMM_MPC_TAIL_COPY or ADMM_MPC_TAIL_ZERO");
+  if (s->reserved != 0) return bad(fn, "step.reserved must be 0");
+  if (s->x_meas && (s->Ap || s->Bp || s->dx)) return bad(fn, "step.x_meas replaces the plant: Ap, Bp and dx must be NULL with it");
+  if (s->q_tail && !h->has_q) return bad(fn, "step.q_tail on a handle that was set up without q");
+  if (s->Ap && !finite_all(s->Ap, (size_t)h->n * h->n)) return bad(fn, "non-finite entry in Ap");
+  if (s->Bp && !finite_all(s->Bp, (size_t)h->n * h->m)) return bad(fn, "non-finite entry in Bp");
+  return ADMM_OK;
+}
+
+// the step itself on the handle's stream; every per-QP array of `d` is device memory (or NULL)
+int advance(admm_handle* h, const admm_mpc_step* s, const DevArgs& d) {
+  int rc;
+  admm::MpcArrays arr{};
+  const int wzy_tail = s->tail == ADMM_MPC_TAIL_ZERO ? admm::MPC_ZERO : admm::MPC_KEEP;
+  arr.count = h->has_q ? 4 : 3;
+  const int chunks = chunk_count(h, arr.count);
+  const size_t P = h->pitch, edge_count = (size_t)arr.count * (chunks - 1) * h->nb * P;
+  if (edge_count > h->mpc_edge_count) {          // (first call, or a larger chunk count asked for since)
+    if (h->mpc_edge) { HIP_TRY(hipFree(h->mpc_edge)); h->mpc_edge = nullptr; h->mpc_edge_count = 0; }
+    if ((rc = dalloc(&h->mpc_edge, edge_count))) return rc;
+    h->mpc_edge_count = edge_count;
+  }
+  if (!h->mpc_xn && (rc = dalloc(&h->mpc_xn, (size_t)h->n * P))) return rc;
+  // the state as (w, z, y) in memory, as admm_get brings it there (w of the last x-update belongs to the old x0)
+  if ((rc = ensure_w(h)) || (rc = ensure_zy(h))) return rc;
+  double* const arrays[4] = {h->w, h->z, h->y, h->q};
+  for (int a = 0; a < arr.count; ++a) { arr.a[a] = arrays[a]; arr.tail[a] = wzy_tail; }
+  if (d.q_tail) arr.tail[3] = admm::MPC_FILL;
+  const admm::MpcGeom g{h->N, h->n, h->m, h->nb, h->batch, h->pitch, chunks};
+  admm::MpcPlant plant{};
+  if (!s->x_meas) {
+    std::memcpy(plant.A, s->Ap ? s->Ap : h->pA.data(), sizeof(double) * h->n * h->n);      // (stage 0 of time-varying dynamics)
+    std::memcpy(plant.B, s->Bp ? s->Bp : h->pB.data(), sizeof(double) * h->n * h->m);
+  }
+  const admm::MpcStep step{h->x0, h->mpc_xn, d.du, d.dx, d.x_meas, d.u, d.x};
+  const unsigned step_blocks = (unsigned)((h->pitch + admm::MPC_THREADS - 1) / admm::MPC_THREADS);
+  hipLaunchKernelGGL(admm::mpc_edges_kernel, dim3(step_blocks, 1 + (unsigned)(arr.count * (chunks - 1))), dim3(admm::MPC_THREADS), 0,
+                     h->stream, arr, g, step, plant, h->mpc_edge);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(admm::mpc_shift_kernel, dim3((unsigned)column_blocks(h), (unsigned)chunks, (unsigned)arr.count),
+                     dim3(admm::MPC_THREADS), 0, h->stream, arr, g, (const double*)h->mpc_edge, d.q_tail);
+  HIP_TRY(hipGetLastError());
+  // the flags admm_update_instances and admm_set_state(w, z, y) leave
+  h->w_stale = false;
+  h->zy_valid = true;
+  h->v_valid = false;
+  drop_side_data(h);
+  h->alt_state = admm_handle::ALT_NONE;
+  return ADMM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int admm_mpc_advance(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next) {
+  const char* fn = "admm_mpc_advance";
+  int rc;
+  if ((rc = check_step(fn, h, s))) return rc;
+  const size_t B = h->batch, nu = B * h->m, nx = B * h->n, nq = B * h->nb;
+  if (s->du && !finite_all(s->du, nu)) return bad(fn, "non-finite entry in du");
+  if (s->dx && !finite_all(s->dx, nx)) return bad(fn, "non-finite entry in dx");
+  if (s->x_meas && !finite_all(s->x_meas, nx)) return bad(fn, "non-finite entry in x_meas");
+  if (s->q_tail && !finite_all(s->q_tail, nq)) return bad(fn, "non-finite entry in q_tail");
+  HIP_TRY(hipSetDevice(h->device));
+  // the small per-QP arrays cross through one device buffer: du | dx or x_meas | q_tail | u_applied | x_next
+  if (!h->mpc_io && (rc = dalloc(&h->mpc_io, 2 * nu + 2 * nx + nq))) return rc;
+  double *du_d = h->mpc_io, *dx_d = du_d + nu, *qt_d = dx_d + nx, *u_d = qt_d + nq, *x_d = u_d + nu;
+  const double* xin = s->x_meas ? s->x_meas : s->dx;
+  if ((s->du && (rc = upload_h2d(h, du_d, s->du, sizeof(double) * nu))) || (xin && (rc = upload_h2d(h, dx_d, xin, sizeof(double) * nx))) ||
+      (s->q_tail && (rc = upload_h2d(h, qt_d, s->q_tail, sizeof(double) * nq))))
+    return rc;
+  const DevArgs d{s->du ? du_d : nullptr, s->dx ? dx_d : nullptr, s->x_meas ? dx_d : nullptr, s->q_tail ? qt_d : nullptr,
+                  u_applied ? u_d : nullptr, x_next ? x_d : nullptr};
+  if ((rc = advance(h, s, d))) return rc;
+  if (u_applied && (rc = download_d2h(h, u_applied, u_d, sizeof(double) * nu))) return rc;
+  if (x_next && (rc = download_d2h(h, x_next, x_d, sizeof(double) * nx))) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return ADMM_OK;
+}
+
+// The device-memory form: du, dx, x_meas, q_tail, u_applied, x_next are device memory of the handle's GPU (Ap, Bp stay host arrays),
+// under the rules of admm_update_instances_device for the inputs and of admm_get_device for the outputs.
+int admm_mpc_advance_device(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next, void* hip_stream) {
+  const char* fn = "admm_mpc_advance_device";
+  int rc;
+  if ((rc = check_step(fn, h, s))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t B = h->batch, nu = B * h->m, nx = B * h->n, nq = B * h->nb;
+  const struct { const double* ptr; size_t count; const char* name; } in[4] = {
+      {s->du, nu, "du"}, {s->dx, nx, "dx"}, {s->x_meas, nx, "x_meas"}, {s->q_tail, nq, "q_tail"}};
+  bool any_input = false;
+  for (const auto& a : in) {
+    if (a.ptr && (rc = check_device_ptr(h->device, a.ptr, a.count * sizeof(double), fn, a.name))) return rc;
+    any_input = any_input || a.ptr;
+  }
+  if ((u_applied && (rc = check_device_ptr(h->device, u_applied, nu * sizeof(double), fn, "u_applied"))) ||
+      (x_next && (rc = check_device_ptr(h->device, x_next, nx * sizeof(double), fn, "x_next"))))
+    return rc;
+  if ((rc = wait_for_caller(h, hip_stream))) return rc;
+  if (any_input) {                               // one pass over each, one synchronisation for all of them
+    if ((rc = check_scratch(h))) return rc;
+    HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, 4 * sizeof(unsigned long long), h->stream));
+    for (int i = 0; i < 4; ++i)
+      if (in[i].ptr && (rc = scan_finite(h->stream, in[i].ptr, in[i].count, h->chk_d + i))) return rc;
+    unsigned long long found[4];
+    HIP_TRY(hipMemcpyAsync(found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < 4; ++i)
+      if (in[i].ptr && found[i] != ~0ull) return bad(fn, std::string("non-finite entry in ") + in[i].name);
+  }
+  const DevArgs d{s->du, s->dx, s->x_meas, s->q_tail, u_applied, x_next};
+  if ((rc = advance(h, s, d))) return rc;
+  if (!hip_stream) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
+  return ADMM_OK;
+}
+
+}  // extern "C"

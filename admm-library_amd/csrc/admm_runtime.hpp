@@ -6,6 +6,7 @@
 //   admm_rho_update.hip rho changes and problem updates: background candidate factors, admm_set_rho, admm_update_problem
 //   admm_pinst_rt.hip per-instance dynamics: device factorisation, trial factorisation, set-up
 //   admm_profile.hip  admm_profile (per-kernel HIP-event timing)
+//   admm_mpc.hip      the receding-horizon step: admm_mpc_advance, admm_mpc_advance_device
 // Everything here is namespace admm::rt; nothing in this header is part of the ABI.
 #pragma once
 
@@ -162,6 +163,10 @@ struct admm_handle {
   double *infeas_y0 = nullptr, *infeas_bnd = nullptr, *infeas_part = nullptr, *infeas_out = nullptr;
   int* infeas_flag = nullptr;    // [pitch] the flag row of infeas_out as int32 (read-out)
   bool infeas_valid = false;     // infeas_bnd describes the handle's current problem (keep_shared() invalidates it)
+  // receding-horizon step (admm_mpc.hip), allocated on the first admm_mpc_advance* call: first blocks of the shift's
+  // chunks [arrays][chunks - 1][nb][pitch], work rows of x+ [n][pitch], and the host form's per-QP inputs and outputs
+  double *mpc_edge = nullptr, *mpc_xn = nullptr, *mpc_io = nullptr;
+  size_t mpc_edge_count = 0;
   int iters_run = 0;
   bool resid_valid = false;
   // A residual-evaluating alternating iteration leaves its finalise to the NEXT scan launch (finalise

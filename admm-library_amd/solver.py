@@ -108,6 +108,9 @@ _SIGNATURES = {
                                            C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
     "admm_scvx_advance_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
                                            C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
+    # receding-horizon step on the device (ADMM_HIP_HAS_MPC)
+    "admm_mpc_advance": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p]),
+    "admm_mpc_advance_device": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p, C.c_void_p]),
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),
@@ -541,6 +544,41 @@ class Solver:
         outs = [torch.empty((self.batch, self.L), dtype=torch.float64, device=dev) if f else None for f in (w, z, y)]
         _check(self._lib, self._lib.admm_get_device(self._h, *[_tptr(o) for o in outs], _stream(dev)))
         return tuple(outs)
+
+    def mpc_advance(self, plant=None, du=None, dx=None, x_meas=None, q_tail=None, tail="copy"):
+        """admm_mpc_advance: one receding-horizon step on the device.  Applies u = z_u,0 + du, sets
+        x0 <- x+ = dx + Ap x0 + Bp u (or x_meas), and moves w, z, y (and q) one stage, the last block following `tail`
+        ("copy" / "zero") or, for q, q_tail.  plant = (Ap, Bp) as (n, n), (n, m) NumPy arrays; None: the handle's A_0, B_0.
+        du (batch, m), dx / x_meas (batch, n), q_tail (batch, n + m): NumPy arrays (host form) or CUDA tensors on the handle's
+        GPU (admm_mpc_advance_device on torch's current stream).  Returns (u_applied, x_next) of the same kind."""
+        n, m = self.problem.n, self.problem.m
+        if tail not in _abi.MPC_TAILS:
+            raise ValueError(f"tail must be one of {sorted(_abi.MPC_TAILS)}, got {tail!r}")
+        keep = []
+        if plant is not None:
+            Ap, Bp = (np.asarray(a, np.float64) for a in plant)
+            if Ap.shape != (n, n) or Bp.shape != (n, m):
+                raise ValueError(f"plant: expected shapes {(n, n)} and {(n, m)}, got {Ap.shape} and {Bp.shape}")
+            keep = [_abi._colmajor(Ap), _abi._colmajor(Bp)]
+        step = _abi.CMpcStep(Ap=dptr(keep[0]) if keep else None, Bp=dptr(keep[1]) if keep else None,
+                             tail=_abi.MPC_TAILS[tail], reserved=0)
+        arrays = {"du": (du, m), "dx": (dx, n), "x_meas": (x_meas, n), "q_tail": (q_tail, n + m)}
+        if any(_on_gpu(a) for a, _ in arrays.values()):
+            import torch
+            dev = self._tensors(**arrays)
+            for k, (a, _) in arrays.items():
+                setattr(step, k, _tptr(a))
+            u = torch.empty((self.batch, m), dtype=torch.float64, device=dev)
+            x = torch.empty((self.batch, n), dtype=torch.float64, device=dev)
+            _check(self._lib, self._lib.admm_mpc_advance_device(self._h, C.byref(step), _tptr(u), _tptr(x), _stream(dev)))
+            return u, x
+        for k, (a, cols) in arrays.items():
+            a = self._vec(a, cols)
+            keep.append(a)
+            setattr(step, k, dptr(a))
+        u, x = np.empty((self.batch, m)), np.empty((self.batch, n))
+        _check(self._lib, self._lib.admm_mpc_advance(self._h, C.byref(step), dptr(u), dptr(x)))
+        return u, x
 
     def profile(self, iters: int, residuals: bool = True, fused: bool = True, alternating: bool = False,
                 back_to_back: bool = False, lean: bool = False):

@@ -386,6 +386,45 @@ int admm_scvx_prepare_device(int32_t device, const admm_scvx_model* model, const
 int admm_scvx_advance_device(int32_t device, const admm_scvx_model* model, const admm_scvx_params* params, const double* x0,
                              const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
 
+/* Receding-horizon (MPC) step on the device (new symbols, announced by ADMM_HIP_HAS_MPC -- no struct or
+ * signature changed): apply the first control, propagate the plant, move the window one stage.  Per QP b, in this order:
+ *   1. the state is brought into the (z, y) pair and w into memory, as admm_get does
+ *   2. u = z_u,0 + du            (rows 0 .. m-1 of block 0 of z; one addition per row, none with du = NULL)
+ *   3. x+ = x_meas if given; else row i: acc = dx_i (or 0), acc = fma(Ap[i,j], x0_j, acc) for j ascending, then
+ *      acc = fma(Bp[i,j], u_j, acc) for j ascending
+ *   4. x0 <- x+, with the effect of admm_update_instances(h, x+, NULL)
+ *   5. w, z, y, and q if the handle has one: block k <- block k+1 (k = 0 .. N-2); block N-1 keeps its content (TAIL_COPY) or
+ *      becomes 0 (TAIL_ZERO); q's block N-1 is q_tail if given
+ *   6. the flags are those admm_set_state(h, w', z', y') leaves; per-QP iters, status, residuals, rho, the factor and the
+ *      certificate / infeasibility caches are untouched
+ * The call equals, bit for bit in the state and in every later iterate, admm_get; that shift on the host;
+ * admm_update_instances(x+, q'); admm_set_state(w', z', y').  The problem data are window-relative: time_varying = 1 and
+ * stage_bounds = 1 are served as they are (a shifted z may lie outside its new stage's box, as admm_set_state allows).
+ * Ap (n*n) and Bp (n*m) are HOST memory in both forms, column-major like admm_problem.A; NULL = the handle's A_0 / B_0.
+ * du (m*batch), dx, x_meas (n*batch), q_tail (nb*batch), u_applied (m*batch), x_next (n*batch) are QP-major; each may be NULL.
+ * admm_mpc_advance_device: those six are device memory of the handle's GPU -- pointer checks, finite scans and stream hand-over as
+ * admm_update_instances_device (inputs) and admm_get_device (outputs): hip_stream waits for the library's writes; the only host
+ * synchronisation is the finite scan's, and with no input array the call queues its work and returns (hip_stream = NULL: it
+ * returns with the work complete).
+ * ADMM_ERR_UNSUPPORTED (nothing launched, the handle unchanged): per-instance dynamics (time_varying = 2), time-sharded handles.
+ * ADMM_ERR_INVALID (likewise): s = NULL, an unknown tail, reserved != 0, x_meas together with Ap / Bp / dx, q_tail on a handle
+ * without q, a non-finite entry in any input. */
+#define ADMM_HIP_HAS_MPC 1
+#define ADMM_MPC_TAIL_COPY 0   /* the last block keeps its old content (the old block N-1 appears twice) */
+#define ADMM_MPC_TAIL_ZERO 1   /* the last block of w, z, y becomes 0 */
+typedef struct admm_mpc_step {
+  const double* Ap;      /* plant, n*n column-major like admm_problem.A; NULL = the handle's A_0 */
+  const double* Bp;      /* n*m; NULL = the handle's B_0.  Ap, Bp are HOST memory in both forms */
+  const double* du;      /* m*batch, added to the commanded control (actuation error); NULL = 0 */
+  const double* dx;      /* n*batch, added to the propagated state (process noise); NULL = 0 */
+  const double* x_meas;  /* n*batch: if given, the new x0 is this and the plant is not evaluated; Ap, Bp, dx must then be NULL */
+  const double* q_tail;  /* nb*batch: the new last block of q; NULL = q's tail follows `tail` */
+  int32_t tail;          /* ADMM_MPC_TAIL_* */
+  int32_t reserved;      /* 0 */
+} admm_mpc_step;
+int admm_mpc_advance(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next);
+int admm_mpc_advance_device(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next, void* hip_stream);
+
 /* Per-QP results of the last admm_solve: first checked iteration at which the
  * rule held (max_iter if never), status (1 converged / 0 not), last r and s. */
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s);
