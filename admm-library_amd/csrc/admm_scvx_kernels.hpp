@@ -1,6 +1,7 @@
 // admm_scvx_kernels.hpp -- the outer step of the batched successive-convexification loop on the device: the
 // device counterparts of scvx.rollout, scvx.linearise, scvx.correction_qp_batch and the decision block of scvx.scvx_batch, for the
-// shipped model (scvx.relative_motion_rhs / rk4_step, n = 6, m = 3).  fp64, explicit fma(), no inline assembly.
+// model M the kernels are instantiated for (n = 6, m = 3; the shipped one, scvx.relative_motion_rhs, in admm_scvx.hip; DESIGN.md
+// §2.8.2: the others in admm_scvx_models.hip).  fp64, explicit fma(), no inline assembly.
 //
 // Every caller-visible array is QP-major C order (the shapes of Problem / DeviceProblem): u (B, N, 3), x (B, N, 6) = x_1 .. x_N,
 // A (B, N, 6, 6) and B (B, N, 6, 3) as row-major blocks, lo | hi | q | z (B, N, 9) in block order (u_k, x_{k+1}).
@@ -13,7 +14,7 @@
 //                          central differences are written into LDS and leave as whole contiguous rows; q, lo, hi likewise
 //   scvx_advance_kernel    one lane per trajectory, sequential in k: the candidate (u_new, x_new), J_lin, J_new, du_max and the
 //                          accept / reject / stop decision; inactive trajectories are loaded and left untouched
-//   scvx_commit_kernel     elementwise: candidate -> reference where `take` is set
+//   scvx_commit_kernel     elementwise: candidate -> reference where `take` is set (no model: it lives in admm_scvx.hip)
 //
 // Every kernel runs one wave per workgroup (SCVX_THREADS = 64).  No early return before a barrier: lanes past the end load the last
 // trajectory / stage and store nothing.
@@ -35,39 +36,70 @@ constexpr int SCVX_ROLL_CH = 8;         // stages per LDS chunk, rollout (64 x (
 constexpr int SCVX_ADV_CH = 4;          // ... advance (64 x (36 + 12 + 24 + 3 + 12 + 24 + 2) doubles = 57 KB)
 constexpr int SCVX_HIST = 9;            // doubles per history record
 
-struct ScvxModel {                      // admm_scvx_model and what the host derives from it once
+// What every model carries: the horizon and the step sizes the host derives once (dt / substeps, h / 2, h / 6)
+struct ScvxGrid {
   int N, batch, substeps;
-  double h, hh, h6, rc, rc3;            // dt / substeps, h / 2, h / 6; rc^3
+  double h, hh, h6;
 };
 
-// scvx.relative_motion_rhs: d = f(s, u), the formulas in the same order (rd^3 = r2 sqrt(r2) for pow(r2, 1.5))
-__device__ __forceinline__ void scvx_rhs(const double (&s)[6], const double (&u)[3], const ScvxModel& md, double (&d)[6]) {
-  const double xr = md.rc + s[0];
-  const double r2 = fma(s[2], s[2], fma(s[1], s[1], xr * xr));
-  const double k = md.rc3 / (r2 * sqrt(r2));
-  d[0] = s[3];
-  d[1] = s[4];
-  d[2] = s[5];
-  d[3] = fma(-k, xr, fma(2.0, s[4], s[0]) + md.rc) + u[0];
-  d[4] = fma(-k, s[1], fma(-2.0, s[3], s[1])) + u[1];
-  d[5] = fma(-k, s[2], u[2]);
-}
+// A model type M is the grid plus the parameters the host derives once from the caller's struct, and
+//   static void rhs(const double (&s)[6], const double (&u)[3], const M& md, double (&d)[6])      d = f(s, u)
+// -- nothing else: RK4, the LDS chunking, the central differences, the cost chains and the decision below are one copy of code.
 
-// scvx.rk4_step: s <- F(s, u), classical RK4 over `substeps` sub-intervals under a held control
-__device__ __forceinline__ void scvx_step(double (&s)[6], const double (&u)[3], const ScvxModel& md) {
+// scvx.relative_motion_rhs (admm_scvx_model; ADMM_SCVX_RELATIVE_CIRCULAR): the formulas in the same order (rd^3 = r2 sqrt(r2) for
+// pow(r2, 1.5)); rc3 = rc^3
+struct ScvxRelativeCircular : ScvxGrid {
+  double rc, rc3;
+  __device__ __forceinline__ static void rhs(const double (&s)[6], const double (&u)[3], const ScvxRelativeCircular& md, double (&d)[6]) {
+    const double xr = md.rc + s[0];
+    const double r2 = fma(s[2], s[2], fma(s[1], s[1], xr * xr));
+    const double k = md.rc3 / (r2 * sqrt(r2));
+    d[0] = s[3];
+    d[1] = s[4];
+    d[2] = s[5];
+    d[3] = fma(-k, xr, fma(2.0, s[4], s[0]) + md.rc) + u[0];
+    d[4] = fma(-k, s[1], fma(-2.0, s[3], s[1])) + u[1];
+    d[5] = fma(-k, s[2], u[2]);
+  }
+};
+
+// scvx.crtbp_rhs (ADMM_SCVX_CRTBP): the circular restricted three-body problem in the rotating frame, primaries at X = -mu and
+// X = 1 - mu, position measured from (x_ref, 0, 0); om = 1 - mu.  The formulas in the same order (r sqrt(r) for the 3/2 power); no
+// special handling near a primary: inf / NaN propagate into the cost, and the candidate then fails ratio >= rho_reject
+struct ScvxCrtbp : ScvxGrid {
+  double mu, om, x_ref;
+  __device__ __forceinline__ static void rhs(const double (&s)[6], const double (&u)[3], const ScvxCrtbp& md, double (&d)[6]) {
+    const double X = md.x_ref + s[0];
+    const double d1 = X + md.mu, d2 = (X - 1.0) + md.mu;
+    const double yz = fma(s[2], s[2], s[1] * s[1]);
+    const double r1 = fma(d1, d1, yz), r2 = fma(d2, d2, yz);
+    const double k1 = md.om / (r1 * sqrt(r1)), k2 = md.mu / (r2 * sqrt(r2));
+    const double k12 = k1 + k2;
+    d[0] = s[3];
+    d[1] = s[4];
+    d[2] = s[5];
+    d[3] = fma(-k2, d2, fma(-k1, d1, fma(2.0, s[4], X))) + u[0];
+    d[4] = fma(-k12, s[1], fma(-2.0, s[3], s[1])) + u[1];
+    d[5] = fma(-k12, s[2], u[2]);
+  }
+};
+
+// rk4_step of the model: s <- F(s, u), classical RK4 over `substeps` sub-intervals under a held control
+template <class M>
+__device__ __forceinline__ void scvx_step(double (&s)[6], const double (&u)[3], const M& md) {
 #pragma unroll 1
   for (int sub = 0; sub < md.substeps; ++sub) {
     double k[6], acc[6], t[6];
-    scvx_rhs(s, u, md, k);
+    M::rhs(s, u, md, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = k[i]; t[i] = fma(md.hh, k[i], s[i]); }
-    scvx_rhs(t, u, md, k);
+    M::rhs(t, u, md, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = fma(2.0, k[i], acc[i]); t[i] = fma(md.hh, k[i], s[i]); }
-    scvx_rhs(t, u, md, k);
+    M::rhs(t, u, md, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = fma(2.0, k[i], acc[i]); t[i] = fma(md.h, k[i], s[i]); }
-    scvx_rhs(t, u, md, k);
+    M::rhs(t, u, md, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) s[i] = fma(md.h6, acc[i] + k[i], s[i]);
   }
@@ -121,6 +153,11 @@ __device__ __forceinline__ void scvx_chunk_store(const double* lds, double* __re
   }
 }
 
+// x is a NaN, by its bits: exponent all ones, mantissa not zero (isnan() is folded away under -fno-honor-nans)
+__device__ __forceinline__ bool scvx_is_nan(double x) {
+  return ((unsigned long long)__double_as_longlong(x) & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
+
 // What admm_scvx_init_device sets besides ub = 0 and xb = rollout(x0, 0)
 struct ScvxInit {
   double *J, *tr_u, *tr_x;
@@ -128,8 +165,8 @@ struct ScvxInit {
   double tr_u0, tr_x0;
 };
 
-template <bool INIT>
-__global__ __launch_bounds__(SCVX_THREADS) void scvx_rollout_kernel(ScvxModel md, admm_scvx_params pr, const double* __restrict__ x0,
+template <class M, bool INIT>
+__global__ __launch_bounds__(SCVX_THREADS) void scvx_rollout_kernel(M md, admm_scvx_params pr, const double* __restrict__ x0,
                                                                     const double* __restrict__ u, double* __restrict__ x, ScvxInit in) {
   constexpr int CH = SCVX_ROLL_CH, SU = SCVX_NU * CH + 1, SX = SCVX_NX * CH + 1;
   __shared__ double lu[SCVX_THREADS * SU];
@@ -171,7 +208,8 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_rollout_kernel(ScvxModel md
 
 // One lane per (trajectory, stage): flat index i = b N + k.  A_k, B_k of scvx.linearise at (xprev_k, u_k) -- xprev_0 = x0, else
 // xb_{k-1} --, and the stage's q, lo, hi of scvx.correction_qp_batch; an inactive trajectory gets trust radii 0.
-__global__ __launch_bounds__(SCVX_THREADS) void scvx_linearise_kernel(ScvxModel md, admm_scvx_params pr, const double* __restrict__ x0,
+template <class M>
+__global__ __launch_bounds__(SCVX_THREADS) void scvx_linearise_kernel(M md, admm_scvx_params pr, const double* __restrict__ x0,
                                                                       const double* __restrict__ ub, const double* __restrict__ xb,
                                                                       const double* __restrict__ tr_u, const double* __restrict__ tr_x,
                                                                       const int32_t* __restrict__ active, double* __restrict__ A,
@@ -262,7 +300,8 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_linearise_kernel(ScvxModel 
 
 // The decision block of scvx.scvx_batch for every ACTIVE trajectory, after the candidate has been built from z in one pass over the
 // stages; adds the number of trajectories still active afterwards to *n_active (one atomic per wave).
-__global__ __launch_bounds__(SCVX_THREADS) void scvx_advance_kernel(ScvxModel md, admm_scvx_params pr, const double* __restrict__ x0,
+template <class M>
+__global__ __launch_bounds__(SCVX_THREADS) void scvx_advance_kernel(M md, admm_scvx_params pr, const double* __restrict__ x0,
                                                                     const double* __restrict__ z, admm_scvx_state st,
                                                                     int* __restrict__ n_active) {
   constexpr int CH = SCVX_ADV_CH, SZ = SCVX_NB * CH + 1, SU = SCVX_NU * CH + 1, SX = SCVX_NX * CH + 1;
@@ -317,14 +356,18 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_advance_kernel(ScvxModel md
     const double J = st.J[b], tu = st.tr_u[b], tx = st.tr_x[b];
     const double J_lin = scvx_cost_total(lu_c, lx_c, ln_c), J_new = scvx_cost_total(nu_c, nx_c, nn_c);
     const double predicted = J - J_lin, actual = J - J_new;
-    const double ratio = predicted > 0.0 ? actual / predicted : -INFINITY;
+    // a NaN compares false in scvx.outer_update: no stop, no accept.  Device code is built with -fno-honor-nans, under which a
+    // compare and its complement are interchangeable, so the NaN cases are taken out by a test of the bits before any compare
+    const bool pred_nan = scvx_is_nan(predicted);
+    const double ratio = !pred_nan && predicted > 0.0 ? actual / predicted : -INFINITY;
+    const bool ratio_nan = scvx_is_nan(ratio);
     const int it = st.outer[b];
     bool acc = false, stop = false;
-    if (predicted <= pr.tol * fmax(1.0, fabs(J))) {          // the model sees nothing left to gain
+    if (!pred_nan && predicted <= pr.tol * fmax(1.0, fabs(J))) {          // the model sees nothing left to gain
       stop = true;
     } else {
-      if (ratio >= pr.rho_reject) {
-        acc = true;
+      acc = !ratio_nan && ratio >= pr.rho_reject;
+      if (acc) {
         st.J[b] = J_new;
         st.accepted[b] += 1;
         if (ratio >= pr.rho_expand) { st.tr_u[b] = 2.0 * tu; st.tr_x[b] = 2.0 * tx; }
@@ -346,20 +389,6 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_advance_kernel(ScvxModel md
   }
   const unsigned long long m = __ballot(still);
   if (lane == 0 && m) atomicAdd(n_active, __popcll(m));
-}
-
-// candidate -> reference for the trajectories the decision accepted (u: B N 3 elements, then x: B N 6)
-__global__ __launch_bounds__(256) void scvx_commit_kernel(int N, size_t nu_total, size_t total, const int32_t* __restrict__ take,
-                                                          const double* __restrict__ u_cand, const double* __restrict__ x_cand,
-                                                          double* __restrict__ ub, double* __restrict__ xb) {
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-    if (e < nu_total) {
-      if (take[e / ((size_t)N * 3)]) ub[e] = u_cand[e];
-    } else {
-      const size_t f = e - nu_total;
-      if (take[f / ((size_t)N * 6)]) xb[f] = x_cand[f];
-    }
-  }
 }
 
 }  // namespace admm

@@ -31,6 +31,7 @@ has its own linearisation, box and linear term, i.e. one QP batch with per-insta
 from __future__ import annotations
 
 import dataclasses
+import functools
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -61,6 +62,123 @@ def rk4_step(s: np.ndarray, u: np.ndarray, dt: float, substeps: int = 4, rc: flo
         k4 = relative_motion_rhs(s + h * k3, u, rc)
         s = s + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
     return s
+
+
+MU_EARTH_MOON = 0.012150585    # mass ratio m2 / (m1 + m2) of the Earth-Moon system
+
+
+def crtbp_rhs(s, u, mu: float, x_ref: float = 0.0):
+    """Circular restricted three-body problem in the nondimensional rotating frame (primaries at X = -mu and X = 1 - mu): time
+    derivative of s = (x, y, z, vx, vy, vz) (..., 6), the position measured from the point (x_ref, 0, 0), under the thrust
+    acceleration u (..., 3).  The normative statement of the device model ScvxCrtbp; NumPy arrays or torch
+    tensors.  Nothing is special near a primary: inf / NaN propagate."""
+    if isinstance(s, np.ndarray):
+        sqrt, stack = np.sqrt, functools.partial(np.stack, axis=-1)
+    else:
+        import torch
+        sqrt, stack = torch.sqrt, functools.partial(torch.stack, dim=-1)
+    x, y, z, vx, vy, vz = (s[..., i] for i in range(6))
+    ux, uy, uz = (u[..., i] for i in range(3))
+    X = x_ref + x;  d1 = X + mu;  d2 = X - 1 + mu;  yz = y**2 + z**2
+    r1 = d1**2 + yz;  r2 = d2**2 + yz
+    k1 = (1 - mu) / (r1 * sqrt(r1));  k2 = mu / (r2 * sqrt(r2))
+    ax = 2*vy + X - k1*d1 - k2*d2 + ux
+    ay = -2*vx + y - (k1 + k2)*y + uy
+    az = -(k1 + k2)*z + uz
+    return stack((vx, vy, vz, ax, ay, az))
+
+
+def _relative_motion_rhs_torch(s, uu, rc):
+    """relative_motion_rhs on torch tensors: the same formulas in the same order."""
+    import torch
+    x, y, z, vx, vy, vz = (s[..., i] for i in range(6))
+    rd3 = ((rc + x) ** 2 + y ** 2 + z ** 2) ** 1.5
+    k = rc ** 3 / rd3
+    ax = 2.0 * vy + x + rc - k * (rc + x) + uu[..., 0]
+    ay = -2.0 * vx + y - k * y + uu[..., 1]
+    az = -k * z + uu[..., 2]
+    return torch.stack([vx, vy, vz, ax, ay, az], dim=-1)
+
+
+def _rk4(rhs, s, u, dt, substeps):
+    h = dt / substeps
+    for _ in range(substeps):
+        k1 = rhs(s, u)
+        k2 = rhs(s + 0.5 * h * k1, u)
+        k3 = rhs(s + 0.5 * h * k2, u)
+        k4 = rhs(s + h * k3, u)
+        s = s + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+    return s
+
+
+@dataclasses.dataclass(frozen=True)
+class Model:
+    """A nonlinear model the loop can be run for, on the host and -- by `kind`, one of the models compiled into the library
+    (admm_scvx_dynamics) -- in the device outer step: n = 6, m = 3, time-invariant."""
+    name: str                     # admm_scvx_model_name(kind)
+    kind: int                     # ADMM_SCVX_RELATIVE_CIRCULAR | ADMM_SCVX_CRTBP
+    par: Tuple[float, ...]        # admm_scvx_dynamics.par, the entries in use
+    rhs: Callable                 # rhs(s, u) on NumPy arrays
+    rhs_torch: Callable           # ... on torch tensors: the same formulas in the same order
+
+    def step(self, s, u, dt: float, substeps: int = 4):
+        """Zero-order-hold propagation of one stage (classical RK4 over rhs, `substeps` sub-intervals): the `step` of rollout,
+        linearise, scvx and scvx_batch."""
+        return _rk4(self.rhs, s, u, dt, substeps)
+
+
+def relative_circular(rc: float = RC_KM) -> Model:
+    """The shipped model: relative_motion_rhs about a circular orbit of radius rc."""
+    return Model("relative_circular", 0, (float(rc),), functools.partial(relative_motion_rhs, rc=rc),
+                 functools.partial(_relative_motion_rhs_torch, rc=rc))
+
+
+def crtbp(mu: float, x_ref: float = 0.0) -> Model:
+    """The circular restricted three-body problem of mass ratio mu, the state relative to (x_ref, 0, 0) (crtbp_rhs).  With x_ref a
+    collinear libration point (crtbp_collinear_point) the origin is an equilibrium and the loop's quadratic cost means "acquire
+    or keep the point"."""
+    if not (np.isfinite(mu) and 0.0 < mu < 1.0) or not np.isfinite(x_ref):
+        raise ValueError("crtbp: mu must lie in (0, 1) and x_ref be finite")
+    f = functools.partial(crtbp_rhs, mu=float(mu), x_ref=float(x_ref))
+    return Model("crtbp", 1, (float(mu), float(x_ref)), f, f)
+
+
+def crtbp_collinear_point(mu: float, which: int) -> float:
+    """X of the collinear libration point L1, L2 or L3 (which = 1, 2, 3) of the CR3BP of mass ratio mu: the root of the x-axis
+    equilibrium equation X - (1 - mu) (X + mu) / |X + mu|^3 - mu (X - 1 + mu) / |X - 1 + mu|^3 = 0 in the point's interval, by
+    Newton's method in extended precision from Hill's estimate, then the fp64 neighbour at which crtbp_rhs at rest is smallest."""
+    if which not in (1, 2, 3):
+        raise ValueError("which must be 1, 2 or 3")
+    LD = np.longdouble
+    m = LD(mu)
+    rh = (m / LD(3)) ** (LD(1) / LD(3))
+    X = {1: LD(1) - m - rh, 2: LD(1) - m + rh, 3: -LD(1) - LD(5) * m / LD(12)}[which]
+
+    def f(X):
+        d1, d2 = X + m, X - LD(1) + m
+        return X - (LD(1) - m) * d1 / abs(d1) ** 3 - m * d2 / abs(d2) ** 3
+
+    def df(X):
+        d1, d2 = X + m, X - LD(1) + m
+        return LD(1) + LD(2) * (LD(1) - m) / abs(d1) ** 3 + LD(2) * m / abs(d2) ** 3
+    for _ in range(60):
+        step = f(X) / df(X)
+        X = X - step
+        if abs(step) <= LD(4) * np.finfo(LD).eps * abs(X):
+            break
+    x = float(X)
+    rest, zero = np.zeros(6), np.zeros(3)
+    cands = [x, np.nextafter(x, -np.inf), np.nextafter(x, np.inf)]
+    return min(cands, key=lambda c: float(np.abs(crtbp_rhs(rest, zero, mu, c)).max()))
+
+
+def _resolve(model: Optional[Model], step):
+    """The `step` of a call that may name a model instead: model.step; both: ValueError."""
+    if model is None:
+        return step
+    if step is not rk4_step:
+        raise ValueError("model and step cannot both be given")
+    return model.step
 
 
 def rollout(x0: np.ndarray, u: np.ndarray, dt: float, step=rk4_step) -> np.ndarray:
@@ -94,35 +212,22 @@ def linearise(xprev: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, eps: f
 
 
 def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = "cuda:0", eps: float = 1e-6,
-                     substeps: int = 4, rc: float = RC_KM, keep_on_device: bool = False):
+                     substeps: int = 4, rc: float = RC_KM, keep_on_device: bool = False, model: Optional[Model] = None):
     """linearise() of the shipped model (rk4_step of relative_motion_rhs) with the n + m central differences evaluated as ONE
     batch of torch tensors on `device`: the same formulas in the same order, fp64.  The NumPy version makes 2 (n + m) x 16
     passes over (B, N, 6) arrays -- 10 s per outer iteration of a 4096-trajectory batch, most of the wall time of
     examples/scvx_batch_rendezvous.py; this is host plumbing, not the solver.
-    keep_on_device: return A, B as the torch tensors on `device` (for a DeviceProblem) instead of NumPy copies."""
+    keep_on_device: return A, B as the torch tensors on `device` (for a DeviceProblem) instead of NumPy copies.
+    model: the right-hand side is model.rhs_torch instead of the shipped one (rc is then not used)."""
     import torch
     xp = torch.as_tensor(np.ascontiguousarray(xprev), dtype=torch.float64, device=device)
     up = torch.as_tensor(np.ascontiguousarray(u), dtype=torch.float64, device=device)
     n, m = xp.shape[-1], up.shape[-1]
 
-    def rhs(s, uu):
-        x, y, z, vx, vy, vz = (s[..., i] for i in range(6))
-        rd3 = ((rc + x) ** 2 + y ** 2 + z ** 2) ** 1.5
-        k = rc ** 3 / rd3
-        ax = 2.0 * vy + x + rc - k * (rc + x) + uu[..., 0]
-        ay = -2.0 * vx + y - k * y + uu[..., 1]
-        az = -k * z + uu[..., 2]
-        return torch.stack([vx, vy, vz, ax, ay, az], dim=-1)
+    rhs = functools.partial(_relative_motion_rhs_torch, rc=rc) if model is None else model.rhs_torch
 
     def step(s, uu):
-        h = dt / substeps
-        for _ in range(substeps):
-            k1 = rhs(s, uu)
-            k2 = rhs(s + 0.5 * h * k1, uu)
-            k3 = rhs(s + 0.5 * h * k2, uu)
-            k4 = rhs(s + h * k3, uu)
-            s = s + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
-        return s
+        return _rk4(rhs, s, uu, dt, substeps)
 
     ex = eps * torch.eye(n, dtype=torch.float64, device=device).reshape((n,) + (1,) * (xp.dim() - 1) + (n,))
     eu = eps * torch.eye(m, dtype=torch.float64, device=device).reshape((m,) + (1,) * (up.dim() - 1) + (m,))
@@ -217,14 +322,16 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
          qp_solver: Optional[Callable[[Problem], Tuple[np.ndarray, int]]] = None,
          u_init: Optional[np.ndarray] = None, tr_u: float = 0.1, tr_x: float = 20.0,
          max_outer: int = 20, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7,
-         step=rk4_step, qp_options: Optional[dict] = None) -> ScvxResult:
+         step=rk4_step, qp_options: Optional[dict] = None, model: Optional[Model] = None) -> ScvxResult:
     """Trust-region successive convexification of
 
         minimise 1/2 sum_k [u_k' R u_k + x_{k+1}' Q_{k+1} x_{k+1}]   s.t.  x_{k+1} = F(x_k, u_k),  u_lo <= u_k <= u_hi.
 
     qp_solver(problem) -> (z of shape (1, L), ADMM iterations); default = the HIP solver.
     A step is accepted when actual / predicted cost decrease >= rho_reject (trust radii halve
-    otherwise, double above rho_expand); stops when the accepted correction is below `tol`."""
+    otherwise, double above rho_expand); stops when the accepted correction is below `tol`.
+    model: a Model (relative_circular(), crtbp(...)) whose step replaces `step`; not both."""
+    step = _resolve(model, step)
     x0 = np.asarray(x0, np.float64)
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
     n, m = Q.shape[0], R.shape[0]
@@ -275,17 +382,20 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
 
 def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
                         tr_u: np.ndarray, tr_x: np.ndarray, step=rk4_step, device: Optional[str] = None,
-                        qp_data_on_device: bool = False):
+                        qp_data_on_device: bool = False, model: Optional[Model] = None):
     """The correction QPs of B trajectories as ONE batch with per-instance dynamics, box and linear term
     (xb (B, N, n), ub (B, N, m), x0 (B, n), trust radii (B,)).
     qp_data_on_device (with device): a DeviceProblem -- A, B stay where linearise_device made them, the rest is built here
-    exactly as for the Problem and copied to the device."""
+    exactly as for the Problem and copied to the device.
+    model (scvx_batch passes it with step = model.step): the device linearisation evaluates model.rhs_torch."""
     Bn, N, n = xb.shape
     m = ub.shape[-1]
     xprev = np.concatenate([x0[:, None, :], xb[:, :-1, :]], axis=1)
-    if qp_data_on_device and (device is None or step is not rk4_step):
+    if qp_data_on_device and (device is None or (step is not rk4_step and model is None)):
         raise ValueError("qp_data_on_device needs the device linearisation (device = 'cuda:k', the shipped rk4_step)")
-    if device is not None and step is rk4_step:
+    if device is not None and model is not None:
+        A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device, model=model)
+    elif device is not None and step is rk4_step:
         A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device)
     else:
         A, B = linearise(xprev, ub, dt, step)
@@ -353,7 +463,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
                tr_u: float = 0.1, tr_x: float = 20.0, max_outer: int = 20, tol: float = 1e-6,
                rho_reject: float = 0.1, rho_expand: float = 0.7, step=rk4_step,
                qp_options: Optional[dict] = None, linearise_on: Optional[str] = None,
-               qp_data_on_device: bool = False, outer_on_device: bool = False) -> List[ScvxResult]:
+               qp_data_on_device: bool = False, outer_on_device: bool = False, model: Optional[Model] = None) -> List[ScvxResult]:
     """scvx() for B initial conditions x0 (B, n) at once: the same trust-region loop per trajectory (own trust radii,
     own accept / reject decisions, own stop), but ONE batched QP solve per outer iteration -- per-instance dynamics,
     bounds and linear term (correction_qp_batch).  A trajectory that has stopped keeps its place in the batch with a
@@ -364,7 +474,10 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     outer_on_device (with linearise_on, the shipped rk4_step): everything between two QP solves -- rollout, linearisation, QP
     assembly, costs, decisions -- runs in the HIP kernels of DeviceOuterStep on the tensors the solver reads and writes; the host
     reads one integer per outer iteration.  Same scheme, same formulas; the roundings differ (device sqrt / fma), so the result
-    agrees with the host loop to the QP tolerance, not bit for bit."""
+    agrees with the host loop to the QP tolerance, not bit for bit.
+    model: a Model whose step replaces `step` (not both); linearise_on then evaluates model.rhs_torch, and outer_on_device runs the
+    kernels of that model (DeviceOuterStep(model=...), the admm_scvx_*_model_device entry points)."""
+    step = _resolve(model, step)
     x0 = np.atleast_2d(np.asarray(x0, np.float64))
     Bn = x0.shape[0]
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
@@ -372,13 +485,13 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     u_lo = np.broadcast_to(np.asarray(u_lo, np.float64), (m,))
     u_hi = np.broadcast_to(np.asarray(u_hi, np.float64), (m,))
     if outer_on_device:
-        if linearise_on is None or step is not rk4_step:
+        if linearise_on is None or (step is not rk4_step and model is None):
             raise ValueError("outer_on_device needs linearise_on = 'cuda:k' and the shipped rk4_step")
         if qp_solver is None:
             qp_solver = gpu_qp_solver(True, z_on_device=True, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8,
                                                                                     max_iter=20000, check_interval=25)))
         loop = DeviceOuterStep(x0, N, dt, Q, R, QN, u_lo, u_hi, device=linearise_on, tol=tol, rho_reject=rho_reject,
-                               rho_expand=rho_expand, max_outer=max_outer)
+                               rho_expand=rho_expand, max_outer=max_outer, model=model)
         loop.init(tr_u, tr_x)
         admm_iters: List[int] = []
         n_active = Bn
@@ -405,7 +518,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         if not active.any():
             break
         p = correction_qp_batch(xb, ub, x0, dt, Q, R, QN, u_lo, u_hi, np.where(active, tru, 0.0), np.where(active, trx, 0.0), step,
-                                device=linearise_on, qp_data_on_device=qp_data_on_device)
+                                device=linearise_on, qp_data_on_device=qp_data_on_device, model=model)
         z, admm_iters = qp_solver(p)
         d = np.asarray(z, np.float64).reshape(Bn, N, m + n)
         du, dx = d[..., :m], d[..., m:]
@@ -424,14 +537,17 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
 
 class DeviceOuterStep:
     """The state of scvx_batch(outer_on_device=True) as torch tensors on one GPU, and the four device entry points on it
-    (ADMM_HIP_HAS_SCVX): rollout / init / prepare / advance.  Shipped model only (relative_motion_rhs, rk4_step).
+    (ADMM_HIP_HAS_SCVX): rollout / init / prepare / advance.  Without `model`: the shipped model (relative_motion_rhs,
+    rk4_step) through admm_scvx_*_device; with a Model: its kind and parameters in an admm_scvx_dynamics, through
+    admm_scvx_*_model_device (ADMM_HIP_HAS_SCVX_MODELS; rc is then not used).
     Every call is queued on torch's current stream; advance() alone waits -- for the count of trajectories still active."""
 
     STATE_F64 = ("ub", "xb", "u_cand", "x_cand", "J", "tr_u", "tr_x")
     STATE_I32 = ("active", "converged", "accepted", "outer", "take")
 
     def __init__(self, x0, N: int, dt: float, Q, R, QN, u_lo, u_hi, device: str = "cuda:0", substeps: int = 4, rc: float = RC_KM,
-                 eps: float = 1e-6, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7, max_outer: int = 20):
+                 eps: float = 1e-6, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7, max_outer: int = 20,
+                 model: Optional[Model] = None):
         import torch
 
         from . import _abi
@@ -441,7 +557,11 @@ class DeviceOuterStep:
         x0 = np.atleast_2d(np.asarray(x0, np.float64))
         Bn = x0.shape[0]
         self.batch, self.N = Bn, int(N)
-        self.model = _abi.CScvxModel(N=int(N), batch=Bn, substeps=int(substeps), dt=float(dt), rc=float(rc))
+        if model is None:
+            self.model, self._suffix = _abi.CScvxModel(N=int(N), batch=Bn, substeps=int(substeps), dt=float(dt), rc=float(rc)), "_device"
+        else:
+            self.model, self._suffix = _abi.CScvxDynamics(N=int(N), batch=Bn, substeps=int(substeps), kind=int(model.kind), dt=float(dt)), "_model_device"
+            self.model.par[:len(model.par)] = [float(v) for v in model.par]
         self.params = _abi.CScvxParams(fd_eps=float(eps), tol=float(tol), rho_reject=float(rho_reject), rho_expand=float(rho_expand))
         for name, a, shape in (("Q", Q, (6, 6)), ("R", R, (3, 3)), ("QN", QN, (6, 6)), ("u_lo", np.broadcast_to(u_lo, (3,)), (3,)),
                                ("u_hi", np.broadcast_to(u_hi, (3,)), (3,))):
@@ -485,26 +605,26 @@ class DeviceOuterStep:
         import ctypes as C
 
         from .solver import _check, _stream
-        fn = getattr(self._lib, name)
+        fn = getattr(self._lib, name + self._suffix)
         _check(self._lib, fn(self.device.index or 0, C.byref(self.model), *args, _stream(self.device)))
 
     def rollout(self, u):
         """x_1 .. x_N (B, N, 6) of the nonlinear dynamics under the controls u (B, N, 3), a CUDA tensor."""
         import torch
         x = torch.empty((self.batch, self.N, 6), dtype=torch.float64, device=self.device)
-        self._call("admm_scvx_rollout_device", self.ptr(self.x0), self.ptr(u), self.ptr(x))
+        self._call("admm_scvx_rollout", self.ptr(self.x0), self.ptr(u), self.ptr(x))
         return x
 
     def init(self, tr_u: float, tr_x: float):
         import ctypes as C
-        self._call("admm_scvx_init_device", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), float(tr_u), float(tr_x))
+        self._call("admm_scvx_init", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), float(tr_u), float(tr_x))
 
     def prepare(self):
         """The correction QPs about the current reference as a DeviceProblem over this object's tensors (rewritten by each call)."""
         import ctypes as C
 
         from .problems import DeviceProblem
-        self._call("admm_scvx_prepare_device", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), self.ptr(self.A),
+        self._call("admm_scvx_prepare", C.byref(self.params), self.ptr(self.x0), C.byref(self.state), self.ptr(self.A),
                    self.ptr(self.B), self.ptr(self.lo), self.ptr(self.hi), self.ptr(self.q))
         return DeviceProblem(N=self.N, A=self.A, B=self.B, Q=self.Qt, R=self.Rt, QN=self.QNt, x0=self.dx0, lo=self.lo, hi=self.hi,
                              q=self.q, name=f"scvx_correction_batch{self.batch}_N{self.N}")
@@ -520,7 +640,7 @@ class DeviceOuterStep:
         if tuple(z.shape) != (self.batch, self.N * 9) or z.dtype != torch.float64 or not z.is_contiguous() or z.device != self.x0.device:
             raise ValueError(f"z: expected a contiguous fp64 ({self.batch}, {self.N * 9}) tensor on {self.x0.device}")
         n_active = C.c_int32(-1)
-        self._call("admm_scvx_advance_device", C.byref(self.params), self.ptr(self.x0), self.ptr(z), C.byref(self.state),
+        self._call("admm_scvx_advance", C.byref(self.params), self.ptr(self.x0), self.ptr(z), C.byref(self.state),
                    C.byref(n_active))
         return int(n_active.value)
 

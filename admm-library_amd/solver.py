@@ -108,6 +108,15 @@ _SIGNATURES = {
                                            C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
     "admm_scvx_advance_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxModel), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
                                            C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
+    # ... with the model as an argument (ADMM_HIP_HAS_SCVX_MODELS): admm_scvx_dynamics in place of admm_scvx_model
+    "admm_scvx_model_name": (C.c_char_p, [C.c_int32]),
+    "admm_scvx_rollout_model_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxDynamics), c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_scvx_init_model_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxDynamics), C.POINTER(_abi.CScvxParams), c_double_p,
+                                              C.POINTER(_abi.CScvxState), C.c_double, C.c_double, C.c_void_p]),
+    "admm_scvx_prepare_model_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxDynamics), C.POINTER(_abi.CScvxParams), c_double_p,
+                                                 C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
+    "admm_scvx_advance_model_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxDynamics), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
+                                                 C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
     # receding-horizon step on the device (ADMM_HIP_HAS_MPC)
     "admm_mpc_advance": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p]),
     "admm_mpc_advance_device": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p, C.c_void_p]),

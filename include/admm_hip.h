@@ -386,6 +386,35 @@ int admm_scvx_prepare_device(int32_t device, const admm_scvx_model* model, const
 int admm_scvx_advance_device(int32_t device, const admm_scvx_model* model, const admm_scvx_params* params, const double* x0,
                              const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
 
+/* The model of the device outer step as an argument (new symbols, announced by ADMM_HIP_HAS_SCVX_MODELS --
+ * no struct or signature changed, ABI version unchanged).  admm_scvx_dynamics names a model compiled into the library (`kind`) and
+ * gives its parameters; n = 6, m = 3 for every kind:
+ *   ADMM_SCVX_RELATIVE_CIRCULAR  the model of admm_scvx_model: par[0] = rc
+ *   ADMM_SCVX_CRTBP              circular restricted three-body problem, nondimensional rotating frame, primaries at X = -mu and
+ *                                X = 1 - mu; s = (x, y, z, vx, vy, vz) with the position measured from (x_ref, 0, 0), u a thrust
+ *                                acceleration: par[0] = mu, par[1] = x_ref.  With X = x_ref + x, d1 = X + mu, d2 = X - 1 + mu,
+ *                                r_i = d_i^2 + y^2 + z^2, k1 = (1 - mu) / r1^(3/2), k2 = mu / r2^(3/2):
+ *                                  ax = 2 vy + X - k1 d1 - k2 d2 + ux,  ay = -2 vx + y - (k1 + k2) y + uy,  az = -(k1 + k2) z + uz
+ *                                Nothing is special near a primary: inf / NaN propagate into the cost and the candidate is rejected.
+ * Unused par entries and `reserved` are 0.  The four calls are admm_scvx_{rollout,init,prepare,advance}_device with the dynamics in
+ * place of the model: same array layouts, admm_scvx_params, admm_scvx_state, stream rules, and every check before the first HIP call
+ * and before any launch.  ADMM_ERR_INVALID names the field: dynamics.N, .batch, .substeps < 1; .dt not finite and positive; an unknown
+ * .kind; .reserved != 0; a non-zero unused .par entry; kind 0: par[0] (rc) not finite and positive; kind 1: par[0] (mu) not finite or
+ * not in (0, 1), par[1] (x_ref) not finite.  admm_scvx_model_name: "relative_circular", "crtbp"; NULL for an unknown kind. */
+#define ADMM_HIP_HAS_SCVX_MODELS 1
+enum { ADMM_SCVX_RELATIVE_CIRCULAR = 0, ADMM_SCVX_CRTBP = 1 };
+typedef struct { int32_t N, batch, substeps, kind; double dt; double par[4]; int32_t reserved; } admm_scvx_dynamics;
+const char* admm_scvx_model_name(int32_t kind);
+int admm_scvx_rollout_model_device(int32_t device, const admm_scvx_dynamics* dynamics, const double* x0, const double* u, double* x,
+                                   void* hip_stream);
+int admm_scvx_init_model_device(int32_t device, const admm_scvx_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                admm_scvx_state* state, double tr_u, double tr_x, void* hip_stream);
+int admm_scvx_prepare_model_device(int32_t device, const admm_scvx_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                   const admm_scvx_state* state, double* A, double* B, double* lo, double* hi, double* q,
+                                   void* hip_stream);
+int admm_scvx_advance_model_device(int32_t device, const admm_scvx_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                   const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
+
 /* Receding-horizon (MPC) step on the device (new symbols, announced by ADMM_HIP_HAS_MPC -- no struct or
  * signature changed): apply the first control, propagate the plant, move the window one stage.  Per QP b, in this order:
  *   1. the state is brought into the (z, y) pair and w into memory, as admm_get does
