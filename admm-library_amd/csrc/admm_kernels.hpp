@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "admm_layout.hpp"
+#include "admm_prox.hpp"
 
 namespace admm {
 
@@ -268,26 +269,6 @@ __device__ __forceinline__ void dpp_matvec_acc(const double (&v)[NREG], const do
   detail::dpp_mv_step<ROWS, COLS, NEG, OFF, 0, NREG>(v, x, acc);
 }
 
-// Thrust-magnitude (second-order-cone) projection factor of one block: the control
-// rows u of a stage with a thrust bound ub and a fuel weight f (kap = f / rho; cost term f ||u||_2)
-// are shrunk by kap, then scaled onto the ball ||u||_2 <= ub,
-//     t = min(ub, max(||u|| - kap, 0)),     c = ||u|| > t ? t / ||u|| : 1,      z_u = c u.
-// kap = 0 is the plain ball projection (t = min(ub, ||u||); ||u|| > t iff ||u|| > ub), and kap = 0 with
-// ub = +inf gives c = 1 exactly; ||u|| <= kap gives c = 0: a coast stage.  sqrt and the division are the
-// correctly rounded fp64 forms, accumulated in row order with fma -- the same operations as the CPU oracle.
-__device__ __forceinline__ double soc_factor(double nrm, double ub, double kap) {
-  const double t = fmin(ub, fmax(nrm - kap, 0.0));
-  return nrm > t ? t / nrm : 1.0;
-}
-
-template <int NU, int NB>
-__device__ __forceinline__ double soc_scale(const double (&vblk)[NB], double ub, double kap) {
-  double ss = 0.0;
-#pragma unroll
-  for (int j = 0; j < NU; ++j) ss = fma(vblk[j], vblk[j], ss);
-  return soc_factor(sqrt(ss), ub, kap);
-}
-
 // ---------------------------------------------------------------------------
 // State compression ("v-form").  After any z-update,
 //     z = clip(v, lo, hi),   y = v - z        with  v = w^ + y_old
@@ -402,9 +383,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xb_kernel(
         if (VFORM) {
           lds_block(rb + LB.LO, mLO);
           lds_block(rb + LB.HI, mHI);
-          // compiled only for problems with a thrust-magnitude bound.  Branch-free: ub = +inf (no bound at this
-          // stage) gives cs = 1 exactly, and where ub is finite the control rows' box is (-inf, inf), so
-          // clip(cs v_u) is the ball projection there and the box projection elsewhere (see xfze_kernel)
+          // compiled only for problems with a thrust-magnitude bound; branch-free (admm_prox.hpp)
           if (SOC) cs = soc_scale<NU, NB>(lz[j], rb[LB.UB], rb[LB.UB + 1]);
         }
         double g[NB];
@@ -412,7 +391,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xb_kernel(
         for (int r = 0; r < NB; ++r) {
           double zz = lz[j][r], yy;
           if (VFORM) {
-            zz = fmin(fmax((SOC && r < NU) ? lz[j][r] * cs : lz[j][r], mLO[r]), mHI[r]);
+            zz = clip((SOC && r < NU) ? lz[j][r] * cs : lz[j][r], mLO[r], mHI[r]);
             yy = lz[j][r] - zz;
           } else {
             yy = ly[j][r];
@@ -1171,28 +1150,25 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xfz_kernel(
           ADMM_LD(NU, NX, K, rn16);
         }
         const unsigned r0 = (unsigned)(k - k0) * NB * PB;
-        // thrust-magnitude bound on this stage's control rows, branch-free: ub = +inf (no bound here) gives both
-        // factors = 1 exactly; where ub is finite the control rows' box is (-inf, inf) (see xfze_kernel)
+        // thrust-magnitude bound on this stage's control rows, branch-free (admm_prox.hpp)
         double cs_old = 1.0, cs_new = 1.0;
         if constexpr (SOC) {
           const double ub = rf[LF.UB], kap = rf[LF.UB + 1];
           if (VIN) cs_old = soc_scale<NU, NB>(c0, ub, kap);
-          if (RESID) {                           // z+ needs ||v+_u||: form the control rows of v+ first
-            double vnew[NB];
+          if (RESID) {                                       // z+ needs ||v+_u||: the control rows of v+ first -- written out, see admm_prox.hpp
+            double vnu[NB];
 #pragma unroll
             for (int r = 0; r < NB; ++r) {
               if (r < NU) {
                 double zo, yo;
-                if (VIN) { zo = fmin(fmax(c0[r] * cs_old, rf[LF.LO + r]), rf[LF.HI + r]); yo = c0[r] - zo; }
+                if (VIN) { zo = clip_hi(clip_lo(c0[r] * cs_old, rf[LF.LO + r]), rf[LF.HI + r]); yo = c0[r] - zo; }
                 else { yo = c0[r]; zo = NEEDZ ? c1[r] : 0.0; }
-                double wh = wv[r];
-                if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-                vnew[r] = wh + yo;
+                vnu[r] = relaxed<RELAX>(alpha, wv[r], zo) + yo;
               } else {
-                vnew[r] = 0.0;
+                vnu[r] = 0.0;
               }
             }
-            cs_new = soc_scale<NU, NB>(vnew, ub, kap);
+            cs_new = soc_scale<NU, NB>(vnu, ub, kap);
           }
         }
 #pragma unroll
@@ -1201,29 +1177,24 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_X_OCCUPANCY void xfz_kernel(
           const bool ball = SOC && r < NU;
           double zo, yo;                       // state before this z-update
           if (VIN) {
-            zo = fmin(fmax(ball ? c0[r] * cs_old : c0[r], l), h);
+            zo = clip(ball ? c0[r] * cs_old : c0[r], l, h);
             yo = c0[r] - zo;
           } else {
             yo = c0[r];
             zo = NEEDZ ? c1[r] : 0.0;
           }
-          double wh = wv[r];
-          if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-          const double vn = wh + yo;
+          const double vn = relaxed<RELAX>(alpha, wv[r], zo) + yo;
 #ifdef ADMM_ABLATE_XFZ_STORE   // timing-only diagnostic: no v+ store (keep vn alive)
           asm volatile("" ::"v"(vn));
 #else
           if (st) vv.store(vn, lb_st, r0 + r * PB);
 #endif
           if (RESID) {
-            const double zn = fmin(fmax(ball ? vn * cs_new : vn, l), h);
+            const double zn = clip(ball ? vn * cs_new : vn, l, h);
             const double yn = vn - zn;
-            const double dr = wv[r] - zn, ds = zn - zo;
-            a_r = fma(dr, dr, a_r);
-            a_s = fma(ds, ds, a_s);
-            a_w = fma(wv[r], wv[r], a_w);
-            a_z = fma(zn, zn, a_z);
-            a_y = fma(yn, yn, a_y);
+            ResidSums t{a_r, a_s, a_w, a_z, a_y};      // (by value: five references changed this kernel's registers)
+            t.add(wv[r], zn, zo, yn);
+            a_r = t.r; a_s = t.s; a_w = t.w; a_z = t.z; a_y = t.y;
           }
           if (r % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
@@ -1253,6 +1224,55 @@ static __global__ __launch_bounds__(256) void scale_kernel(double* __restrict__ 
   }
 }
 
+// One row of two adjacent QPs, 16-byte pairs: (z, y) from v by the box, or -- the control rows of a thrust stage -- z = c v
+// without the clip (their box is (-inf, inf): admm_prox.hpp).
+struct ZY2 { double2 z, y; };
+__device__ __forceinline__ ZY2 zy2_box(double2 v, double lo, double hi) {
+  const double2 z = make_double2(clip(v.x, lo, hi), clip(v.y, lo, hi));
+  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
+}
+// ... with the bounds of row r still in memory: each read between the two halves of the clip, as the read-out kernels always did
+template <class P>
+__device__ __forceinline__ ZY2 zy2_box(double2 v, P lo, P hi, int r) {
+  const double2 z = make_double2(clip_hi(clip_lo(v.x, lo[r]), hi[r]), clip_hi(clip_lo(v.y, lo[r]), hi[r]));
+  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
+}
+__device__ __forceinline__ ZY2 zy2_scaled(double2 v, double2 c) {
+  const double2 z = make_double2(v.x * c.x, v.y * c.y);
+  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
+}
+__device__ __forceinline__ void zy2_store(const ZY2& p, double* z, double* y, size_t o = 0) {
+  *reinterpret_cast<double2*>(z + o) = p.z;
+  *reinterpret_cast<double2*>(y + o) = p.y;
+}
+
+// v+ = w^ + y of one row of two adjacent QPs, from the loaded (z, y)
+template <bool RELAX>
+__device__ __forceinline__ double2 v_plus2(double alpha, double2 w, double2 z, double2 y) {
+  return make_double2(relaxed<RELAX>(alpha, w.x, z.x) + y.x, relaxed<RELAX>(alpha, w.y, z.y) + y.y);
+}
+
+// One row of the unfused z-update for two adjacent QPs, in place: (z, y) <- z-update of (w, z, y); acc: the sums of either QP
+template <bool RESID, bool RELAX>
+__device__ __forceinline__ void zdual_row(double2 wv, double2 zv, double2 yv, bool scaled, double2 c, double lo, double hi,
+                                          double alpha, double* z, double* y, ResidSums (&acc)[2]) {
+  const double2 v = v_plus2<RELAX>(alpha, wv, zv, yv);
+  const ZY2 p = scaled ? zy2_scaled(v, c) : zy2_box(v, lo, hi);
+  zy2_store(p, z, y);
+  if (RESID) {
+    acc[0].add(wv.x, p.z.x, zv.x, p.y.x);
+    acc[1].add(wv.y, p.z.y, zv.y, p.y.y);
+  }
+}
+
+__device__ __forceinline__ void store_sums2(double* part, size_t P, const ResidSums (&acc)[2]) {
+  *reinterpret_cast<double2*>(part + 0 * P) = make_double2(acc[0].r, acc[1].r);
+  *reinterpret_cast<double2*>(part + 1 * P) = make_double2(acc[0].s, acc[1].s);
+  *reinterpret_cast<double2*>(part + 2 * P) = make_double2(acc[0].w, acc[1].w);
+  *reinterpret_cast<double2*>(part + 3 * P) = make_double2(acc[0].z, acc[1].z);
+  *reinterpret_cast<double2*>(part + 4 * P) = make_double2(acc[0].y, acc[1].y);
+}
+
 // v -> (z, y): z = clip(v), y = v - z.  Read-out / mode switches only.  One lane =
 // two adjacent QPs, blockIdx.y = row chunk (same geometry as zdual_kernel).
 static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_kernel(
@@ -1273,25 +1293,13 @@ static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_kernel(
 #pragma unroll
     for (int i = 0; i < U; ++i) {
       const size_t o = (size_t)(r + i) * pitch + col;
-      double2 zz, yy;
-      zz.x = fmin(fmax(vv[i].x, lo[r + i]), hi[r + i]);
-      zz.y = fmin(fmax(vv[i].y, lo[r + i]), hi[r + i]);
-      yy.x = vv[i].x - zz.x;
-      yy.y = vv[i].y - zz.y;
-      *reinterpret_cast<double2*>(z + o) = zz;
-      *reinterpret_cast<double2*>(y + o) = yy;
+      zy2_store(zy2_box(vv[i], lo, hi, r + i), z, y, o);
     }
   }
   for (; r < r_end; ++r) {
     const size_t o = (size_t)r * pitch + col;
     const double2 vv = *reinterpret_cast<const double2*>(v + o);
-    double2 zz, yy;
-    zz.x = fmin(fmax(vv.x, lo[r]), hi[r]);
-    zz.y = fmin(fmax(vv.y, lo[r]), hi[r]);
-    yy.x = vv.x - zz.x;
-    yy.y = vv.y - zz.y;
-    *reinterpret_cast<double2*>(z + o) = zz;
-    *reinterpret_cast<double2*>(y + o) = yy;
+    zy2_store(zy2_box(vv, lo, hi, r), z, y, o);
   }
 }
 
@@ -1324,7 +1332,7 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
   const size_t P = (size_t)pitch;
   cdouble_p lo = as_const(lo_);
   cdouble_p hi = as_const(hi_);
-  double2 a_r = {0, 0}, a_s = {0, 0}, a_w = {0, 0}, a_z = {0, 0}, a_y = {0, 0};
+  ResidSums acc[2];
 #ifndef ADMM_Z_UNROLL
 #define ADMM_Z_UNROLL 4
 #endif
@@ -1341,35 +1349,13 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
       wv[i] = *reinterpret_cast<const double2*>(w + o);
 #endif
       yv[i] = *reinterpret_cast<const double2*>(y + o);
+      zv[i] = make_double2(0.0, 0.0);
       if (RESID || RELAX) zv[i] = *reinterpret_cast<const double2*>(z + o);
     }
 #pragma unroll
     for (int i = 0; i < U; ++i) {
       const size_t o = (size_t)(r + i) * P + col;
-      const double l = lo[r + i], h = hi[r + i];
-      double2 wh = wv[i];
-      if (RELAX) {
-        wh.x = fma(alpha, wv[i].x, (1.0 - alpha) * zv[i].x);
-        wh.y = fma(alpha, wv[i].y, (1.0 - alpha) * zv[i].y);
-      }
-      double2 v, zn, yn;
-      v.x = wh.x + yv[i].x;
-      v.y = wh.y + yv[i].y;
-      zn.x = fmin(fmax(v.x, l), h);
-      zn.y = fmin(fmax(v.y, l), h);
-      yn.x = v.x - zn.x;
-      yn.y = v.y - zn.y;
-      *reinterpret_cast<double2*>(z + o) = zn;
-      *reinterpret_cast<double2*>(y + o) = yn;
-      if (RESID) {
-        double dx = wv[i].x - zn.x, dy = wv[i].y - zn.y;
-        a_r.x = fma(dx, dx, a_r.x); a_r.y = fma(dy, dy, a_r.y);
-        dx = zn.x - zv[i].x; dy = zn.y - zv[i].y;
-        a_s.x = fma(dx, dx, a_s.x); a_s.y = fma(dy, dy, a_s.y);
-        a_w.x = fma(wv[i].x, wv[i].x, a_w.x); a_w.y = fma(wv[i].y, wv[i].y, a_w.y);
-        a_z.x = fma(zn.x, zn.x, a_z.x); a_z.y = fma(zn.y, zn.y, a_z.y);
-        a_y.x = fma(yn.x, yn.x, a_y.x); a_y.y = fma(yn.y, yn.y, a_y.y);
-      }
+      zdual_row<RESID, RELAX>(wv[i], zv[i], yv[i], false, wv[i], lo[r + i], hi[r + i], alpha, z + o, y + o, acc);
     }
   }
   for (; r < r_end; ++r) {
@@ -1378,39 +1364,9 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
     const double2 yv = *reinterpret_cast<const double2*>(y + o);
     double2 zv = {0, 0};
     if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-    const double l = lo[r], h = hi[r];
-    double2 wh = wv;
-    if (RELAX) {
-      wh.x = fma(alpha, wv.x, (1.0 - alpha) * zv.x);
-      wh.y = fma(alpha, wv.y, (1.0 - alpha) * zv.y);
-    }
-    double2 v, zn, yn;
-    v.x = wh.x + yv.x;
-    v.y = wh.y + yv.y;
-    zn.x = fmin(fmax(v.x, l), h);
-    zn.y = fmin(fmax(v.y, l), h);
-    yn.x = v.x - zn.x;
-    yn.y = v.y - zn.y;
-    *reinterpret_cast<double2*>(z + o) = zn;
-    *reinterpret_cast<double2*>(y + o) = yn;
-    if (RESID) {
-      double dx = wv.x - zn.x, dy = wv.y - zn.y;
-      a_r.x = fma(dx, dx, a_r.x); a_r.y = fma(dy, dy, a_r.y);
-      dx = zn.x - zv.x; dy = zn.y - zv.y;
-      a_s.x = fma(dx, dx, a_s.x); a_s.y = fma(dy, dy, a_s.y);
-      a_w.x = fma(wv.x, wv.x, a_w.x); a_w.y = fma(wv.y, wv.y, a_w.y);
-      a_z.x = fma(zn.x, zn.x, a_z.x); a_z.y = fma(zn.y, zn.y, a_z.y);
-      a_y.x = fma(yn.x, yn.x, a_y.x); a_y.y = fma(yn.y, yn.y, a_y.y);
-    }
+    zdual_row<RESID, RELAX>(wv, zv, yv, false, wv, lo[r], hi[r], alpha, z + o, y + o, acc);
   }
-  if (RESID) {
-    const size_t o = (size_t)chunk * 5 * P + col;
-    *reinterpret_cast<double2*>(part + o + 0 * P) = a_r;
-    *reinterpret_cast<double2*>(part + o + 1 * P) = a_s;
-    *reinterpret_cast<double2*>(part + o + 2 * P) = a_w;
-    *reinterpret_cast<double2*>(part + o + 3 * P) = a_z;
-    *reinterpret_cast<double2*>(part + o + 4 * P) = a_y;
-  }
+  if (RESID) store_sums2(part + (size_t)chunk * 5 * P + col, P, acc);
 }
 
 // ---------------------------------------------------------------------------
@@ -1421,10 +1377,7 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
 // read-out only; the fused xfz / xb kernels do the same work on register-resident blocks.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double2 soc_scale2(double2 ss, double ub, double kap) {
-  double2 c;
-  c.x = soc_factor(sqrt(ss.x), ub, kap);
-  c.y = soc_factor(sqrt(ss.y), ub, kap);
-  return c;
+  return make_double2(soc_factor(sqrt(ss.x), ub, kap), soc_factor(sqrt(ss.y), ub, kap));
 }
 
 template <bool RESID, bool RELAX>
@@ -1442,7 +1395,7 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
   cdouble_p hi = as_const(hi_);
   cdouble_p ubv = as_const(ub_);
   cdouble_p kapv = as_const(kap_);
-  double2 a_r = {0, 0}, a_s = {0, 0}, a_w = {0, 0}, a_z = {0, 0}, a_y = {0, 0};
+  ResidSums acc[2];
   for (int rb = r_begin; rb < r_end; rb += nb) {
     const double ub = ubv[rb / nb], kap = kapv[rb / nb];
     const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their box)
@@ -1453,15 +1406,11 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
         const size_t o = (size_t)(rb + j) * P + col;
         const double2 wv = *reinterpret_cast<const double2*>(w + o);
         const double2 yv = *reinterpret_cast<const double2*>(y + o);
-        double2 wh = wv;
-        if (RELAX) {
-          const double2 zv = *reinterpret_cast<const double2*>(z + o);
-          wh.x = fma(alpha, wv.x, (1.0 - alpha) * zv.x);
-          wh.y = fma(alpha, wv.y, (1.0 - alpha) * zv.y);
-        }
-        const double vx = wh.x + yv.x, vy = wh.y + yv.y;
-        ss.x = fma(vx, vx, ss.x);
-        ss.y = fma(vy, vy, ss.y);
+        double2 zv = {0, 0};
+        if (RELAX) zv = *reinterpret_cast<const double2*>(z + o);
+        const double2 vn = v_plus2<RELAX>(alpha, wv, zv, yv);
+        ss.x = fma(vn.x, vn.x, ss.x);
+        ss.y = fma(vn.y, vn.y, ss.y);
       }
       cs = soc_scale2(ss, ub, kap);
     }
@@ -1472,45 +1421,10 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
       const double2 yv = *reinterpret_cast<const double2*>(y + o);
       double2 zv = {0, 0};
       if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-      const double l = lo[row], h = hi[row];
-      double2 wh = wv;
-      if (RELAX) {
-        wh.x = fma(alpha, wv.x, (1.0 - alpha) * zv.x);
-        wh.y = fma(alpha, wv.y, (1.0 - alpha) * zv.y);
-      }
-      double2 v, zn, yn;
-      v.x = wh.x + yv.x;
-      v.y = wh.y + yv.y;
-      if (soc && r < m) {
-        zn.x = v.x * cs.x;
-        zn.y = v.y * cs.y;
-      } else {
-        zn.x = fmin(fmax(v.x, l), h);
-        zn.y = fmin(fmax(v.y, l), h);
-      }
-      yn.x = v.x - zn.x;
-      yn.y = v.y - zn.y;
-      *reinterpret_cast<double2*>(z + o) = zn;
-      *reinterpret_cast<double2*>(y + o) = yn;
-      if (RESID) {
-        double dx = wv.x - zn.x, dy = wv.y - zn.y;
-        a_r.x = fma(dx, dx, a_r.x); a_r.y = fma(dy, dy, a_r.y);
-        dx = zn.x - zv.x; dy = zn.y - zv.y;
-        a_s.x = fma(dx, dx, a_s.x); a_s.y = fma(dy, dy, a_s.y);
-        a_w.x = fma(wv.x, wv.x, a_w.x); a_w.y = fma(wv.y, wv.y, a_w.y);
-        a_z.x = fma(zn.x, zn.x, a_z.x); a_z.y = fma(zn.y, zn.y, a_z.y);
-        a_y.x = fma(yn.x, yn.x, a_y.x); a_y.y = fma(yn.y, yn.y, a_y.y);
-      }
+      zdual_row<RESID, RELAX>(wv, zv, yv, soc && r < m, cs, lo[row], hi[row], alpha, z + o, y + o, acc);
     }
   }
-  if (RESID) {
-    const size_t o = (size_t)chunk * 5 * P + col;
-    *reinterpret_cast<double2*>(part + o + 0 * P) = a_r;
-    *reinterpret_cast<double2*>(part + o + 1 * P) = a_s;
-    *reinterpret_cast<double2*>(part + o + 2 * P) = a_w;
-    *reinterpret_cast<double2*>(part + o + 3 * P) = a_z;
-    *reinterpret_cast<double2*>(part + o + 4 * P) = a_y;
-  }
+  if (RESID) store_sums2(part + (size_t)chunk * 5 * P + col, P, acc);
 }
 
 static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
@@ -1542,18 +1456,8 @@ static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
       const int row = rb + r;
       const size_t o = (size_t)row * pitch + col;
       const double2 vv = *reinterpret_cast<const double2*>(v + o);
-      double2 zz, yy;
-      if (soc && r < m) {
-        zz.x = vv.x * cs.x;
-        zz.y = vv.y * cs.y;
-      } else {
-        zz.x = fmin(fmax(vv.x, lo[row]), hi[row]);
-        zz.y = fmin(fmax(vv.y, lo[row]), hi[row]);
-      }
-      yy.x = vv.x - zz.x;
-      yy.y = vv.y - zz.y;
-      *reinterpret_cast<double2*>(z + o) = zz;
-      *reinterpret_cast<double2*>(y + o) = yy;
+      if (soc && r < m) zy2_store(zy2_scaled(vv, cs), z, y, o);
+      else zy2_store(zy2_box(vv, lo, hi, row), z, y, o);
     }
   }
 }

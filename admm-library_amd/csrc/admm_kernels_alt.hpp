@@ -311,30 +311,25 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           lds_block(rf + LF.HI, mHI);
         }
         const unsigned r0 = (unsigned)(k - k0) * NB * PB;
-        // thrust-magnitude bound on this stage's control rows (SOC forms only): the two
-        // ball-projection factors, of the old state and of v+.  BRANCH-FREE: a stage without the bound carries
-        // ub = +inf, for which both factors are exactly 1 (norm > inf is false), and where the bound is finite the
-        // box of the control rows is (-inf, inf) (validated at setup), so  z_u = clip(c v_u, lo, hi)  is the ball
-        // projection in the one case and the box projection in the other, bit for bit.  (The first version branched
-        // on the wave-uniform `ub < inf`: every row of the block then stayed live across the branch and the two
-        // sqrt / division sequences inside it, and the kernels went to scratch at most shapes.)
+        // thrust-magnitude bound on this stage's control rows (SOC forms only): the two projection
+        // factors, of the old state and of v+, branch-free (admm_prox.hpp)
         double cs_old = 1.0, cs_new = 1.0;
         if constexpr (SOC) {
           const double ub = rf[LF.UB], kap = rf[LF.UB + 1];      // kap = fuel weight / rho (0: none)
           cs_old = soc_scale<NU, NB>(c0, ub, kap);
-          double vnu[NB];
+          {                                       // z+ needs ||v+_u||: the control rows of v+ first -- written out, see admm_prox.hpp
+            double vnu[NB];
 #pragma unroll
-          for (int r = 0; r < NB; ++r) {
-            if (r < NU) {
-              const double zo = fmin(fmax(c0[r] * cs_old, rf[LF.LO + r]), rf[LF.HI + r]), yo = c0[r] - zo;
-              double wh = wv[r];
-              if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-              vnu[r] = wh + yo;
-            } else {
-              vnu[r] = 0.0;
+            for (int r = 0; r < NB; ++r) {
+              if (r < NU) {
+                const double zo = clip_hi(clip_lo(c0[r] * cs_old, rf[LF.LO + r]), rf[LF.HI + r]), yo = c0[r] - zo;
+                vnu[r] = relaxed<RELAX>(alpha, wv[r], zo) + yo;
+              } else {
+                vnu[r] = 0.0;
+              }
             }
+            cs_new = soc_scale<NU, NB>(vnu, ub, kap);
           }
-          cs_new = soc_scale<NU, NB>(vnu, ub, kap);
         }
 #pragma unroll
         for (int r = 0; r < NB; ++r) {
@@ -357,25 +352,20 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
           }
           const bool ball = SOC && r < NU;
           const double lo_r = SOC ? rf[LF.LO + r] : mLO[SOC ? 0 : r], hi_r = SOC ? rf[LF.HI + r] : mHI[SOC ? 0 : r];
-          const double zo = fmin(fmax(ball ? c0[r] * cs_old : c0[r], lo_r), hi_r);
+          const double zo = clip(ball ? c0[r] * cs_old : c0[r], lo_r, hi_r);
           const double yo = c0[r] - zo;
-          double wh = wv[r];
-          if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-          const double vn = wh + yo;
+          const double vn = relaxed<RELAX>(alpha, wv[r], zo) + yo;
           if (!(XFREE == 2 && r >= NU))      // XFREE = 2: the next iteration does not read these rows either
             vv.store<ADMM_ALT_STORE_AUX>(vn, lb_st, r0 + r * PB);
           if (L_SD && r < NU) vw.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, (unsigned)(k - k0) * NU * PB + r * PB);
-          const double zn = fmin(fmax(ball ? vn * cs_new : vn, lo_r), hi_r);
+          const double zn = clip(ball ? vn * cs_new : vn, lo_r, hi_r);
           const double yn = vn - zn;
           g[r] = -rho * (zn - yn);
           if (HASQ) g[r] += cq[r];
           if (RESID) {
-            const double dr = wv[r] - zn, ds = zn - zo;
-            a_r = fma(dr, dr, a_r);
-            a_s = fma(ds, ds, a_s);
-            a_w = fma(wv[r], wv[r], a_w);
-            a_z = fma(zn, zn, a_z);
-            a_y = fma(yn, yn, a_y);
+            ResidSums t{a_r, a_s, a_w, a_z, a_y};      // (by value: five references changed this kernel's registers)
+            t.add(wv[r], zn, zo, yn);
+            a_r = t.r; a_s = t.s; a_w = t.w; a_z = t.z; a_y = t.y;
           }
           if (r % 3 == 2) __builtin_amdgcn_sched_barrier(0);
         }
@@ -627,23 +617,23 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         // ---- z-update, dual ascent, residual partials ----
         double g[NB];
         const unsigned r0 = (unsigned)SIDX(k) * NB * PB;
-        double cs_old = 1.0, cs_new = 1.0;     // thrust-magnitude bound, branch-free (see xfze_kernel)
+        double cs_old = 1.0, cs_new = 1.0;     // thrust-magnitude bound, branch-free (admm_prox.hpp)
         if constexpr (SOC) {
           const double ub = rb[LB.UB], kap = rb[LB.UB + 1];
           cs_old = soc_scale<NU, NB>(c0, ub, kap);
-          double vnu[NB];
+          {                                       // z+ needs ||v+_u||: the control rows of v+ first -- written out, see admm_prox.hpp
+            double vnu[NB];
 #pragma unroll
-          for (int r = 0; r < NB; ++r) {
-            if (r < NU) {
-              const double zo = fmin(fmax(c0[r] * cs_old, rb[LB.LO + r]), rb[LB.HI + r]), yo = c0[r] - zo;
-              double wh = wv[r];
-              if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-              vnu[r] = wh + yo;
-            } else {
-              vnu[r] = 0.0;
+            for (int r = 0; r < NB; ++r) {
+              if (r < NU) {
+                const double zo = clip_hi(clip_lo(c0[r] * cs_old, rb[LB.LO + r]), rb[LB.HI + r]), yo = c0[r] - zo;
+                vnu[r] = relaxed<RELAX>(alpha, wv[r], zo) + yo;
+              } else {
+                vnu[r] = 0.0;
+              }
             }
+            cs_new = soc_scale<NU, NB>(vnu, ub, kap);
           }
-          cs_new = soc_scale<NU, NB>(vnu, ub, kap);
         }
 #pragma unroll
         for (int r3 = 0; r3 < NB; r3 += 3) {
@@ -665,25 +655,20 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
             }
             const bool ball = SOC && r < NU;
             const double lo = rb[LB.LO + r], hi = rb[LB.HI + r];
-            const double zo = fmin(fmax(ball ? c0[r] * cs_old : c0[r], lo), hi);
+            const double zo = clip(ball ? c0[r] * cs_old : c0[r], lo, hi);
             const double yo = c0[r] - zo;
-            double wh = wv[r];
-            if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-            const double vn = wh + yo;
+            const double vn = relaxed<RELAX>(alpha, wv[r], zo) + yo;
             if (!(XFREE == 2 && r >= NU))
               vv.store<ADMM_ALT_STORE_AUX>(vn, lb_st, r0 + r * PB);
             if (L_SD && r < NU) vw.store<ADMM_ALT_STORE_AUX>(wv[r], lb_st, (unsigned)SIDX(k) * NU * PB + r * PB);
-            const double zn = fmin(fmax(ball ? vn * cs_new : vn, lo), hi);
+            const double zn = clip(ball ? vn * cs_new : vn, lo, hi);
             const double yn = vn - zn;
             g[r] = -rho * (zn - yn);
             if (HASQ) g[r] += cq[r];
             if (RESID) {
-              const double dr = wv[r] - zn, ds = zn - zo;
-              a_r = fma(dr, dr, a_r);
-              a_s = fma(ds, ds, a_s);
-              a_w = fma(wv[r], wv[r], a_w);
-              a_z = fma(zn, zn, a_z);
-              a_y = fma(yn, yn, a_y);
+              ResidSums t{a_r, a_s, a_w, a_z, a_y};      // (by value: five references changed this kernel's registers)
+              t.add(wv[r], zn, zo, yn);
+              a_r = t.r; a_s = t.s; a_w = t.w; a_z = t.z; a_y = t.y;
             }
           }
           __builtin_amdgcn_sched_barrier(0);

@@ -103,22 +103,13 @@ __device__ __forceinline__ void glds_retire() { asm volatile("s_waitcnt vmcnt(0)
 template <bool RESID, bool RELAX>
 __device__ __forceinline__ void mf_zupdate(double c0, double w, double lo, double hi, double alpha, double rho,
                                            double& vn, double& gg, double (&acc)[5]) {
-  const double zo = fmin(fmax(c0, lo), hi);
+  const double zo = clip(c0, lo, hi);
   const double yo = c0 - zo;
-  double wh = w;
-  if (RELAX) wh = fma(alpha, w, (1.0 - alpha) * zo);
-  vn = wh + yo;
-  const double zn = fmin(fmax(vn, lo), hi);
+  vn = relaxed<RELAX>(alpha, w, zo) + yo;
+  const double zn = clip(vn, lo, hi);
   const double yn = vn - zn;
   gg = -rho * (zn - yn);
-  if (RESID) {
-    const double dr = w - zn, ds = zn - zo;
-    acc[0] = fma(dr, dr, acc[0]);
-    acc[1] = fma(ds, ds, acc[1]);
-    acc[2] = fma(w, w, acc[2]);
-    acc[3] = fma(zn, zn, acc[3]);
-    acc[4] = fma(yn, yn, acc[4]);
-  }
+  if (RESID) ResidSums::add(acc, w, zn, zo, yn);
 }
 
 // One row of the scan output; the common case of one slab (every batch that fills the chip) takes ONE load instead of
@@ -627,7 +618,7 @@ __global__ __launch_bounds__(MF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
           for (int q = 0; q < 5; ++q) {
             const int slot = q * 4 + g;
-            const double zz = fmin(fmax(c0[nt][q], lohi[slot]), lohi[20 + slot]);
+            const double zz = clip_hi(clip_lo(c0[nt][q], lohi[slot]), lohi[20 + slot]);
             gg[nt][q] = ((q < NR || q == 3) || (q == 4 && XT)) ? -rho * (zz - (c0[nt][q] - zz)) : 0.0;
           }
       }

@@ -27,6 +27,8 @@
 
 #include <cstddef>
 
+#include "admm_prox.hpp"
+
 namespace admm {
 
 constexpr int PI_THREADS = 64;      // one wave per workgroup: small batches still spread over the CUs
@@ -198,18 +200,6 @@ __global__ __launch_bounds__(PI_THREADS) void pfactor_kernel(
   }
 }
 
-// Thrust-magnitude bound ||u_k||_2 <= ub_k on the control rows of a block: the factor c with z_u = c v_u.
-// sqrt and the division are the correctly rounded fp64 forms, accumulated in row order with fma -- the oracle's operations.
-// ub = +inf (no bound at this stage) gives exactly 1.
-template <int NU, int NB>
-__device__ __forceinline__ double pi_soc_scale(const double (&vblk)[NB], double ub) {
-  double ss = 0.0;
-#pragma unroll
-  for (int j = 0; j < NU; ++j) ss = fma(vblk[j], vblk[j], ss);
-  const double nrm = sqrt(ss);
-  return nrm > ub ? ub / nrm : 1.0;
-}
-
 // ---------------------------------------------------------------------------
 // Stage operands of one QP, fetched as ONE batch of independent loads (the first version read each operand where it
 // was used: ~100 dependent round trips per stage, 18-30 us per stage; batched: one round trip).  The sweeps keep TWO of
@@ -290,12 +280,12 @@ __global__ __launch_bounds__(PI_THREADS) void pxb_kernel(
   auto body = [&](const Stage& s, int k) {
     double g[NB];
     double cs = 1.0;                               // thrust-magnitude bound of this stage (branch-free: +inf -> 1)
-    if constexpr (SOC) cs = pi_soc_scale<NU, NB>(s.s0, ubd[k]);
+    if constexpr (SOC) cs = ball_scale<NU, NB>(s.s0, ubd[k]);
 #pragma unroll
     for (int r = 0; r < NB; ++r) {
       double zz = s.s0[r], yy;
       if (VFORM) {
-        zz = fmin(fmax((SOC && r < NU) ? s.s0[r] * cs : s.s0[r], s.lo[r]), s.hi[r]);
+        zz = clip((SOC && r < NU) ? s.s0[r] * cs : s.s0[r], s.lo[r], s.hi[r]);
         yy = s.s0[r] - zz;
       } else {
         yy = s.s1[r];
@@ -419,23 +409,21 @@ __global__ __launch_bounds__(PI_THREADS) void pxfz_kernel(
     double cs_old = 1.0, cs_new = 1.0;
     if constexpr (SOC) {
       const double ub = ubd[k];
-      if (VIN) cs_old = pi_soc_scale<NU, NB>(s.s0, ub);
-      if (RESID) {                                  // z+ needs ||v+_u||: the control rows of v+ first
-        double vnew[NB];
+      if (VIN) cs_old = ball_scale<NU, NB>(s.s0, ub);
+      if (RESID) {                                       // z+ needs ||v+_u||: the control rows of v+ first -- written out, see admm_prox.hpp
+        double vnu[NB];
 #pragma unroll
         for (int r = 0; r < NB; ++r) {
           if (r < NU) {
             double zo, yo;
-            if (VIN) { zo = fmin(fmax(s.s0[r] * cs_old, s.lo[r]), s.hi[r]); yo = s.s0[r] - zo; }
+            if (VIN) { zo = clip_hi(clip_lo(s.s0[r] * cs_old, s.lo[r]), s.hi[r]); yo = s.s0[r] - zo; }
             else { yo = s.s0[r]; zo = NEEDZ ? s.s1[NEEDZ ? r : 0] : 0.0; }
-            double wh = wv[r];
-            if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-            vnew[r] = wh + yo;
+            vnu[r] = relaxed<RELAX>(alpha, wv[r], zo) + yo;
           } else {
-            vnew[r] = 0.0;
+            vnu[r] = 0.0;
           }
         }
-        cs_new = pi_soc_scale<NU, NB>(vnew, ub);
+        cs_new = ball_scale<NU, NB>(vnu, ub);
       }
     }
 #pragma unroll
@@ -446,25 +434,18 @@ __global__ __launch_bounds__(PI_THREADS) void pxfz_kernel(
       if (ZUP) {
         double zo, yo;
         if (VIN) {
-          zo = fmin(fmax(ball ? s.s0[r] * cs_old : s.s0[r], s.lo[r]), s.hi[r]);
+          zo = clip(ball ? s.s0[r] * cs_old : s.s0[r], s.lo[r], s.hi[r]);
           yo = s.s0[r] - zo;
         } else {
           yo = s.s0[r];
           zo = NEEDZ ? s.s1[NEEDZ ? r : 0] : 0.0;
         }
-        double wh = wv[r];
-        if (RELAX) wh = fma(alpha, wv[r], (1.0 - alpha) * zo);
-        const double vn = wh + yo;
+        const double vn = relaxed<RELAX>(alpha, wv[r], zo) + yo;
         v[o] = vn;
         if (RESID) {
-          const double zn = fmin(fmax(ball ? vn * cs_new : vn, s.lo[r]), s.hi[r]);
+          const double zn = clip(ball ? vn * cs_new : vn, s.lo[r], s.hi[r]);
           const double yn = vn - zn;
-          const double dr = wv[r] - zn, ds = zn - zo;
-          a_r = fma(dr, dr, a_r);
-          a_s = fma(ds, ds, a_s);
-          a_w = fma(wv[r], wv[r], a_w);
-          a_z = fma(zn, zn, a_z);
-          a_y = fma(yn, yn, a_y);
+          ResidSums::add(a_r, a_s, a_w, a_z, a_y, wv[r], zn, zo, yn);
         }
       }
     }
@@ -902,12 +883,11 @@ static __global__ __launch_bounds__(256) void pv_to_zy_soc_kernel(const double* 
     const size_t base = (size_t)k * nb * pitch + col;
     double ss = 0.0;
     for (int j = 0; j < m; ++j) { const double vu = v[base + (size_t)j * pitch]; ss = fma(vu, vu, ss); }
-    const double nrm = sqrt(ss), ubk = ub[k];
-    const double cs = nrm > ubk ? ubk / nrm : 1.0;
+    const double cs = ball_factor(sqrt(ss), ub[k]);
     for (int r = 0; r < nb; ++r) {
       const size_t o = base + (size_t)r * pitch;
       const double vv = v[o];
-      const double zz = fmin(fmax(r < m ? vv * cs : vv, lo[o]), hi[o]);
+      const double zz = clip_hi(clip_lo(r < m ? vv * cs : vv, lo[o]), hi[o]);
       z[o] = zz;
       y[o] = vv - zz;
     }
@@ -919,7 +899,7 @@ static __global__ __launch_bounds__(256) void pv_to_zy_kernel(const double* __re
                                                               const double* __restrict__ hi, size_t count) {
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256) {
     const double vv = v[i];
-    const double zz = fmin(fmax(vv, lo[i]), hi[i]);
+    const double zz = clip_hi(clip_lo(vv, lo[i]), hi[i]);
     z[i] = zz;
     y[i] = vv - zz;
   }

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(PROWS_BLOCK) void pxb_rows_kernel(
   // `pre`: the value that is clipped -- s0, or s0 scaled onto the thrust-magnitude ball (control rows, SOC)
   auto gterm = [&](double s0, double pre, double s1, double lo_, double hi_, double qv) {
     double zz = s0, yy;
-    if (VFORM) { zz = fmin(fmax(pre, lo_), hi_); yy = s0 - zz; } else { yy = s1; }
+    if (VFORM) { zz = clip(pre, lo_, hi_); yy = s0 - zz; } else { yy = s1; }
     double g = -rho * (zz - yy);
     if (HASQ) g += qv;
     return g;
@@ -94,8 +94,7 @@ __global__ __launch_bounds__(PROWS_BLOCK) void pxb_rows_kernel(
       double ss = 0.0;
 #pragma unroll
       for (int l = 0; l < NU; ++l) { const double vu = across(o.u0, l); ss = fma(vu, vu, ss); }
-      const double nrm = sqrt(ss), ub = ubd[k];
-      cs = nrm > ub ? ub / nrm : 1.0;
+      cs = ball_factor(sqrt(ss), ubd[k]);
     }
     const double gx = gterm(o.x0, o.x0, o.x1, TB_ ? m.lox : o.lox, TB_ ? m.hix : o.hix, o.qx);
     const double gu = gterm(o.u0, SOC ? o.u0 * cs : o.u0, o.u1, TB_ ? m.lou : o.lou, TB_ ? m.hiu : o.hiu, o.qu);
@@ -317,21 +316,14 @@ __global__ __launch_bounds__(PROWS_BLOCK) void pxfz_rows_kernel(
     if (STOREW && store) w[o] = wv;
     if (ZUP) {
       double zo, yo;
-      if (VIN) { zo = fmin(fmax(SOC ? s0 * cs_old : s0, lo_), hi_); yo = s0 - zo; }
+      if (VIN) { zo = clip(SOC ? s0 * cs_old : s0, lo_, hi_); yo = s0 - zo; }
       else { yo = s0; zo = NEEDZ ? s1 : 0.0; }
-      double wh = wv;
-      if (RELAX) wh = fma(alpha, wv, (1.0 - alpha) * zo);
-      const double vn = wh + yo;
+      const double vn = relaxed<RELAX>(alpha, wv, zo) + yo;
       if (store) v[o] = vn;
       if (RESID && store) {
-        const double zn = fmin(fmax(SOC ? vn * cs_new : vn, lo_), hi_);
+        const double zn = clip(SOC ? vn * cs_new : vn, lo_, hi_);
         const double yn = vn - zn;
-        const double dr = wv - zn, ds = zn - zo;
-        acc[0] = fma(dr, dr, acc[0]);
-        acc[1] = fma(ds, ds, acc[1]);
-        acc[2] = fma(wv, wv, acc[2]);
-        acc[3] = fma(zn, zn, acc[3]);
-        acc[4] = fma(yn, yn, acc[4]);
+        ResidSums::add(acc, wv, zn, zo, yn);
       }
     }
   };
@@ -366,21 +358,17 @@ __global__ __launch_bounds__(PROWS_BLOCK) void pxfz_rows_kernel(
         double ss = 0.0;
 #pragma unroll
         for (int l = 0; l < NU; ++l) { const double vu = across(o.u0, l); ss = fma(vu, vu, ss); }
-        const double nrm = sqrt(ss);
-        cs_old = nrm > ub ? ub / nrm : 1.0;
+        cs_old = ball_factor(sqrt(ss), ub);
       }
       if (RESID) {                                  // z+ needs ||v+_u||: this lane's control row of v+ first
         double zo, yo;
-        if (VIN) { zo = fmin(fmax(o.u0 * cs_old, lou_), hiu_); yo = o.u0 - zo; }
+        if (VIN) { zo = clip(o.u0 * cs_old, lou_, hiu_); yo = o.u0 - zo; }
         else { yo = o.u0; zo = NEEDZ ? o.u1 : 0.0; }
-        double wh = wu;
-        if (RELAX) wh = fma(alpha, wu, (1.0 - alpha) * zo);
-        const double vnu = wh + yo;
+        const double vnu = relaxed<RELAX>(alpha, wu, zo) + yo;
         double ss = 0.0;
 #pragma unroll
         for (int l = 0; l < NU; ++l) { const double vu = across(vnu, l); ss = fma(vu, vu, ss); }
-        const double nrm = sqrt(ss);
-        cs_new = nrm > ub ? ub / nrm : 1.0;
+        cs_new = ball_factor(sqrt(ss), ub);
       }
     }
     zrow(wu, o.u0, o.u1, lou_, hiu_, ou, valid && live_u, accu, cs_old, cs_new);

@@ -1,0 +1,98 @@
+// The z-update of DESIGN.md §2.3 / §2.7, written once: every kernel family (admm_kernels.hpp, admm_kernels_alt.hpp,
+// admm_mfma.hpp, admm_pinst.hpp, admm_pinst_rows.hpp) composes its rows from the functions below, so the iterates agree to
+// the last bit across families and the v-form (§4.5) can rebuild (z, y) from v with the very operations that produced them.
+// Arithmetic only: loads, stores, prefetch and scheduling stay with the kernels.  Callable on the host as well (plain
+// inline functions without hipcc), which is how tests/test_prox_host.py pins this one definition without a GPU.
+//
+// One z-update of a row, from the old state (zo, yo), the x-update's w and the relaxation parameter alpha:
+//     w^  = RELAX ? fma(alpha, w, (1 - alpha) zo) : w
+//     v+  = w^ + yo
+//     zn  = clip(c' v+, lo, hi),   yn = v+ - zn            (c' = 1 except on the control rows of a thrust stage)
+// and the old state is either the loaded pair or, in the v-form, rebuilt as  zo = clip(c v, lo, hi), yo = v - zo.
+//
+// Thrust-magnitude stages (second-order cone, §2.7).  The control rows u of a stage with a thrust bound ub and a fuel
+// weight f (kap = f / rho; cost term f ||u||_2) are shrunk by kap, then scaled onto the ball ||u||_2 <= ub:
+//     t = min(ub, max(||u|| - kap, 0)),     c = ||u|| > t ? t / ||u|| : 1,      z_u = c u.
+// kap = 0 is the plain ball projection (t = min(ub, ||u||); ||u|| > t iff ||u|| > ub), and ||u|| <= kap gives c = 0: a coast
+// stage.  sqrt and the division are the correctly rounded fp64 forms and the sum of squares is an fma chain in row order --
+// the operations of the CPU oracle.
+// BRANCH-FREE in the fused kernels: a stage without a bound carries ub = +inf (and kap = 0), for which the factor is exactly
+// 1 (norm > inf is false), and where a bound or a weight is set the box of the control rows is (-inf, inf) (validated at
+// setup), so  z_u = clip(c v_u, lo, hi)  is the ball projection in the one case and the box projection in the other, bit
+// for bit.  (The first version branched on the wave-uniform `ub < inf`: every row of the block then stayed live across the
+// branch and the two sqrt / division sequences inside it, and the fused kernels went to scratch at most shapes.)
+// A kernel that reaches the same bits by another sequence keeps it: zdual_soc_kernel / v_to_zy_soc_kernel branch on the
+// wave-uniform `soc && r < m` and take z_u = c v_u without the clip -- clip(x, -inf, inf) = x for every non-NaN x.
+#pragma once
+#include <cmath>
+
+#if defined(__HIPCC__)
+#define ADMM_PROX_FN __host__ __device__ __forceinline__
+#else
+#define ADMM_PROX_FN inline
+#endif
+
+namespace admm {
+
+// soc_factor is the general (fuel) form; ball_factor is the per-instance kernels' form, which carry no fuel weight: the two
+// give the same bits at kap = 0 but are different instruction sequences, and the per-instance kernels do not pay for the max / subtract.
+ADMM_PROX_FN double soc_factor(double nrm, double ub, double kap) {
+  const double t = fmin(ub, fmax(nrm - kap, 0.0));
+  return nrm > t ? t / nrm : 1.0;
+}
+ADMM_PROX_FN double ball_factor(double nrm, double ub) { return nrm > ub ? ub / nrm : 1.0; }
+
+// ||u||_2 of the first NU rows of a block, accumulated in row order with fma
+template <int NU, int NB>
+ADMM_PROX_FN double rows_norm(const double (&blk)[NB]) {
+  double ss = 0.0;
+#pragma unroll
+  for (int j = 0; j < NU; ++j) ss = fma(blk[j], blk[j], ss);
+  return sqrt(ss);
+}
+
+// the factor of a block from its first NU rows
+template <int NU, int NB>
+ADMM_PROX_FN double soc_scale(const double (&blk)[NB], double ub, double kap) { return soc_factor(rows_norm<NU, NB>(blk), ub, kap); }
+template <int NU, int NB>
+ADMM_PROX_FN double ball_scale(const double (&blk)[NB], double ub) { return ball_factor(rows_norm<NU, NB>(blk), ub); }
+
+// the clip and its two halves (a site whose bound is still in memory reads it between them: max, then min)
+ADMM_PROX_FN double clip_lo(double v, double lo) { return fmax(v, lo); }
+ADMM_PROX_FN double clip_hi(double v, double hi) { return fmin(v, hi); }
+ADMM_PROX_FN double clip(double v, double lo, double hi) { return clip_hi(clip_lo(v, lo), hi); }
+
+// the relaxed x-update output w^ from w and the old z
+template <bool RELAX>
+ADMM_PROX_FN double relaxed(double alpha, double w, double zo) {
+  return RELAX ? fma(alpha, w, (1.0 - alpha) * zo) : w;
+}
+
+// What stays at the sites, and why.  A row of a kernel that has a thrust-bound (SOC) form is written over these functions as
+//     zo = clip(ball ? v * c : v, lo, hi);  yo = v - zo;  vn = relaxed(alpha, w, zo) + yo;  zn = clip(ball ? vn * c' : vn, lo, hi);  yn = vn - zn;
+// and the SOC pre-pass (z+ needs ||v+_u||, so the control rows of v+ are formed first, then the factor of v+) as the same
+// operations on the control rows.  Functions returning the pair (z, y), and a pre-pass function taking the rows and bounds,
+// were tried: the bits are the same, but the compiler orders the operations of every SOC form differently and 126 kernels
+// came out with other register counts; with the text above every kernel has the registers it had.
+
+// The five residual partial sums of a QP, in their one fixed order:  (w - z+)^2, (z+ - z)^2, w^2, z+^2, y+^2.
+// xfz / xfze / xbze keep five scalars and add a row through an object built from them BY VALUE in the row's scope: the
+// reference form below changed their registers, and one object for the whole kernel cost xfz_kernel 20-40 of them.
+struct ResidSums {
+  double r = 0.0, s = 0.0, w = 0.0, z = 0.0, y = 0.0;
+  // the one definition, over five accumulators wherever a kernel keeps them (scalars, an array, this object)
+  static ADMM_PROX_FN void add(double& r, double& s, double& w, double& z, double& y, double wv, double zn, double zo, double yn) {
+    const double dr = wv - zn, ds = zn - zo;
+    r = fma(dr, dr, r);
+    s = fma(ds, ds, s);
+    w = fma(wv, wv, w);
+    z = fma(zn, zn, z);
+    y = fma(yn, yn, y);
+  }
+  static ADMM_PROX_FN void add(double (&acc)[5], double wv, double zn, double zo, double yn) {
+    add(acc[0], acc[1], acc[2], acc[3], acc[4], wv, zn, zo, yn);
+  }
+  ADMM_PROX_FN void add(double wv, double zn, double zo, double yn) { add(r, s, w, z, y, wv, zn, zo, yn); }
+};
+
+}  // namespace admm

@@ -138,7 +138,7 @@ def _pi_families(shape, form):
 @pytest.mark.parametrize("shape", PER_INSTANCE, ids=sid)
 def test_per_instance_families(gpu, shape, form, monkeypatch):
     """Per-instance dynamics with a box per QP (the kinds of the table rotate through the QPs: a kernel that reads another QP's box
-    fails): pi_soc_scale, the sweeps and the read-out of admm_pinst.hpp, admm_pinst_rows.hpp and admm_pinst_wide.hpp; the rows
+    fails): ball_factor, the sweeps and the read-out of admm_pinst.hpp, admm_pinst_rows.hpp and admm_pinst_wide.hpp; the rows
     factorisation at (6, 3).  The thrust-bound form also runs at rho = 0.25."""
     n, m = shape
     families = _pi_families(shape, form) + (("ADMM_PI_ROWS_FACTOR",) if shape == (6, 3) and form == "box" else ())

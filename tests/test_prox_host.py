@@ -6,7 +6,11 @@ chain in row order -- the reference's default (relax_fma=True, norm_fma=True).  
 -ffp-contract=off and writes alpha * w + (1 - alpha) * z: two roundings; oracle/admm_ref.py and tests/_fuel_ref.py (NumPy) do the
 same and also round each square before adding.  Each oracle is compared, bit for bit, with the variant of the reference that takes
 its form; at alpha = 1 and on the exact tuples of the table the variants coincide."""
+import ctypes as C
 import dataclasses
+import os
+import shutil
+import subprocess
 
 import numpy as np
 import pytest
@@ -135,3 +139,60 @@ def test_host_factors_of_the_decoupled_problem_are_exact(lib, shape):
                     assert rec.shape[1] % 8 == 0 and _dyadic(rec.view(np.float64)), (shape, rho, segments)
             for form in ("ball", "fuel_ball"):                       # the probe does not depend on the box or the bounds
                 assert host_factor(pc.make(n, m, 7, form, with_q=True, rho=rho).p, rho, segments)["alt_ok"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/admm_prox.hpp: the single definition of the z-update that every kernel family composes, on the host
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def prox_block(tmp_path_factory):
+    """tests/prox_block.cpp + csrc/admm_prox.hpp as a shared object (host compiler, no contraction: the header's explicit fma
+    calls are the only fused operations, as on the device)."""
+    import __graft_entry__ as ge
+    assert "admm_prox.hpp" in ge.HEADERS
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no C++ compiler"
+    so = tmp_path_factory.mktemp("prox") / "prox_block.so"
+    subprocess.run([cxx, "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-I", ge.CSRC,
+                    os.path.join(os.path.dirname(os.path.abspath(__file__)), "prox_block.cpp"), "-o", str(so)], check=True)
+    lib = C.CDLL(str(so))
+    dp = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+    lib.prox_zupdate.argtypes = [C.c_int] * 7 + [dp] * 7 + [C.c_double] + [dp] * 4
+    lib.prox_zupdate.restype = C.c_int
+    return lib
+
+
+@pytest.mark.parametrize("alpha", [1.0, 1.5])
+@pytest.mark.parametrize("shape", [(2, 1), (6, 3)], ids=sid)
+def test_the_header_z_update_equals_the_reference(prox_block, shape, alpha):
+    """The block z-update of admm_prox.hpp on the model iterates, three iterations, batch 7: the old state from (z, y) in the first
+    iteration and rebuilt from the header's own v+ afterwards (the v-form).  z and y equal the exact-rational reference of the
+    GPU sweep with np.array_equal; the five sums give the reference's residual norms within 1e-12 max(1, |ref|).  The forms
+    without a fuel weight also run with the per-instance kernels' factor."""
+    n, m = shape
+    batch = 7
+    for form in pc.FORMS:
+        for rho in (pc.RHOS if form == "fuel_ball" else (1.0,)):
+            case = pc.make(n, m, batch, form, rho=rho)
+            ref = pc.reference(n, m, batch, form, rho=rho, alpha=alpha)
+            lo, hi = (np.ascontiguousarray(a.reshape(batch, -1)) for a in (case.lo, case.hi))
+            for fuel in ((1,) if form.startswith("fuel") else (1, 0)):
+                s0, s1, vin = case.y0, case.z0, 0
+                for it, st in enumerate(ref):
+                    v, z, y = (np.full_like(case.z0, np.nan) for _ in range(3))
+                    sums = np.full((batch, 5), np.nan)
+                    rc = prox_block.prox_zupdate(n, m, vin, int(alpha != 1.0), fuel, batch, pc.N, np.ascontiguousarray(s0),
+                                                 np.ascontiguousarray(s1), np.ascontiguousarray(st["w"]), lo, hi, case.ub, case.kap,
+                                                 alpha, v, z, y, sums)
+                    ctx = (form, rho, fuel, it)
+                    assert rc == 0
+                    assert not np.isnan(z).any() and not np.isnan(y).any(), ctx
+                    assert np.array_equal(z, st["z"]), (ctx, "z", np.abs(z - st["z"]).max())
+                    assert np.array_equal(y, st["y"]), (ctx, "y", np.abs(y - st["y"]).max())
+                    assert np.array_equal(v, st["v"]), (ctx, "v")
+                    root = np.sqrt(sums.astype(np.longdouble))
+                    got = (root[:, 0], rho * root[:, 1], root[:, 2], root[:, 3], rho * root[:, 4])
+                    for name, g, want in zip(("r", "s", "nw", "nz", "ny"), got, st["res"]):
+                        err = np.abs(g - want)
+                        assert (err <= 1e-12 * np.maximum(1.0, np.abs(want))).all(), (ctx, name, float(err.max()))
+                    s0, s1, vin = v, np.zeros_like(v), 1
