@@ -79,6 +79,15 @@ SCVX_RELATIVE_CIRCULAR = 0
 SCVX_CRTBP = 1
 
 
+class CScvxStageDynamics(C.Structure):  # admm_scvx_stage_dynamics: a time-dependent model (kind), its parameters and its node table
+    _fields_ = [("N", C.c_int32), ("batch", C.c_int32), ("substeps", C.c_int32), ("kind", C.c_int32), ("dt", C.c_double),
+                ("par", C.c_double * 4), ("nodes", c_double_p), ("n_nodes", C.c_int64), ("reserved", C.c_int32)]
+
+
+SCVX_STAGE_RELATIVE_TABULATED = 0
+SCVX_NODE_PAR = 4
+
+
 class CScvxParams(C.Structure):         # admm_scvx_params (Q, R, QN row-major)
     _fields_ = [("Q", C.c_double * 36), ("R", C.c_double * 9), ("QN", C.c_double * 36), ("u_lo", C.c_double * 3),
                 ("u_hi", C.c_double * 3), ("fd_eps", C.c_double), ("tol", C.c_double), ("rho_reject", C.c_double),

@@ -1,6 +1,6 @@
 // admm_scvx_host.hpp -- host side shared by the units that instantiate the SCvx kernels for a model (admm_scvx.hip: the shipped
 // model and the admm_scvx_*_device entry points; admm_scvx_models.hip: the CR3BP and the admm_scvx_*_model_device entry points;
-// DESIGN.md §2.8.1, §2.8.2).  Argument checks, the Arg tables, enter_device, the per-device counter and the launch code, once.
+// admm_scvx_stage.hip: the models that read per-node data and the admm_scvx_*_stage_device entry points).  Argument checks, the Arg tables, enter_device, the per-device counter and the launch code, once.
 // Every check -- arguments first, without a HIP call; then the pointers -- comes before the first launch.  An entry point checks
 // its own model struct, builds the device-side model M (admm_scvx_kernels.hpp) and calls scvx_<call><M>.
 #pragma once
@@ -101,6 +101,15 @@ inline int enter_device(const char* fn, int device) {
   return ADMM_OK;
 }
 
+// a model that reads per-node data (admm::ScvxTakesNodes): its table joins the call's arrays, checked like them.
+// The entry point has checked that the pointer is not NULL and that the table has 2 substeps N + 1 rows.  Returns the new count
+template <class M>
+int node_args(const M& md, Arg* a, int count) {
+  if constexpr (admm::ScvxTakesNodes<M>::value)
+    a[count++] = Arg{md.nodes, ((size_t)2 * md.substeps * md.N + 1) * M::NODE_PAR, "nodes", false};
+  return count;
+}
+
 inline unsigned waves_of(int batch) { return (unsigned)((batch + admm::SCVX_THREADS - 1) / admm::SCVX_THREADS); }
 
 // scvx_commit_kernel on stream s (it has no model; defined in admm_scvx.hip)
@@ -112,8 +121,9 @@ template <class M>
 int scvx_rollout(const char* fn, int device, const M& md, const double* x0, const double* u, double* x, void* hip_stream) {
   int rc;
   const size_t B = md.batch, N = md.N;
-  const Arg args[] = {{x0, B * 6, "x0", false}, {u, B * N * 3, "u", false}, {x, B * N * 6, "x", false}};
-  if ((rc = check_null(fn, args, 3)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, 3))) return rc;
+  Arg args[4] = {{x0, B * 6, "x0", false}, {u, B * N * 3, "u", false}, {x, B * N * 6, "x", false}};
+  const int na = node_args(md, args, 3);
+  if ((rc = check_null(fn, args, na)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, na))) return rc;
   hipLaunchKernelGGL((admm::scvx_rollout_kernel<M, false>), dim3(waves_of(md.batch)), dim3(admm::SCVX_THREADS), 0,
                      static_cast<hipStream_t>(hip_stream), md, admm_scvx_params{}, x0, u, x, admm::ScvxInit{});
   HIP_TRY(hipGetLastError());
@@ -129,10 +139,11 @@ int scvx_init(const char* fn, int device, const M& md, const admm_scvx_params* p
   if (!std::isfinite(tr_u) || tr_u < 0.0) return bad(fn, "tr_u must be finite and >= 0");
   if (!std::isfinite(tr_x) || tr_x < 0.0) return bad(fn, "tr_x must be finite and >= 0");
   if (state->history_capacity < 1) return bad(fn, "state.history_capacity must be >= 1");
-  Arg args[14];
+  Arg args[15];
   const int ns = state_args(md, state, args);
   args[ns] = Arg{x0, (size_t)md.batch * 6, "x0", false};
-  if ((rc = check_null(fn, args, ns + 1)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, ns + 1))) return rc;
+  const int na = node_args(md, args, ns + 1);
+  if ((rc = check_null(fn, args, na)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, na))) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   HIP_TRY(hipMemsetAsync(state->ub, 0, sizeof(double) * (size_t)md.batch * md.N * 3, s));
   const admm::ScvxInit in{state->J, state->tr_u, state->tr_x, state->active, state->converged, state->accepted, state->outer,
@@ -150,11 +161,11 @@ int scvx_prepare(const char* fn, int device, const M& md, const admm_scvx_params
   if ((rc = check_params(fn, params))) return rc;
   if (!state) return bad(fn, "state is NULL");
   const size_t Bn = md.batch, N = md.N;
-  const Arg args[] = {{x0, Bn * 6, "x0", false}, {state->ub, Bn * N * 3, "state.ub", false}, {state->xb, Bn * N * 6, "state.xb", false},
+  Arg args[12] = {{x0, Bn * 6, "x0", false}, {state->ub, Bn * N * 3, "state.ub", false}, {state->xb, Bn * N * 6, "state.xb", false},
                       {state->tr_u, Bn, "state.tr_u", false}, {state->tr_x, Bn, "state.tr_x", false}, {state->active, Bn, "state.active", true},
                       {A, Bn * N * 36, "A", false}, {B, Bn * N * 18, "B", false}, {lo, Bn * N * 9, "lo", false},
                       {hi, Bn * N * 9, "hi", false}, {q, Bn * N * 9, "q", false}};
-  constexpr int na = sizeof args / sizeof args[0];
+  const int na = node_args(md, args, 11);
   if ((rc = check_null(fn, args, na)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, na))) return rc;
   const size_t blocks = (Bn * N + admm::SCVX_THREADS - 1) / admm::SCVX_THREADS;
   if (blocks > 0x7fffffffu) return bad(fn, "batch * N is too large");
@@ -173,11 +184,12 @@ int scvx_advance(const char* fn, int device, const M& md, const admm_scvx_params
   if (!n_active) return bad(fn, "n_active is NULL");
   if (state->history_capacity < 1) return bad(fn, "state.history_capacity must be >= 1");
   const size_t Bn = md.batch, N = md.N;
-  Arg args[15];
+  Arg args[16];
   const int ns = state_args(md, state, args);
   args[ns] = Arg{x0, Bn * 6, "x0", false};
   args[ns + 1] = Arg{z, Bn * N * 9, "z", false};
-  if ((rc = check_null(fn, args, ns + 2)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, ns + 2))) return rc;
+  const int na = node_args(md, args, ns + 2);
+  if ((rc = check_null(fn, args, na)) || (rc = enter_device(fn, device)) || (rc = check_device(fn, device, args, na))) return rc;
   hipStream_t s = static_cast<hipStream_t>(hip_stream);
   // every active trajectory writes record outer[b]: it must exist (two small copies; nothing has been launched yet)
   std::vector<int32_t> flags(2 * Bn);

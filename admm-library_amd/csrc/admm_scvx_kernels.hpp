@@ -1,7 +1,8 @@
 // admm_scvx_kernels.hpp -- the outer step of the batched successive-convexification loop on the device: the
 // device counterparts of scvx.rollout, scvx.linearise, scvx.correction_qp_batch and the decision block of scvx.scvx_batch, for the
 // model M the kernels are instantiated for (n = 6, m = 3; the shipped one, scvx.relative_motion_rhs, in admm_scvx.hip; DESIGN.md
-// §2.8.2: the others in admm_scvx_models.hip).  fp64, explicit fma(), no inline assembly.
+// §2.8.2: the CR3BP in admm_scvx_models.hip; §2.8.3: the models that read per-node data in admm_scvx_stage.hip).  fp64, explicit
+// fma(), no inline assembly.
 //
 // Every caller-visible array is QP-major C order (the shapes of Problem / DeviceProblem): u (B, N, 3), x (B, N, 6) = x_1 .. x_N,
 // A (B, N, 6, 6) and B (B, N, 6, 3) as row-major blocks, lo | hi | q | z (B, N, 9) in block order (u_k, x_{k+1}).
@@ -44,7 +45,7 @@ struct ScvxGrid {
 
 // A model type M is the grid plus the parameters the host derives once from the caller's struct, and
 //   static void rhs(const double (&s)[6], const double (&u)[3], const M& md, double (&d)[6])      d = f(s, u)
-// -- nothing else: RK4, the LDS chunking, the central differences, the cost chains and the decision below are one copy of code.
+// (a model that reads per-node data: ScvxTakesNodes below) -- nothing else: RK4, the LDS chunking, the central differences, the cost chains and the decision below are one copy of code.
 
 // scvx.relative_motion_rhs (admm_scvx_model; ADMM_SCVX_RELATIVE_CIRCULAR): the formulas in the same order (rd^3 = r2 sqrt(r2) for
 // pow(r2, 1.5)); rc3 = rc^3
@@ -84,24 +85,82 @@ struct ScvxCrtbp : ScvxGrid {
   }
 };
 
-// rk4_step of the model: s <- F(s, u), classical RK4 over `substeps` sub-intervals under a held control
+// A model may read per-node data: it declares `static constexpr int NODE_PAR = ADMM_SCVX_NODE_PAR`, carries
+// `const double* nodes` (row-major rows of NODE_PAR doubles, one per RK4 node of the horizon, shared by the batch) and its rhs takes
+// the node's row: rhs(s, u, md, e, d).  A compile-time property: for the models without it the code below is the code it was.
+template <class M, class = void>
+struct ScvxTakesNodes { static constexpr bool value = false; };
 template <class M>
-__device__ __forceinline__ void scvx_step(double (&s)[6], const double (&u)[3], const M& md) {
+struct ScvxTakesNodes<M, decltype((void)M::NODE_PAR)> { static constexpr bool value = true; };
+
+// scvx.relative_tabulated_rhs (ADMM_SCVX_STAGE_RELATIVE_TABULATED): exact relative motion in the rotating frame of a chief that moves
+// in a plane, x radial, y along-track, z cross-track; the node's row e = (rc, w, wd, g): chief radius, angular rate, angular
+// acceleration, the chief's radial gravity mu / rc^2.  The formulas in the same order (r2 sqrt(r2) for the 3/2 power)
+struct ScvxRelativeTabulated : ScvxGrid {
+  static constexpr int NODE_PAR = ADMM_SCVX_NODE_PAR;
+  double mu;
+  const double* nodes;
+  __device__ __forceinline__ static void rhs(const double (&s)[6], const double (&u)[3], const ScvxRelativeTabulated& md,
+                                             const double (&e)[4], double (&d)[6]) {
+    const double xr = e[0] + s[0];
+    const double r2 = fma(s[2], s[2], fma(s[1], s[1], xr * xr));
+    const double k = md.mu / (r2 * sqrt(r2));
+    const double w2 = e[1] * e[1], tw = 2.0 * e[1];
+    d[0] = s[3];
+    d[1] = s[4];
+    d[2] = s[5];
+    d[3] = fma(-k, xr, fma(w2, s[0], fma(e[2], s[1], tw * s[4])) + e[3]) + u[0];
+    d[4] = fma(-k, s[1], fma(w2, s[1], fma(-e[2], s[0], -tw * s[3]))) + u[1];
+    d[5] = fma(-k, s[2], u[2]);
+  }
+};
+
+template <class M>
+__device__ __forceinline__ void scvx_rhs(const double (&s)[6], const double (&u)[3], const M& md, const double (&e)[4], double (&d)[6]) {
+  if constexpr (ScvxTakesNodes<M>::value) M::rhs(s, u, md, e, d);
+  else M::rhs(s, u, md, d);
+}
+
+// the first node row of stage k: global node 2 substeps k (a model without node data: no pointer)
+template <class M>
+__device__ __forceinline__ const double* scvx_stage_nodes(const M& md, int k) {
+  if constexpr (ScvxTakesNodes<M>::value) return md.nodes + (size_t)k * (2 * md.substeps) * M::NODE_PAR;
+  else return nullptr;
+}
+
+// rk4_step of the model: s <- F(s, u), classical RK4 over `substeps` sub-intervals under a held control.  nd: the stage's first
+// node row (scvx_stage_nodes); sub-interval i reads rows 2 i (k1), 2 i + 1 (k2, k3) and 2 i + 2 (k4, the next one's first)
+template <class M>
+__device__ __forceinline__ void scvx_step(double (&s)[6], const double (&u)[3], const M& md, const double* __restrict__ nd) {
+  constexpr bool NODES = ScvxTakesNodes<M>::value;
+  double e0[4] = {}, e1[4] = {}, e2[4] = {};
+  if constexpr (NODES) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) e0[i] = nd[i];
+  }
 #pragma unroll 1
   for (int sub = 0; sub < md.substeps; ++sub) {
+    if constexpr (NODES) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { e1[i] = nd[(2 * sub + 1) * 4 + i]; e2[i] = nd[(2 * sub + 2) * 4 + i]; }
+    }
     double k[6], acc[6], t[6];
-    M::rhs(s, u, md, k);
+    scvx_rhs(s, u, md, e0, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = k[i]; t[i] = fma(md.hh, k[i], s[i]); }
-    M::rhs(t, u, md, k);
+    scvx_rhs(t, u, md, e1, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = fma(2.0, k[i], acc[i]); t[i] = fma(md.hh, k[i], s[i]); }
-    M::rhs(t, u, md, k);
+    scvx_rhs(t, u, md, e1, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) { acc[i] = fma(2.0, k[i], acc[i]); t[i] = fma(md.h, k[i], s[i]); }
-    M::rhs(t, u, md, k);
+    scvx_rhs(t, u, md, e2, k);
 #pragma unroll
     for (int i = 0; i < 6; ++i) s[i] = fma(md.h6, acc[i] + k[i], s[i]);
+    if constexpr (NODES) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) e0[i] = e2[i];
+    }
   }
 }
 
@@ -186,7 +245,7 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_rollout_kernel(M md, admm_s
       double uk[3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) uk[i] = lu[lane * SU + kk * 3 + i];
-      scvx_step(s, uk, md);
+      scvx_step(s, uk, md, scvx_stage_nodes(md, k0 + kk));
 #pragma unroll
       for (int i = 0; i < 6; ++i) lx[lane * SX + kk * 6 + i] = s[i];
       if (INIT) scvx_cost_stage(pr, uk, s, k0 + kk == md.N - 1, cu, cx, cn);
@@ -229,6 +288,7 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_linearise_kernel(M md, admm
 #pragma unroll
   for (int r = 0; r < 3; ++r) u[r] = ub[i * 3 + r];
   const double eps = pr.fd_eps, inv = 2.0 * eps;
+  const double* nd = scvx_stage_nodes(md, k);          // this lane's stage: its own rows
 
   // direction j: state j (j < 6: column j of A), control j - 6 (column j - 6 of B).  The perturbation is added as in the host code,
   // x + d with d = eps e_j (x + 0.0 = x on the other rows), selected per row so that no register array is indexed by j
@@ -244,12 +304,12 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_linearise_kernel(M md, admm
     for (int r = 0; r < 6; ++r) fp[r] = xp[r] + (r == j ? eps : 0.0);
 #pragma unroll
     for (int r = 0; r < 3; ++r) up[r] = u[r] + (r + 6 == j ? eps : 0.0);
-    scvx_step(fp, up, md);
+    scvx_step(fp, up, md, nd);
 #pragma unroll
     for (int r = 0; r < 6; ++r) fm[r] = xp[r] - (r == j ? eps : 0.0);
 #pragma unroll
     for (int r = 0; r < 3; ++r) up[r] = u[r] - (r + 6 == j ? eps : 0.0);
-    scvx_step(fm, up, md);
+    scvx_step(fm, up, md, nd);
     if (j < 6) {
 #pragma unroll
       for (int r = 0; r < 6; ++r) lds[lane * SA + r * 6 + j] = (fp[r] - fm[r]) / inv;
@@ -342,7 +402,7 @@ __global__ __launch_bounds__(SCVX_THREADS) void scvx_advance_kernel(M md, admm_s
 #pragma unroll
       for (int i = 0; i < 6; ++i) xl[i] = lx[lane * SX + kk * 6 + i] + lz[lane * SZ + kk * 9 + 3 + i];
       scvx_cost_stage(pr, ul, xl, last, lu_c, lx_c, ln_c);
-      scvx_step(s, un, md);
+      scvx_step(s, un, md, scvx_stage_nodes(md, k0 + kk));
 #pragma unroll
       for (int i = 0; i < 6; ++i) ox[lane * SX + kk * 6 + i] = s[i];
       scvx_cost_stage(pr, un, s, last, nu_c, nx_c, nn_c);

@@ -172,32 +172,182 @@ def crtbp_collinear_point(mu: float, which: int) -> float:
     return min(cands, key=lambda c: float(np.abs(crtbp_rhs(rest, zero, mu, c)).max()))
 
 
-def _resolve(model: Optional[Model], step):
-    """The `step` of a call that may name a model instead: model.step; both: ValueError."""
+def relative_tabulated_rhs(s, u, e, mu: float):
+    """Exact nonlinear relative motion in the rotating frame of a chief that moves in a plane (x radial, y along-track, z
+    cross-track): time derivative of s = (x, y, z, vx, vy, vz) (..., 6) under the thrust acceleration u (..., 3) at a node whose
+    row e (..., 4) = (rc, w, wd, g) holds the chief's radius, angular rate, angular acceleration and radial gravity mu / rc^2.
+    The normative statement of the device model ScvxRelativeTabulated; NumPy arrays or torch tensors.  With
+    rc = a, w = 1, wd = 0, g = a, mu = a^3 it is relative_motion_rhs."""
+    if isinstance(s, np.ndarray):
+        sqrt, stack = np.sqrt, functools.partial(np.stack, axis=-1)
+    else:
+        import torch
+        sqrt, stack = torch.sqrt, functools.partial(torch.stack, dim=-1)
+    x, y, z, vx, vy, vz = (s[..., i] for i in range(6))
+    rc, w, wd, g = (e[..., i] for i in range(4))
+    xr = rc + x
+    r2 = xr**2 + y**2 + z**2
+    k = mu / (r2 * sqrt(r2))
+    ax = 2*w*vy + wd*y + w*w*x + g - k*xr + u[..., 0]
+    ay = -2*w*vx - wd*x + w*w*y - k*y + u[..., 1]
+    az = -k*z + u[..., 2]
+    return stack((vx, vy, vz, ax, ay, az))
+
+
+def _rk4_nodes(rhs, s, u, dt, e, substeps):
+    """_rk4 for a right-hand side that reads node rows: e (..., 2 substeps + 1, 4) holds the stage's rows -- sub-interval i uses
+    row 2 i (k1), 2 i + 1 (k2, k3) and 2 i + 2 (k4)."""
+    h = dt / substeps
+    for i in range(substeps):
+        e0, e1, e2 = e[..., 2 * i, :], e[..., 2 * i + 1, :], e[..., 2 * i + 2, :]
+        k1 = rhs(s, u, e0)
+        k2 = rhs(s + 0.5 * h * k1, u, e1)
+        k3 = rhs(s + 0.5 * h * k2, u, e1)
+        k4 = rhs(s + h * k3, u, e2)
+        s = s + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+    return s
+
+
+@dataclasses.dataclass(frozen=True)
+class StageModel:
+    """A TIME-DEPENDENT model the loop can be run for (n = 6, m = 3): its right-hand side reads ADMM_SCVX_NODE_PAR = 4 values per
+    RK4 node from a table shared by all trajectories (admm_scvx_stage_dynamics).  The nodes of a grid
+    (N, dt, substeps) lie at the times t0 + g h / 2, h = dt / substeps, g = 0 .. 2 substeps N; all time dependence is in the table."""
+    name: str                     # admm_scvx_stage_model_name(kind)
+    kind: int                     # ADMM_SCVX_STAGE_RELATIVE_TABULATED
+    par: Tuple[float, ...]        # admm_scvx_stage_dynamics.par, the entries in use
+    rhs: Callable                 # rhs(s, u, e) on NumPy arrays, e the node's row (..., 4)
+    rhs_torch: Callable           # ... on torch tensors: the same formulas in the same order
+    nodes_fn: Callable            # nodes_fn(N, dt, substeps) -> the table (2 substeps N + 1, 4)
+
+    def nodes(self, N: int, dt: float, substeps: int = 4) -> np.ndarray:
+        """The table of the grid (N, dt, substeps): (2 substeps N + 1, 4) fp64, C order."""
+        t = np.ascontiguousarray(self.nodes_fn(int(N), float(dt), int(substeps)), np.float64)
+        if t.shape != (2 * int(substeps) * int(N) + 1, 4):
+            raise ValueError(f"{self.name}: the node table has shape {t.shape}, expected {(2 * int(substeps) * int(N) + 1, 4)}")
+        return t
+
+    def stage_nodes(self, N: int, dt: float, substeps: int = 4) -> np.ndarray:
+        """The table by stage: (N, 2 substeps + 1, 4), stage k holding the rows 2 substeps k .. 2 substeps (k + 1)."""
+        idx = 2 * substeps * np.arange(N)[:, None] + np.arange(2 * substeps + 1)[None, :]
+        return self.nodes(N, dt, substeps)[idx]
+
+    def step(self, s, u, dt: float, e, substeps: int = 4):
+        """Zero-order-hold propagation of one stage whose node rows are e (..., 2 substeps + 1, 4)."""
+        return _rk4_nodes(self.rhs, s, u, dt, e, substeps)
+
+
+def kepler_E(M, e: float):
+    """The eccentric anomaly E of Kepler's equation E - e sin E = M, by Newton's method in np.longdouble (M: array)."""
+    LD = np.longdouble
+    M, e = np.asarray(M, LD), LD(e)
+    E = M + e * np.sin(M)
+    for _ in range(60):
+        d = (E - e * np.sin(E) - M) / (LD(1) - e * np.cos(E))
+        E = E - d
+        if np.all(np.abs(d) <= LD(4) * np.finfo(LD).eps * np.maximum(LD(1), np.abs(E))):
+            break
+    return E
+
+
+def elliptic_nodes(a: float, e: float, M0: float, N: int, dt: float, substeps: int = 4) -> np.ndarray:
+    """The node table (2 substeps N + 1, 4) of relative_tabulated_rhs for a chief on a Kepler orbit of semi-major axis a and
+    eccentricity e that is at mean anomaly M0 at the first node.  The time unit is 1 / mean motion (mu = a^3, as the circular model
+    has it), so node g lies at mean anomaly M0 + g h / 2, h = dt / substeps.  Evaluated in np.longdouble and rounded to fp64 once:
+    rc = a (1 - e cos E), w = a^2 sqrt(1 - e^2) / rc^2, wd = -2 w rdot / rc with rdot = a e sin E / (1 - e cos E), g = a^3 / rc^2."""
+    if not (np.isfinite(a) and a > 0.0) or not (np.isfinite(e) and 0.0 <= e < 1.0):
+        raise ValueError("elliptic_nodes: a must be positive and e lie in [0, 1)")
+    LD = np.longdouble
+    a_, e_ = LD(a), LD(e)
+    hh = LD(dt) / LD(substeps) / LD(2)
+    E = kepler_E(LD(M0) + np.arange(2 * int(substeps) * int(N) + 1).astype(LD) * hh, e)
+    den = LD(1) - e_ * np.cos(E)
+    rc = a_ * den
+    w = a_ * a_ * np.sqrt(LD(1) - e_ * e_) / (rc * rc)
+    rdot = a_ * e_ * np.sin(E) / den
+    wd = -LD(2) * w * rdot / rc
+    g = a_ * a_ * a_ / (rc * rc)
+    return np.ascontiguousarray(np.stack([rc, w, wd, g], axis=-1).astype(np.float64))
+
+
+def relative_tabulated(nodes_fn: Callable, mu: float) -> StageModel:
+    """relative_tabulated_rhs about a chief whose motion the caller tabulates: nodes_fn(N, dt, substeps) -> (2 substeps N + 1, 4)
+    rows (rc, w, wd, mu / rc^2)."""
+    if not (np.isfinite(mu) and mu > 0.0):
+        raise ValueError("relative_tabulated: mu must be finite and positive")
+    f = functools.partial(relative_tabulated_rhs, mu=float(mu))
+    return StageModel("relative_tabulated", 0, (float(mu),), f, f, nodes_fn)
+
+
+def relative_elliptic(a: float = RC_KM, e: float = 0.0, M0: float = 0.0) -> StageModel:
+    """Relative motion about a chief on a Kepler orbit (elliptic_nodes): semi-major axis a, eccentricity e, mean anomaly M0 at the
+    start of the horizon; time in units of 1 / mean motion."""
+    if not (np.isfinite(a) and a > 0.0) or not (np.isfinite(e) and 0.0 <= e < 1.0):
+        raise ValueError("relative_elliptic: a must be positive and e lie in [0, 1)")
+    return relative_tabulated(functools.partial(elliptic_nodes, float(a), float(e), float(M0)), float(a) ** 3)
+
+
+def _resolve(model, step):
+    """The `step` of a call that may name a model instead: model.step (a StageModel: `step` itself -- the callee is handed the model
+    as well, _timed); both: ValueError."""
     if model is None:
         return step
     if step is not rk4_step:
-        raise ValueError("model and step cannot both be given")
-    return model.step
+        raise ValueError("model and step cannot both be given" if not isinstance(model, StageModel) else
+                         "a time-dependent model and step cannot both be given")
+    return step if isinstance(model, StageModel) else model.step
 
 
-def rollout(x0: np.ndarray, u: np.ndarray, dt: float, step=rk4_step) -> np.ndarray:
+def _timed(model):
+    """model if it is time-dependent, else None."""
+    return model if isinstance(model, StageModel) else None
+
+
+def _model_step(model, step, substeps):
+    """rollout's and linearise's `step` under their keywords model and substeps (a Model: its step, at `substeps` if given)."""
+    if model is None:
+        if substeps is not None:
+            raise ValueError("substeps goes with model (a foreign step carries its own)")
+        return step
+    step = _resolve(model, step)
+    return step if substeps is None or isinstance(model, StageModel) else functools.partial(step, substeps=substeps)
+
+
+def rollout(x0: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, model=None, substeps: Optional[int] = None) -> np.ndarray:
     """States x_1..x_N (N, n) of the nonlinear dynamics from x0 under controls u (N, m); with a leading
-    batch axis on both ((B, n), (B, N, m)) the B trajectories are propagated together -> (B, N, n)."""
+    batch axis on both ((B, n), (B, N, m)) the B trajectories are propagated together -> (B, N, n).
+    model: a Model or StageModel in place of `step` (not both), at `substeps` sub-intervals (default 4); stage k of a StageModel
+    reads the rows 2 substeps k .. 2 substeps (k + 1) of model.nodes(N, dt, substeps)."""
+    step = _model_step(model, step, substeps)
     u = np.asarray(u, np.float64)
     s = np.asarray(x0, np.float64)
     N = u.shape[-2]
     xs = np.empty(u.shape[:-1] + (s.shape[-1],))
+    if _timed(model):
+        sub = 4 if substeps is None else int(substeps)
+        e = model.stage_nodes(N, dt, sub)
+        for k in range(N):
+            s = model.step(s, u[..., k, :], dt, e[k], sub)
+            xs[..., k, :] = s
+        return xs
     for k in range(N):
         s = step(s, u[..., k, :], dt)
         xs[..., k, :] = s
     return xs
 
 
-def linearise(xprev: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, eps: float = 1e-6
-              ) -> Tuple[np.ndarray, np.ndarray]:
+def linearise(xprev: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, eps: float = 1e-6, model=None,
+              substeps: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
     """A_k = dF/dx, B_k = dF/du of the stage map F at (xprev_k, u_k), k = 0..N-1, by central
-    differences (vectorised over stages and perturbation directions)."""
+    differences (vectorised over stages and perturbation directions).
+    model, substeps: as in rollout; with a StageModel the stage axis (the last but one of xprev) is the whole horizon 0..N-1."""
+    step = _model_step(model, step, substeps)
+    if _timed(model):
+        sub = 4 if substeps is None else int(substeps)
+        e = model.stage_nodes(xprev.shape[-2], dt, sub)
+
+        def step(s, uu, dt):      # noqa: F811
+            return model.step(s, uu, dt, e, sub)
     lead, n = xprev.shape[:-1], xprev.shape[-1]          # (N,) or (B, N)
     m = u.shape[-1]
     A = np.empty(lead + (n, n))
@@ -212,13 +362,14 @@ def linearise(xprev: np.ndarray, u: np.ndarray, dt: float, step=rk4_step, eps: f
 
 
 def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = "cuda:0", eps: float = 1e-6,
-                     substeps: int = 4, rc: float = RC_KM, keep_on_device: bool = False, model: Optional[Model] = None):
+                     substeps: int = 4, rc: float = RC_KM, keep_on_device: bool = False, model=None):
     """linearise() of the shipped model (rk4_step of relative_motion_rhs) with the n + m central differences evaluated as ONE
     batch of torch tensors on `device`: the same formulas in the same order, fp64.  The NumPy version makes 2 (n + m) x 16
     passes over (B, N, 6) arrays -- 10 s per outer iteration of a 4096-trajectory batch, most of the wall time of
     examples/scvx_batch_rendezvous.py; this is host plumbing, not the solver.
     keep_on_device: return A, B as the torch tensors on `device` (for a DeviceProblem) instead of NumPy copies.
-    model: the right-hand side is model.rhs_torch instead of the shipped one (rc is then not used)."""
+    model: the right-hand side is model.rhs_torch instead of the shipped one (rc is then not used); a StageModel: its node rows are
+    uploaded once and broadcast along the stage axis (the last but one of xprev: the whole horizon)."""
     import torch
     xp = torch.as_tensor(np.ascontiguousarray(xprev), dtype=torch.float64, device=device)
     up = torch.as_tensor(np.ascontiguousarray(u), dtype=torch.float64, device=device)
@@ -228,6 +379,12 @@ def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = 
 
     def step(s, uu):
         return _rk4(rhs, s, uu, dt, substeps)
+
+    if _timed(model):
+        e = torch.as_tensor(model.stage_nodes(xp.shape[-2], dt, substeps), device=device)
+
+        def step(s, uu):      # noqa: F811
+            return _rk4_nodes(rhs, s, uu, dt, e, substeps)
 
     ex = eps * torch.eye(n, dtype=torch.float64, device=device).reshape((n,) + (1,) * (xp.dim() - 1) + (n,))
     eu = eps * torch.eye(m, dtype=torch.float64, device=device).reshape((m,) + (1,) * (up.dim() - 1) + (m,))
@@ -259,12 +416,13 @@ def trajectory_cost(x: np.ndarray, u: np.ndarray, Q, R, QN):
 
 
 def correction_qp(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
-                  tr_u: float, tr_x: float, step=rk4_step) -> Problem:
-    """The QP of one outer iteration (module docstring) as a hot-path Problem (batch = 1)."""
+                  tr_u: float, tr_x: float, step=rk4_step, model=None, substeps: Optional[int] = None) -> Problem:
+    """The QP of one outer iteration (module docstring) as a hot-path Problem (batch = 1).
+    model, substeps: as in linearise (scvx passes a StageModel on; a Model arrives as its step)."""
     N, n = xb.shape
     m = ub.shape[1]
     xprev = np.vstack([x0[None], xb[:-1]])
-    A, B = linearise(xprev, ub, dt, step)
+    A, B = linearise(xprev, ub, dt, step, model=model, substeps=substeps)
     q = np.empty((N, m + n))
     q[:, :m] = ub @ R.T
     q[:-1, m:] = xb[:-1] @ Q.T
@@ -322,7 +480,7 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
          qp_solver: Optional[Callable[[Problem], Tuple[np.ndarray, int]]] = None,
          u_init: Optional[np.ndarray] = None, tr_u: float = 0.1, tr_x: float = 20.0,
          max_outer: int = 20, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7,
-         step=rk4_step, qp_options: Optional[dict] = None, model: Optional[Model] = None) -> ScvxResult:
+         step=rk4_step, qp_options: Optional[dict] = None, model=None) -> ScvxResult:
     """Trust-region successive convexification of
 
         minimise 1/2 sum_k [u_k' R u_k + x_{k+1}' Q_{k+1} x_{k+1}]   s.t.  x_{k+1} = F(x_k, u_k),  u_lo <= u_k <= u_hi.
@@ -330,8 +488,10 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     qp_solver(problem) -> (z of shape (1, L), ADMM iterations); default = the HIP solver.
     A step is accepted when actual / predicted cost decrease >= rho_reject (trust radii halve
     otherwise, double above rho_expand); stops when the accepted correction is below `tol`.
-    model: a Model (relative_circular(), crtbp(...)) whose step replaces `step`; not both."""
+    model: a Model (relative_circular(), crtbp(...)) whose step replaces `step`; not both.  Or a StageModel (relative_elliptic(...),
+    relative_tabulated(...)): a time-dependent model, whose stages read the node table of the grid (N, dt, 4 sub-intervals)."""
     step = _resolve(model, step)
+    tm = _timed(model)
     x0 = np.asarray(x0, np.float64)
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
     n, m = Q.shape[0], R.shape[0]
@@ -341,19 +501,19 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         qp_solver = gpu_qp_solver(**(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
                                                         check_interval=25)))
     ub = np.zeros((N, m)) if u_init is None else np.clip(np.asarray(u_init, np.float64), u_lo, u_hi)
-    xb = rollout(x0, ub, dt, step)
+    xb = rollout(x0, ub, dt, step, model=tm)
     J = trajectory_cost(xb, ub, Q, R, QN)
     hist: List[dict] = []
     accepted, converged = 0, False
     for it in range(1, max_outer + 1):
-        p = correction_qp(xb, ub, x0, dt, Q, R, QN, u_lo, u_hi, tr_u, tr_x, step)
+        p = correction_qp(xb, ub, x0, dt, Q, R, QN, u_lo, u_hi, tr_u, tr_x, step, model=tm)
         z, admm_iters = qp_solver(p)
         d = np.asarray(z, np.float64).reshape(N, m + n)
         du, dx = d[:, :m], d[:, m:]
         # cost the QP's model predicts for (xb + dx, ub + du)
         J_lin = trajectory_cost(xb + dx, ub + du, Q, R, QN)
         u_new = np.clip(ub + du, u_lo, u_hi)
-        x_new = rollout(x0, u_new, dt, step)
+        x_new = rollout(x0, u_new, dt, step, model=tm)
         J_new = trajectory_cost(x_new, u_new, Q, R, QN)
         predicted, actual = J - J_lin, J - J_new
         ratio = actual / predicted if predicted > 0 else -np.inf
@@ -382,23 +542,30 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
 
 def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
                         tr_u: np.ndarray, tr_x: np.ndarray, step=rk4_step, device: Optional[str] = None,
-                        qp_data_on_device: bool = False, model: Optional[Model] = None):
+                        qp_data_on_device: bool = False, model=None, substeps: Optional[int] = None):
     """The correction QPs of B trajectories as ONE batch with per-instance dynamics, box and linear term
     (xb (B, N, n), ub (B, N, m), x0 (B, n), trust radii (B,)).
     qp_data_on_device (with device): a DeviceProblem -- A, B stay where linearise_device made them, the rest is built here
     exactly as for the Problem and copied to the device.
-    model (scvx_batch passes it with step = model.step): the device linearisation evaluates model.rhs_torch."""
+    model (scvx_batch passes it with step = model.step): the device linearisation evaluates model.rhs_torch.  A StageModel: the
+    host linearisation reads its node table too, at `substeps` sub-intervals (default 4; with a StageModel only)."""
+    tm = _timed(model)
+    if tm is not None and step is not rk4_step:
+        raise ValueError("a time-dependent model and step cannot both be given")
+    if substeps is not None and tm is None:
+        raise ValueError("substeps goes with a time-dependent model (a step carries its own)")
     Bn, N, n = xb.shape
     m = ub.shape[-1]
     xprev = np.concatenate([x0[:, None, :], xb[:, :-1, :]], axis=1)
     if qp_data_on_device and (device is None or (step is not rk4_step and model is None)):
         raise ValueError("qp_data_on_device needs the device linearisation (device = 'cuda:k', the shipped rk4_step)")
     if device is not None and model is not None:
-        A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device, model=model)
+        A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device, model=model,
+                                **({} if substeps is None else dict(substeps=substeps)))
     elif device is not None and step is rk4_step:
         A, B = linearise_device(xprev, ub, dt, device, keep_on_device=qp_data_on_device)
     else:
-        A, B = linearise(xprev, ub, dt, step)
+        A, B = linearise(xprev, ub, dt, step, model=tm, substeps=substeps)
     q = np.empty((Bn, N, m + n))
     q[..., :m] = ub @ R.T
     q[:, :-1, m:] = xb[:, :-1, :] @ Q.T
@@ -463,7 +630,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
                tr_u: float = 0.1, tr_x: float = 20.0, max_outer: int = 20, tol: float = 1e-6,
                rho_reject: float = 0.1, rho_expand: float = 0.7, step=rk4_step,
                qp_options: Optional[dict] = None, linearise_on: Optional[str] = None,
-               qp_data_on_device: bool = False, outer_on_device: bool = False, model: Optional[Model] = None) -> List[ScvxResult]:
+               qp_data_on_device: bool = False, outer_on_device: bool = False, model=None) -> List[ScvxResult]:
     """scvx() for B initial conditions x0 (B, n) at once: the same trust-region loop per trajectory (own trust radii,
     own accept / reject decisions, own stop), but ONE batched QP solve per outer iteration -- per-instance dynamics,
     bounds and linear term (correction_qp_batch).  A trajectory that has stopped keeps its place in the batch with a
@@ -476,8 +643,10 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     reads one integer per outer iteration.  Same scheme, same formulas; the roundings differ (device sqrt / fma), so the result
     agrees with the host loop to the QP tolerance, not bit for bit.
     model: a Model whose step replaces `step` (not both); linearise_on then evaluates model.rhs_torch, and outer_on_device runs the
-    kernels of that model (DeviceOuterStep(model=...), the admm_scvx_*_model_device entry points)."""
+    kernels of that model (DeviceOuterStep(model=...), the admm_scvx_*_model_device entry points).  Or a StageModel, a
+    time-dependent model (4 sub-intervals per stage): the same three routes, the device one through admm_scvx_*_stage_device."""
     step = _resolve(model, step)
+    tm = _timed(model)
     x0 = np.atleast_2d(np.asarray(x0, np.float64))
     Bn = x0.shape[0]
     Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
@@ -506,7 +675,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         qp_solver = gpu_qp_solver(qp_data_on_device, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
                                                                            check_interval=25)))
     ub = np.zeros((Bn, N, m))
-    xb = rollout(x0, ub, dt, step)
+    xb = rollout(x0, ub, dt, step, model=tm)
     J = trajectory_cost(xb, ub, Q, R, QN)
     tru = np.full(Bn, float(tr_u))
     trx = np.full(Bn, float(tr_x))
@@ -524,7 +693,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         du, dx = d[..., :m], d[..., m:]
         J_lin = trajectory_cost(xb + dx, ub + du, Q, R, QN)
         u_new = np.clip(ub + du, u_lo, u_hi)
-        x_new = rollout(x0, u_new, dt, step)
+        x_new = rollout(x0, u_new, dt, step, model=tm)
         J_new = trajectory_cost(x_new, u_new, Q, R, QN)
         take, records = outer_update(J, J_lin, J_new, np.abs(du).max(axis=(1, 2)), tru, trx, active, converged, accepted,
                                      tol, rho_reject, rho_expand)
@@ -539,7 +708,8 @@ class DeviceOuterStep:
     """The state of scvx_batch(outer_on_device=True) as torch tensors on one GPU, and the four device entry points on it
     (ADMM_HIP_HAS_SCVX): rollout / init / prepare / advance.  Without `model`: the shipped model (relative_motion_rhs,
     rk4_step) through admm_scvx_*_device; with a Model: its kind and parameters in an admm_scvx_dynamics, through
-    admm_scvx_*_model_device (ADMM_HIP_HAS_SCVX_MODELS; rc is then not used).
+    admm_scvx_*_model_device (ADMM_HIP_HAS_SCVX_MODELS; rc is then not used); with a StageModel: its node table
+    of the grid (N, dt, substeps), uploaded once, in an admm_scvx_stage_dynamics, through admm_scvx_*_stage_device (§2.8.3).
     Every call is queued on torch's current stream; advance() alone waits -- for the count of trajectories still active."""
 
     STATE_F64 = ("ub", "xb", "u_cand", "x_cand", "J", "tr_u", "tr_x")
@@ -547,7 +717,7 @@ class DeviceOuterStep:
 
     def __init__(self, x0, N: int, dt: float, Q, R, QN, u_lo, u_hi, device: str = "cuda:0", substeps: int = 4, rc: float = RC_KM,
                  eps: float = 1e-6, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7, max_outer: int = 20,
-                 model: Optional[Model] = None):
+                 model=None):
         import torch
 
         from . import _abi
@@ -557,7 +727,13 @@ class DeviceOuterStep:
         x0 = np.atleast_2d(np.asarray(x0, np.float64))
         Bn = x0.shape[0]
         self.batch, self.N = Bn, int(N)
-        if model is None:
+        if isinstance(model, StageModel):
+            # the table of the grid, uploaded once; the struct holds its device pointer
+            self.nodes = torch.as_tensor(model.nodes(int(N), float(dt), int(substeps)), device=self.device)
+            self.model, self._suffix = _abi.CScvxStageDynamics(N=int(N), batch=Bn, substeps=int(substeps), kind=int(model.kind), dt=float(dt),
+                                                               nodes=self.ptr(self.nodes), n_nodes=int(self.nodes.shape[0])), "_stage_device"
+            self.model.par[:len(model.par)] = [float(v) for v in model.par]
+        elif model is None:
             self.model, self._suffix = _abi.CScvxModel(N=int(N), batch=Bn, substeps=int(substeps), dt=float(dt), rc=float(rc)), "_device"
         else:
             self.model, self._suffix = _abi.CScvxDynamics(N=int(N), batch=Bn, substeps=int(substeps), kind=int(model.kind), dt=float(dt)), "_model_device"

@@ -117,6 +117,15 @@ _SIGNATURES = {
                                                  C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
     "admm_scvx_advance_model_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxDynamics), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
                                                  C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
+    # ... for a time-dependent model (ADMM_HIP_HAS_SCVX_STAGE_MODELS): admm_scvx_stage_dynamics, which carries the node table
+    "admm_scvx_stage_model_name": (C.c_char_p, [C.c_int32]),
+    "admm_scvx_rollout_stage_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxStageDynamics), c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_scvx_init_stage_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxStageDynamics), C.POINTER(_abi.CScvxParams), c_double_p,
+                                              C.POINTER(_abi.CScvxState), C.c_double, C.c_double, C.c_void_p]),
+    "admm_scvx_prepare_stage_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxStageDynamics), C.POINTER(_abi.CScvxParams), c_double_p,
+                                                 C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
+    "admm_scvx_advance_stage_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxStageDynamics), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
+                                                 C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
     # receding-horizon step on the device (ADMM_HIP_HAS_MPC)
     "admm_mpc_advance": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p]),
     "admm_mpc_advance_device": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p, C.c_void_p]),

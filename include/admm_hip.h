@@ -415,6 +415,42 @@ int admm_scvx_prepare_model_device(int32_t device, const admm_scvx_dynamics* dyn
 int admm_scvx_advance_model_device(int32_t device, const admm_scvx_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
                                    const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
 
+/* Time-dependent models of the device outer step (new symbols, announced by
+ * ADMM_HIP_HAS_SCVX_STAGE_MODELS -- no struct or signature changed, ABI version unchanged).  A stage is integrated by classical RK4
+ * over `substeps` sub-intervals of h = dt / substeps, so the right-hand side is evaluated at the times t0 + g h / 2 of the global
+ * nodes g = 0 .. 2 substeps N: sub-interval i of stage k, g0 = 2 (substeps k + i), reads node g0 (k1), g0 + 1 (k2, k3) and g0 + 2
+ * (k4).  The model reads ADMM_SCVX_NODE_PAR doubles per node from `nodes` (n_nodes rows, row-major, GPU memory of the call's device,
+ * shared by all trajectories; n_nodes = 2 substeps N + 1).  The library computes no epoch: a caller who moves the window passes a
+ * pointer further into a longer table.  n = 6, m = 3:
+ *   ADMM_SCVX_STAGE_RELATIVE_TABULATED  exact relative motion in the rotating frame of a chief that moves in a plane, x radial,
+ *                                       y along-track, z cross-track; the node's row (rc, w, wd, g) = chief radius, angular rate,
+ *                                       angular acceleration, the chief's radial gravity mu / rc^2; par[0] = mu.  With xr = rc + x,
+ *                                       r2 = xr^2 + y^2 + z^2, k = mu / r2^(3/2):
+ *                                         ax =  2 w vy + wd y + w^2 x + g - k xr + ux
+ *                                         ay = -2 w vx - wd x + w^2 y     - k y  + uy
+ *                                         az =                            - k z  + uz
+ * The four calls are admm_scvx_{rollout,init,prepare,advance}_model_device with this struct in place of admm_scvx_dynamics: same
+ * array layouts, admm_scvx_params, admm_scvx_state and stream rules.  ADMM_ERR_INVALID names the field, before the first HIP call:
+ * dynamics.N, .batch, .substeps < 1; .dt not finite and positive; an unknown .kind; .reserved != 0; par[0] (mu) not finite and
+ * positive; par[1..3] != 0; .nodes NULL; .n_nodes != 2 substeps N + 1.  Then `nodes` is checked like every other array: memory of
+ * that device, 4 n_nodes doubles long.  Its values are not scanned: a NaN or inf propagates into the cost and the candidate is
+ * rejected.  admm_scvx_stage_model_name: "relative_tabulated"; NULL for an unknown kind. */
+#define ADMM_HIP_HAS_SCVX_STAGE_MODELS 1
+#define ADMM_SCVX_NODE_PAR 4
+enum { ADMM_SCVX_STAGE_RELATIVE_TABULATED = 0 };
+typedef struct { int32_t N, batch, substeps, kind; double dt; double par[4];
+                 const double* nodes; int64_t n_nodes; int32_t reserved; } admm_scvx_stage_dynamics;
+const char* admm_scvx_stage_model_name(int32_t kind);
+int admm_scvx_rollout_stage_device(int32_t device, const admm_scvx_stage_dynamics* dynamics, const double* x0, const double* u, double* x,
+                                   void* hip_stream);
+int admm_scvx_init_stage_device(int32_t device, const admm_scvx_stage_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                admm_scvx_state* state, double tr_u, double tr_x, void* hip_stream);
+int admm_scvx_prepare_stage_device(int32_t device, const admm_scvx_stage_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                   const admm_scvx_state* state, double* A, double* B, double* lo, double* hi, double* q,
+                                   void* hip_stream);
+int admm_scvx_advance_stage_device(int32_t device, const admm_scvx_stage_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
+                                   const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
+
 /* Receding-horizon (MPC) step on the device (new symbols, announced by ADMM_HIP_HAS_MPC -- no struct or
  * signature changed): apply the first control, propagate the plant, move the window one stage.  Per QP b, in this order:
  *   1. the state is brought into the (z, y) pair and w into memory, as admm_get does
