@@ -123,6 +123,12 @@ int admm_record_sizes_alt(int32_t n, int32_t m, int32_t* rfe, int32_t* rbe) {
   return ADMM_OK;
 }
 
+int admm_record_alloc_check(int64_t alloc_bytes, int32_t stages, int32_t stage_bytes, int64_t* needed) {
+  if (alloc_bytes < 0 || stages < 0 || stage_bytes < 0) return fail(ADMM_ERR_INVALID, "sizes must not be negative");
+  if (needed) *needed = (int64_t)rec_alloc_needed((size_t)stages, (size_t)stage_bytes);
+  return check_record_alloc("admm_record_alloc_check", (size_t)alloc_bytes, (size_t)stages, (size_t)stage_bytes);
+}
+
 int admm_host_factor_alt(const admm_problem* p, double rho, int32_t segments, double* recFE, double* recBE,
                          double* WB, int32_t* ok) {
   if (!p) return fail(ADMM_ERR_INVALID, "NULL problem");
@@ -436,8 +442,15 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   }
   const bool need_alt_buffers = h->alt_allowed;
   if (need_alt_buffers) {
-    TRY_RELEASE(dalloc(&h->recFE, h->fac.recFE.size()));
-    TRY_RELEASE(dalloc(&h->recBE, h->fac.recBE.size()));
+    // (+ 1 KiB, zeroed: the fused kernels copy a chunk of records in whole KiB pieces, admm_kernels.hpp glds_chunk)
+    h->recFE_bytes = sizeof(double) * h->fac.recFE.size() + REC_SLACK_BYTES;
+    h->recBE_bytes = sizeof(double) * h->fac.recBE.size() + REC_SLACK_BYTES;
+    TRY_RELEASE(dalloc(&h->recFE, h->recFE_bytes / sizeof(double)));
+    TRY_RELEASE(dalloc(&h->recBE, h->recBE_bytes / sizeof(double)));
+    HIP_TRY_RELEASE(hipMemset(h->recFE, 0, h->recFE_bytes));
+    HIP_TRY_RELEASE(hipMemset(h->recBE, 0, h->recBE_bytes));
+    TRY_RELEASE(check_record_alloc("admm_setup, recFE", h->recFE_bytes, (size_t)h->N, sizeof(double) * h->fac.RFE));
+    TRY_RELEASE(check_record_alloc("admm_setup, recBE", h->recBE_bytes, (size_t)h->N, sizeof(double) * h->fac.RBE));
     TRY_RELEASE(dalloc(&h->scanWpB, h->fac.scanWpB.size()));
     TRY_RELEASE(dalloc(&h->scan_rangeB, h->fac.scanRangeB.size()));
     DALLOC_WIN(h->mvec, Nmw * P, win_bias_m(h));               // db rows of the forward elimination

@@ -483,6 +483,9 @@ int upload_factor(admm_handle* h) {
   }
   if (h->has_fuel && (rc = upload_kappa(h))) return rc;             // kappa = weight / rho follows every refactor
   if (h->alt_allowed) {
+    // (the refactored records go into the allocation of admm_setup: its slack stays zero, and still covers them)
+    if ((rc = check_record_alloc("refactor, recFE", h->recFE_bytes, h->fac.recFE.size() / h->fac.RFE, sizeof(double) * h->fac.RFE))) return rc;
+    if ((rc = check_record_alloc("refactor, recBE", h->recBE_bytes, h->fac.recBE.size() / h->fac.RBE, sizeof(double) * h->fac.RBE))) return rc;
     HIP_TRY(hipMemcpy(h->recFE, h->fac.recFE.data(), sizeof(double) * h->fac.recFE.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->recBE, h->fac.recBE.data(), sizeof(double) * h->fac.recBE.size(), hipMemcpyHostToDevice));
     if (!h->scan_gemv) HIP_TRY(hipMemcpy(h->scanWpB, h->fac.scanWpB.data(), sizeof(double) * h->fac.scanWpB.size(), hipMemcpyHostToDevice));

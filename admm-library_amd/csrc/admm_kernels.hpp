@@ -101,6 +101,64 @@ __device__ __forceinline__ void stage_records(double* lds, const double* src, in
   }
 }
 
+// ---------------------------------------------------------------------------
+// Asynchronous global -> LDS copy of one chunk of records (LDS-DMA, global_load_lds_dwordx4: no staging registers,
+// no ds_write pass), shared by the MFMA family and the one-lane fused kernels (DESIGN.md §4.5 "record staging").
+// A wave-instruction moves 64 lanes x 16 B = one contiguous KiB to "M0 (wave-uniform LDS address) + lane x 16", so the
+// chunk is copied in whole KiB pieces, wave w of the WAVES waves taking pieces w, w + WAVES, ...: an LDS buffer is
+// rounded up to a KiB (glds_lds_bytes) and every device array of records carries a KiB of slack (GLDS_SLACK_BYTES),
+// because the last piece runs up to 1008 bytes past the chunk on both sides.
+// Issued through inline asm ON PURPOSE: with an LDS-DMA it knows of in flight, hipcc (ROCm 7.2) turns every counted
+// `s_waitcnt vmcnt(N)` into vmcnt(0) (cdna_hip_programming.md §5, "Pipelining across barriers") -- in the stage loop
+// that made each stage wait for the previous stage's v+ STORES before touching its prefetched operands (measured:
+// 371 us per launch instead of ~300 at n = 12, MFMA family).  Hidden from the compiler, the DMA is still counted by
+// the hardware: a counted wait can only over-wait (the DMA is younger than the loads it is waiting for), never
+// under-wait, and the buffer being filled is not read before a retire + the barrier that ends the current chunk.
+// ---------------------------------------------------------------------------
+constexpr int GLDS_SLACK_BYTES = 1024;
+constexpr int glds_lds_bytes(int chunk_bytes) { return ((chunk_bytes + 1023) / 1024) * 1024; }
+
+template <int WAVES>
+__device__ __forceinline__ void glds_chunk(const unsigned char* src, unsigned char* lds_dst, int bytes, int wave, int lane) {
+  const int pieces = (bytes + 1023) >> 10;
+  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds_dst;
+  for (int p = wave; p < pieces; p += WAVES) {
+    const unsigned char* gsrc = src + (size_t)p * 1024 + lane * 16;
+    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)p * 1024u);
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
+  }
+}
+// every LDS-DMA of this wave has landed (then a barrier makes the other waves' pieces visible too)
+__device__ __forceinline__ void glds_retire() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// The same without a drain: vector-memory operations of a wave retire in issue order (one counter for loads, stores and
+// LDS-DMA on gfx9-class hardware), so "at most N outstanding" retires every DMA that at least N vector-memory
+// instructions of this wave have been issued after -- and waits for nothing younger than those N.
+// Through the builtin, not asm: the compiler reads an s_waitcnt it can see into its own bookkeeping.  An asm wait leaves it
+// believing that the loads issued before a loop are still in flight at the loop's entry, and it then waits for the ring loads
+// of EVERY stage with the small counts that would be right on that entry path only (vmcnt(2), (1), (0) at the top of each
+// stage instead of vmcnt(11): a drain of the previous stage's stores per stage).
+template <int N>
+__device__ __forceinline__ void glds_retire_older() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit count");
+  asm volatile("" ::: "memory");      // (no load or store moves across the wait: the count is about program order)
+  __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));      // gfx9 encoding: vmcnt(N), expcnt and lgkmcnt untouched
+  asm volatile("" ::: "memory");
+}
+
+// Two LDS buffers of the one-lane fused kernels (double-buffered record staging): stages per buffer such that BOTH buffers,
+// each with the 16-double tail dpp_op_load may read and rounded up to a KiB, fit the 64 KiB of stage_chunk's single
+// buffer (two workgroups per CU still fit); a multiple of the prefetch depth, capped like stage_chunk.
+constexpr int stage_chunk2(int rec_doubles, int pf) {
+  int ch = (4096 - 16) / rec_doubles;
+  if (ch > 128) ch = 128;
+  ch = (ch / pf) * pf;
+  if (ch < pf) ch = pf;
+  return ch;
+}
+constexpr int stage_buf_doubles(int rec_doubles, int ch) { return glds_lds_bytes((ch * rec_doubles + 16) * 8) / 8; }
+
 // Per-stage matrices are wave-uniform; reading them through the constant
 // address space makes hipcc select scalar (SMEM) loads for them.
 typedef const __attribute__((address_space(4))) double* cdouble_p;

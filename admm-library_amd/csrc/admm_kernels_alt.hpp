@@ -17,7 +17,7 @@
 // against 29.33 for xb + xfz (each elimination leaves only its m-row feed-forward term per stage).
 //     lean residual form (LEAN = NR | NW | SD, consecutive residual iterations, unbounded state rows):
 //           d / db read 2.67 + v_u read 2.67 + w_u,old read 2.67 + v_u+ written 2.67 + w_u written 2.67 + db / d written 2.67 = 16
-// Same layout, staging and addressing as admm_kernels.hpp.
+// Same layout and addressing as admm_kernels.hpp; the records are staged asynchronously (alt_retire_chunk below).
 #pragma once
 
 #include "admm_kernels.hpp"
@@ -112,8 +112,42 @@ constexpr bool alt_dims(int nx, int nu) { return nx >= 1 && nu >= 1; }
 // Compiled for the headline shapes without q and without the thrust bound; anything else runs the full forms.
 // (ALT_LEAN_NR / _NW / _SD and alt_lean_dims(): admm_dispatch.hpp, shared with the runtime.)
 
-// Sum of the (<= 8) split-K slabs of one scan output row (see xf_kernel).
+// Record staging of the two fused kernels (DESIGN.md §4.5 "record staging"): the records of a segment reach LDS chunk by
+// chunk through the LDS-DMA of admm_kernels.hpp into two buffers -- chunk 0 is the first thing a kernel issues, chunk c + 1
+// is issued behind the barrier that opens chunk c and lands while chunk c's stages run, so a chunk switch is one barrier
+// and no wave ever drains its state prefetch for the records.
+// Vector-memory instructions a wave issues per stage (loads of the prefetch ring + stores); ALT_V*: rows of v loaded / stored.
+constexpr int alt_vm_per_stage(int nx, int nu, bool hasq, bool l_nr, bool l_sd, int v_loaded, int v_stored) {
+  return nu + (l_nr ? nu : 0) + v_loaded + (hasq ? nx + nu : 0) + v_stored + (l_sd ? nu : 0) + nu;
+}
+// Retire of the chunk in flight, at the end of the chunk before it (a full chunk: CH stages).  The DMA was issued before
+// every load and store of those CH stages, so with CH >= 2 at least two stages' worth of vector-memory instructions are
+// younger than it: "at most one stage's worth outstanding" retires it and waits for nothing the last stage issued.
+template <int CH, int PER_STAGE>
+__device__ __forceinline__ void alt_retire_chunk() {
+  if constexpr (CH >= 2) glds_retire_older<(PER_STAGE < 63 ? PER_STAGE : 63)>();
+  else glds_retire_older<0>();
+}
+
+// A value loaded before the stage loop, pinned in front of the head's wait.  The loads of the ring's first stage are only
+// used inside the loop, and the compiler is free to sink them below the wait (the arrays are __restrict__: no asm memory
+// clobber holds them) -- it then believes them still in flight at the loop's entry and waits for the ring loads of EVERY stage
+// with the small counts that would be right on that entry path only (vmcnt(2), (1), (0) at the top of each stage, a drain of
+// the previous stage's stores, instead of vmcnt(11)).  Reading the value here puts the load, and the compiler's own wait for
+// it, before the loop.
+__device__ __forceinline__ void alt_pin(double& v) { asm volatile("" : "+v"(v)); }
+
+// The lane id, recomputed at each use (volatile: not kept live in a register across the stage loop, where every register counts).
+__device__ __forceinline__ int alt_lane() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
+// Sum of the (<= 8) split-K slabs of one scan output row (see xf_kernel); one slab (every batch above a handful of QPs):
+// one load instead of eight.
 __device__ __forceinline__ double scan_row(const double* base, size_t o, int nsplit, size_t split_stride) {
+  if (nsplit == 1) return base[o];          // wave-uniform branch
   double p[8];
 #pragma unroll
   for (int sp = 0; sp < 8; ++sp) p[sp] = base[(size_t)(sp < nsplit ? sp : 0) * split_stride + o];
@@ -147,20 +181,22 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   constexpr int RF = LF.SIZE;
   constexpr int PF = alt_pf_f(NB, HASQ, SOC, XFREE);
   [[maybe_unused]] constexpr int ALT_G = alt_g_f(NB);
-  constexpr int CH = stage_chunk(RF, PF);
-  __shared__ __attribute__((aligned(16))) double rec[CH * RF + 16];      // (+ 16: the distributed read of the last stage's last register)
+  constexpr int CH = stage_chunk2(RF, PF);       // stages per LDS buffer
+  constexpr int BUFD = stage_buf_doubles(RF, CH);      // (incl. 16: the distributed read of the last stage's last register)
+  static_assert(2 * BUFD * 8 <= 65536 || CH == PF, "the two record buffers share the 64 KiB of the single one");
+  __shared__ __attribute__((aligned(16))) double recs[2 * BUFD];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar; the lane id is recomputed where needed: alt_lane)
   // operators distributed over the lanes of a row (dpp_matvec_acc, admm_kernels.hpp), read from LDS two operators ahead of
   // their FMAs (ADMM_LD): PSI, K, A, B | z-update | DK, DG, OB, FM, GA, PI, then PSI, K of the next stage
   constexpr int NREG = (LF.LO + 15) / 16;
   double ops[NREG];
-  const double* rec16 = rec + (threadIdx.x & 15);
 #if ADMM_DPP_OPERANDS
 #define ADMM_MV(R_, C_, NEG_, BLK_, X_, ACC_) dpp_matvec_acc<R_, C_, NEG_, LF.BLK_, NREG>(ops, X_, ACC_)
 #define ADMM_LD(R_, C_, BLK_, PTR_) dpp_op_load<LF.BLK_, (R_) * (C_), NREG>(PTR_, ops)
 #else
 #define ADMM_MV(R_, C_, NEG_, BLK_, X_, ACC_) lds_matvec_acc<R_, C_, NEG_, ALT_G>(rf + LF.BLK_, X_, ACC_)
 #define ADMM_LD(R_, C_, BLK_, PTR_) (void)(PTR_)
-  (void)rec16; (void)ops;
+  (void)ops;
 #endif
 
   const int col_raw = grid_col_block() * XB_THREADS + threadIdx.x;
@@ -169,6 +205,9 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   const int s = grid_segment();
   cint_p seg_start = as_const(seg_start_);
   const int k0 = seg_start[s], k1 = seg_start[s + 1];
+  // the first chunk of records, before anything else is asked of memory (the records do not depend on the scan)
+  glds_chunk<XB_THREADS / 64>(reinterpret_cast<const unsigned char*>(recFE + (size_t)k0 * RF), reinterpret_cast<unsigned char*>(recs),
+                              ((k1 - k0 < CH) ? k1 - k0 : CH) * RF * 8, wave, alt_lane());
   const size_t P = (size_t)pitch;
   const unsigned lb = (unsigned)col * 8u;
   const unsigned PB = (unsigned)pitch * 8u;
@@ -223,11 +262,39 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
     }
   }
   double a_r = 0, a_s = 0, a_w = 0, a_z = 0, a_y = 0;
+  constexpr int V_LOADED = (XFREE && (!RESID || L_NR)) ? NU : NB, V_STORED = (XFREE == 2 || (XFREE && L_NW)) ? NU : NB;
+  constexpr int VM_STAGE = alt_vm_per_stage(NX, NU, HASQ, L_NR, L_SD, V_LOADED, V_STORED);
+  int buf = 0;
+  // A chunk's records have landed when its stages begin: this wave's pieces by a retire -- the first chunk's here (the head's
+  // loads are all due in the first stage anyway), a later chunk's at the end of the chunk before it, without a drain -- and
+  // the other waves' pieces by the barrier, which also ends every read of the other buffer.
+  // (the head's ring loads are issued BEFORE the wait: alt_pin -- in the forms on the 256-register budget; the others have no
+  //  register to spare for it at the head and keep the conservative waits)
+  if constexpr (alt_min_waves(NB, HASQ, SOC) >= 2)
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+#pragma unroll
+    for (int jj = 0; jj < NU; ++jj) {
+      alt_pin(ld[j][jj]);
+      if (L_NR) alt_pin(lw[j][jj]);
+    }
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      if (!(XFREE && (!RESID || L_NR) && r >= NU)) alt_pin(l0[j][r]);
+      if (HASQ) alt_pin(lq[j][r]);
+    }
+  }
+  glds_retire_older<0>();
   for (int kc = k0; kc < k1; kc += CH) {
     const int khi = (kc + CH - 1 < k1 - 1) ? kc + CH - 1 : k1 - 1;
     __syncthreads();
-    stage_records<XB_THREADS>(rec, recFE + (size_t)kc * RF, (khi - kc + 1) * RF, threadIdx.x);
-    __syncthreads();
+    const double* rec = recs + buf * BUFD;
+    [[maybe_unused]] const double* rec16 = rec + (alt_lane() & 15);
+    if (khi + 1 < k1)                                  // the next chunk, in flight while this one's stages run
+      glds_chunk<XB_THREADS / 64>(reinterpret_cast<const unsigned char*>(recFE + (size_t)(khi + 1) * RF),
+                                  reinterpret_cast<unsigned char*>(recs + (buf ^ 1) * BUFD),
+                                  ((k1 - khi - 1 < CH) ? k1 - khi - 1 : CH) * RF * 8, wave, alt_lane());
+    buf ^= 1;
     ADMM_LD(NU, NX, PSI, rec16);                       // the chunk's first stage (later ones: at the end of their predecessor)
     ADMM_LD(NU, NX, K, rec16);
     for (int kb = kc; kb <= khi; kb += PF) {
@@ -407,6 +474,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    alt_retire_chunk<CH, VM_STAGE>();      // the next chunk's records (behind the last chunk: nothing to retire, and nothing waited for)
   }
   if (col_raw < pitch) {
     const size_t o = (size_t)s * NX * P + col;
@@ -454,20 +522,22 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   constexpr int RB = LB.SIZE;
   constexpr int PF = alt_pf_b(NB, XFREE, HASQ, SOC);
   [[maybe_unused]] constexpr int ALT_G = alt_g_b(NB);
-  constexpr int CH = stage_chunk(RB, PF);
-  __shared__ __attribute__((aligned(16))) double rec[CH * RB + 16];
+  constexpr int CH = stage_chunk2(RB, PF);       // stages per LDS buffer (record staging: see xfze_kernel)
+  constexpr int BUFD = stage_buf_doubles(RB, CH);
+  static_assert(2 * BUFD * 8 <= 65536 || CH == PF, "the two record buffers share the 64 KiB of the single one");
+  __shared__ __attribute__((aligned(16))) double recs[2 * BUFD];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // (scalar; the lane id is recomputed where needed: alt_lane)
   // operators distributed over the lanes of a row, read two operators ahead of their FMAs (see xfze_kernel):
   // PSB, KB, AI, AIB | z-update | BT, SI, AT, KT, OM, then PSB, KB of the next (= previous in time) stage
   constexpr int NREG = (LB.LO + 15) / 16;
   double ops[NREG];
-  const double* rec16 = rec + (threadIdx.x & 15);
 #if ADMM_DPP_OPERANDS
 #define ADMM_MV(R_, C_, NEG_, BLK_, X_, ACC_) dpp_matvec_acc<R_, C_, NEG_, LB.BLK_, NREG>(ops, X_, ACC_)
 #define ADMM_LD(R_, C_, BLK_, PTR_) dpp_op_load<LB.BLK_, (R_) * (C_), NREG>(PTR_, ops)
 #else
 #define ADMM_MV(R_, C_, NEG_, BLK_, X_, ACC_) lds_matvec_acc<R_, C_, NEG_, ALT_G>(rb + LB.BLK_, X_, ACC_)
 #define ADMM_LD(R_, C_, BLK_, PTR_) (void)(PTR_)
-  (void)rec16; (void)ops;
+  (void)ops;
 #endif
 
   const int col_raw = grid_col_block() * XB_THREADS + threadIdx.x;
@@ -476,6 +546,11 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
   const int s = grid_segment();
   cint_p seg_start = as_const(seg_start_);
   const int k0 = seg_start[s], k1 = seg_start[s + 1];
+  {  // the first chunk of records (the segment's LAST stages), before anything else is asked of memory
+    const int klo = (k1 - CH > k0) ? k1 - CH : k0;
+    glds_chunk<XB_THREADS / 64>(reinterpret_cast<const unsigned char*>(recBE + (size_t)klo * RB), reinterpret_cast<unsigned char*>(recs),
+                                (k1 - klo) * RB * 8, wave, alt_lane());
+  }
   const size_t P = (size_t)pitch;
   const unsigned lb = (unsigned)col * 8u;
   const unsigned PB = (unsigned)pitch * 8u;
@@ -535,11 +610,37 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
     }
   }
   double a_r = 0, a_s = 0, a_w = 0, a_z = 0, a_y = 0;
+  constexpr int V_LOADED = (XFREE && (!RESID || L_NR)) ? NU : NB, V_STORED = (XFREE == 2 || (XFREE && L_NW)) ? NU : NB;
+  constexpr int VM_STAGE = alt_vm_per_stage(NX, NU, HASQ, L_NR, L_SD, V_LOADED, V_STORED);
+  int buf = 0;
+  // (the head's ring loads are issued BEFORE the wait: alt_pin -- in the forms on the 256-register budget; the others have no
+  //  register to spare for it at the head and keep the conservative waits)
+  if constexpr (alt_min_waves(NB, HASQ, SOC) >= 2)
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) {
+      alt_pin(lm[j][i]);
+      if (L_NR) alt_pin(lw[j][i]);
+    }
+#pragma unroll
+    for (int r = 0; r < NB; ++r) {
+      if (!(XFREE && (!RESID || L_NR) && r >= NU)) alt_pin(l0[j][r]);
+      if (HASQ) alt_pin(lq[j][r]);
+    }
+  }
+  glds_retire_older<0>();                                // the first chunk's records have landed (see xfze_kernel)
   for (int kc = k1 - 1; kc >= k0; kc -= CH) {
     const int klo = (kc - CH + 1 > k0) ? kc - CH + 1 : k0;
     __syncthreads();
-    stage_records<XB_THREADS>(rec, recBE + (size_t)klo * RB, (kc - klo + 1) * RB, threadIdx.x);
-    __syncthreads();
+    const double* rec = recs + buf * BUFD;
+    [[maybe_unused]] const double* rec16 = rec + (alt_lane() & 15);
+    if (klo > k0) {                                      // the next chunk (earlier stages), in flight while this one's stages run
+      const int nlo = (klo - CH > k0) ? klo - CH : k0;
+      glds_chunk<XB_THREADS / 64>(reinterpret_cast<const unsigned char*>(recBE + (size_t)nlo * RB),
+                                  reinterpret_cast<unsigned char*>(recs + (buf ^ 1) * BUFD), (klo - nlo) * RB * 8, wave, alt_lane());
+    }
+    buf ^= 1;
     ADMM_LD(NU, NX, PSB, rec16 + (kc - klo) * RB);       // the chunk's first (= last in time) stage
     ADMM_LD(NU, NX, KB, rec16 + (kc - klo) * RB);
     for (int kb = kc; kb >= klo; kb -= PF) {
@@ -706,6 +807,7 @@ __global__ __launch_bounds__(XB_THREADS) ADMM_ALT_OCCUPANCY(NX + NU, HASQ, SOC) 
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    alt_retire_chunk<CH, VM_STAGE>();      // the next chunk's records (see xfze_kernel)
   }
   if (col_raw < pitch) {
     const size_t o = (size_t)s * NX * P + col;

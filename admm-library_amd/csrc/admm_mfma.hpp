@@ -70,32 +70,10 @@ constexpr int mfma_chunk(int rec_bytes, int pf) {
   return ch < pf ? pf : ch;
 }
 
-// Asynchronous global -> LDS copy of one chunk of records (LDS-DMA, global_load_lds_dwordx4: no staging registers,
-// no ds_write pass).  A wave-instruction moves 64 lanes x 16 B = one contiguous KiB to "M0 (wave-uniform LDS
-// address) + lane x 16", so the chunk is copied in whole KiB pieces, wave w taking pieces w, w + 8, ...: the LDS
-// buffers are rounded up to a KiB and the device arrays carry a KiB of slack, so the last piece may run past the
-// chunk.
-// Issued through inline asm ON PURPOSE: with an LDS-DMA it knows of in flight, hipcc (ROCm 7.2) turns every counted
-// `s_waitcnt vmcnt(N)` into vmcnt(0) (cdna_hip_programming.md §5, "Pipelining across barriers") -- in the stage loop
-// that made each stage wait for the previous stage's v+ STORES before touching its prefetched operands (measured:
-// 371 us per launch instead of ~300 at n = 12).  Hidden from the compiler, the DMA is still counted by the hardware:
-// a counted wait can only over-wait (the DMA is younger than the loads it is waiting for), never under-wait, and the
-// chunk that is being filled is not read before glds_retire() + the barrier that ends the current chunk.
-constexpr int mfma_lds_bytes(int chunk_bytes) { return ((chunk_bytes + 1023) / 1024) * 1024; }
-
-__device__ __forceinline__ void glds_chunk(const unsigned char* src, unsigned char* lds_dst, int bytes, int wave, int lane) {
-  const int pieces = (bytes + 1023) >> 10;
-  const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds_dst;
-  for (int p = wave; p < pieces; p += MF_THREADS / 64) {
-    const unsigned char* gsrc = src + (size_t)p * 1024 + lane * 16;
-    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)p * 1024u);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(dst) : "memory");
-  }
-}
-// every LDS-DMA of this wave has landed (then a barrier makes the other waves' pieces visible too)
-__device__ __forceinline__ void glds_retire() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+// Asynchronous, double-buffered global -> LDS copy of the record chunks: glds_chunk / glds_retire of admm_kernels.hpp
+// (shared with the one-lane fused kernels), the eight waves taking the KiB pieces w, w + 8, ...  The chunk that is being
+// filled is not read before glds_retire() + the barrier that ends the current chunk.
+constexpr int mfma_lds_bytes(int chunk_bytes) { return glds_lds_bytes(chunk_bytes); }
 
 // One register (4 rows x 16 QPs) of the z-update, dual ascent and residual partials; returns v+ and the linear
 // term g = -rho (z+ - y+) of the next x-update.  Padding slots carry c0 = w = 0 and the box (-inf, inf): every
@@ -249,14 +227,14 @@ __global__ __launch_bounds__(MF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) load_stage(k0 + j, j, nt);
 
-  glds_chunk(recMF + (size_t)k0 * RM, lds[0], ((k1 - k0 < CH) ? k1 - k0 : CH) * RM, wave, lane);
+  glds_chunk<MF_THREADS / 64>(recMF + (size_t)k0 * RM, lds[0], ((k1 - k0 < CH) ? k1 - k0 : CH) * RM, wave, lane);
   glds_retire();
   __syncthreads();
   int buf = 0;
   for (int kc = k0; kc < k1; kc += CH) {
     const int khi = (kc + CH < k1) ? kc + CH : k1;               // this chunk: stages kc .. khi-1
     const int nnext = (khi < k1) ? ((khi + CH < k1 ? CH : k1 - khi) * RM) : 0;
-    if (nnext) glds_chunk(recMF + (size_t)khi * RM, lds[buf ^ 1], nnext, wave, lane);   // next chunk, in flight during this one
+    if (nnext) glds_chunk<MF_THREADS / 64>(recMF + (size_t)khi * RM, lds[buf ^ 1], nnext, wave, lane);   // next chunk, in flight during this one
     for (int kb = kc; kb < khi; kb += MF_PF) {
 #pragma unroll
      for (int j = 0; j < MF_PF; ++j) {
@@ -520,7 +498,7 @@ __global__ __launch_bounds__(MF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
 
   {  // first chunk: stages k1-CH .. k1-1 (clipped at k0); LDS slot j = k - klo
     const int klo = (k1 - CH > k0) ? k1 - CH : k0;
-    glds_chunk(recMB + (size_t)klo * RM, lds[0], (k1 - klo) * RM, wave, lane);
+    glds_chunk<MF_THREADS / 64>(recMB + (size_t)klo * RM, lds[0], (k1 - klo) * RM, wave, lane);
   }
   glds_retire();
   __syncthreads();
@@ -529,7 +507,7 @@ __global__ __launch_bounds__(MF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     const int klo = (kc - CH > k0) ? kc - CH : k0;
     const int nlo = (klo - CH > k0) ? klo - CH : k0;           // next chunk: stages nlo .. klo-1
     const int nnext = (klo > k0) ? (klo - nlo) * RM : 0;
-    if (nnext) glds_chunk(recMB + (size_t)nlo * RM, lds[buf ^ 1], nnext, wave, lane);
+    if (nnext) glds_chunk<MF_THREADS / 64>(recMB + (size_t)nlo * RM, lds[buf ^ 1], nnext, wave, lane);
     for (int kb = kc - 1; kb >= klo; kb -= MF_PF) {
 #pragma unroll
      for (int j = 0; j < MF_PF; ++j) {

@@ -100,6 +100,7 @@ struct admm_handle {
   int *scan_rows = nullptr, *scan_rowsB = nullptr;
   // alternating-direction iteration
   double *recFE = nullptr, *recBE = nullptr, *mvec = nullptr, *scanWpB = nullptr;
+  size_t recFE_bytes = 0, recBE_bytes = 0;     // allocated, incl. the slack of the LDS-DMA copy (check_record_alloc below)
   int* scan_rangeB = nullptr;
   // MFMA form of the fused kernels: fragment records, mode (0 = not in use, 1 mixed, 2 fp64), and whether
   // launch_x currently routes to it (the fp64 refinement phase of a MIXED solve turns it off)
@@ -246,6 +247,19 @@ int dalloc(T** p, size_t count) {
   return ADMM_OK;
 }
 
+
+// Device arrays of stage records that a kernel stages by LDS-DMA (glds_chunk, admm_kernels.hpp: recFE / recBE, recMF / recMB):
+// a chunk is copied in whole KiB pieces, so its last piece reads up to 1008 bytes past the chunk -- past the ARRAY for the
+// last chunk.  Such an array is allocated with a KiB of (zeroed) slack, and every set-up and every upload checks that the
+// allocation covers stages x stage_bytes rounded up to the next KiB (admm_record_alloc_check: the same test, host only).
+constexpr size_t REC_SLACK_BYTES = 1024;
+inline size_t rec_alloc_needed(size_t stages, size_t stage_bytes) { return (stages * stage_bytes + 1023) / 1024 * 1024; }
+inline int check_record_alloc(const char* what, size_t alloc_bytes, size_t stages, size_t stage_bytes) {
+  if (alloc_bytes >= rec_alloc_needed(stages, stage_bytes)) return ADMM_OK;
+  return fail(ADMM_ERR_INVALID, std::string(what) + ": " + std::to_string(alloc_bytes) + " bytes allocated for " + std::to_string(stages) +
+              " stage records of " + std::to_string(stage_bytes) + " bytes; the KiB-wise LDS-DMA copy reads up to " +
+              std::to_string(rec_alloc_needed(stages, stage_bytes)));
+}
 
 // ---- launches, exchange and iteration forms (admm_launch.hip)
 admm::XLaunch xlaunch_of(const admm_handle* h);

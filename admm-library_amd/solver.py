@@ -132,6 +132,7 @@ _SIGNATURES = {
     "admm_record_sizes_alt": (C.c_int, [C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_alt": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, c_double_p, c_double_p,
                                        c_double_p, c_int32_p]),
+    "admm_record_alloc_check": (C.c_int, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "admm_mfma_record_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
     "admm_host_factor_mfma": (C.c_int, [C.POINTER(CProblem), C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                         c_int32_p]),

@@ -644,6 +644,11 @@ int admm_host_scan_matrices_timeshard(const admm_problem* p, double rho, int32_t
 int admm_record_sizes_alt(int32_t n, int32_t m, int32_t* rfe, int32_t* rbe);
 int admm_host_factor_alt(const admm_problem* p, double rho, int32_t segments, double* recFE, double* recBE,
                          double* WB, int32_t* ok);
+/* The fused kernels copy these records to on-chip memory in whole KiB pieces, so a device array of them is allocated with a
+ * KiB of slack behind `stages` records of `stage_bytes` bytes.  This is the test admm_setup and every refactor apply to their
+ * allocations (host only): ADMM_ERR_INVALID if alloc_bytes does not cover stages * stage_bytes rounded up to the next KiB
+ * (*needed, may be NULL). */
+int admm_record_alloc_check(int64_t alloc_bytes, int32_t stages, int32_t stage_bytes, int64_t* needed);
 
 /* MFMA form (csrc/admm_mfma_layout.hpp): bytes per stage of the forward / backward fragment
  * records of mode ADMM_PRECISION_MIXED or ADMM_PRECISION_FP64_MFMA, and the records themselves (N * bytes each;
