@@ -100,6 +100,10 @@ class CScvxState(C.Structure):          # admm_scvx_state: device pointers
                [("history", c_double_p), ("history_capacity", C.c_int32)]
 
 
+class CScvxAdjointOut(C.Structure):     # admm_scvx_adjoint_out: device pointers, any may be NULL, not all
+    _fields_ = [(k, c_double_p) for k in ("nu", "primer", "grad", "dJdx0", "stat")] + [("n_bound", c_int32_p)]
+
+
 class CMpcStep(C.Structure):            # admm_mpc_step (Ap, Bp: host arrays; the rest host or device memory by the entry point)
     _fields_ = [(k, c_double_p) for k in ("Ap", "Bp", "du", "dx", "x_meas", "q_tail")] + \
                [("tail", C.c_int32), ("reserved", C.c_int32)]

@@ -397,6 +397,18 @@ def linearise_device(xprev: np.ndarray, u: np.ndarray, dt: float, device: str = 
 
 
 @dataclasses.dataclass
+class ScvxCertificate:
+    """Costates and the first-order optimality measure of the NONLINEAR problem at a trajectory (adjoint()).  NumPy
+    arrays from adjoint(), torch tensors from DeviceOuterStep.certify(); with a leading batch axis where the trajectory had one."""
+    nu: object                    # (N, 6): nu[k] = nu_{k+1}, the costate of stage k's dynamics (sign and indexing of DESIGN.md §2.9)
+    primer: object                # (N, 3): B_k' nu_{k+1}
+    grad: object                  # (N, 3): dJ/du_k at fixed x0 = R u_k - primer_k
+    dJdx0: object                 # (6,): dJ/dx_0 at fixed u = -A_0' nu_1
+    stat: object                  # the largest violation of first-order optimality over the components of u in their box
+    n_bound: object               # the number of components of u on a bound
+
+
+@dataclasses.dataclass
 class ScvxResult:
     u: np.ndarray                 # (N, m) controls
     x: np.ndarray                 # (N, n) states x_1..x_N of the NONLINEAR dynamics under u
@@ -405,6 +417,7 @@ class ScvxResult:
     accepted: int
     converged: bool
     history: List[dict]           # per outer iteration: cost, predicted / actual decrease, ratio, trust radius, |du|, ADMM iterations
+    certificate: Optional[ScvxCertificate] = None      # with certify=True: adjoint() at (x, u)
 
 
 def trajectory_cost(x: np.ndarray, u: np.ndarray, Q, R, QN):
@@ -413,6 +426,62 @@ def trajectory_cost(x: np.ndarray, u: np.ndarray, Q, R, QN):
     c = c + 0.5 * np.einsum("...ki,ij,...kj->...", x[..., :-1, :], Q, x[..., :-1, :])
     c = c + 0.5 * np.einsum("...i,ij,...j->...", x[..., -1, :], QN, x[..., -1, :])
     return float(c) if np.ndim(c) == 0 else c
+
+
+def stationarity(grad: np.ndarray, u: np.ndarray, u_lo, u_hi) -> Tuple[np.ndarray, np.ndarray]:
+    """(stat, n_bound) of ScvxCertificate from the reduced gradient grad (..., N, 3) at the controls u in the box [u_lo, u_hi]
+    (per axis), comparisons exact: a component violates first-order optimality by 0 if u_lo == u_hi, by max(-g, 0) on its lower
+    bound, max(g, 0) on its upper bound and |g| elsewhere; stat is the maximum over (k, j) -- NaN if any entry of grad is a NaN."""
+    grad, u = np.asarray(grad, np.float64), np.asarray(u, np.float64)
+    lo = np.broadcast_to(np.asarray(u_lo, np.float64), (u.shape[-1],))
+    hi = np.broadcast_to(np.asarray(u_hi, np.float64), (u.shape[-1],))
+    at_lo, at_hi = u == lo, u == hi
+    v = np.where(at_lo, np.maximum(-grad, 0.0), np.where(at_hi, np.maximum(grad, 0.0), np.abs(grad)))
+    v = np.where(lo == hi, 0.0, v)
+    stat = np.where(np.isnan(grad).any(axis=(-1, -2)), np.nan, np.nan_to_num(v, nan=0.0).max(axis=(-1, -2)))
+    return stat, (at_lo | at_hi).sum(axis=(-1, -2)).astype(np.int32)
+
+
+def adjoint(x0: np.ndarray, u: np.ndarray, x: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi, step=rk4_step, model=None,
+            eps: float = 1e-6, A: Optional[np.ndarray] = None, B: Optional[np.ndarray] = None) -> ScvxCertificate:
+    """The discrete adjoint of trajectory_cost(rollout(x0, u), u) at the trajectory (x0, u, x = x_1 .. x_N), with or without a
+    leading batch axis: costates, primer vector, reduced gradient dJ/du at fixed x0, dJ/dx0 at fixed u, and the first-order
+    optimality measure of u in its box (stationarity) -- the host reference of admm_scvx_adjoint_device.
+
+        nu_N = -QN x_N,    nu_{k+1} = A_{k+1}' nu_{k+2} - Q x_{k+1}  (k = N-2 .. 0),    primer_k = B_k' nu_{k+1},
+        grad_k = R u_k - primer_k,    dJdx0 = -A_0' nu_1                                (Q, R, QN symmetric)
+
+    A (..., N, 6, 6), B (..., N, 6, 3): the stage Jacobians at (x_k, u_k); by default linearise(...) of step / model at `eps`
+    (model, step: as in rollout)."""
+    u, x = np.asarray(u, np.float64), np.asarray(x, np.float64)
+    x0 = np.asarray(x0, np.float64)
+    Q, R, QN = (np.asarray(a, np.float64) for a in (Q, R, QN))
+    single = u.ndim == 2
+    if single:
+        u, x, x0 = u[None], x[None], x0[None]
+        A, B = (None if a is None else np.asarray(a)[None] for a in (A, B))
+    if (A is None) != (B is None):
+        raise ValueError("adjoint: A and B go together")
+    if A is None:
+        xprev = np.concatenate([x0[:, None, :], x[:, :-1, :]], axis=1)
+        A, B = linearise(xprev, u, dt, step, eps, model=model)
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    Bn, N, m = u.shape
+    n = x.shape[-1]
+    qu = u @ R.T
+    qx = x @ Q.T
+    qx[:, -1] = x[:, -1] @ QN.T
+    nu = np.empty((Bn, N, n))
+    nu[:, -1] = -qx[:, -1]
+    for k in range(N - 2, -1, -1):
+        nu[:, k] = np.einsum("bji,bj->bi", A[:, k + 1], nu[:, k + 1]) - qx[:, k]
+    primer = np.einsum("bkij,bki->bkj", B, nu)
+    grad = qu - primer
+    dJdx0 = -np.einsum("bji,bj->bi", A[:, 0], nu[:, 0])
+    stat, n_bound = stationarity(grad, u, u_lo, u_hi)
+    if single:
+        return ScvxCertificate(nu[0], primer[0], grad[0], dJdx0[0], float(stat[0]), int(n_bound[0]))
+    return ScvxCertificate(nu, primer, grad, dJdx0, stat, n_bound)
 
 
 def correction_qp(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
@@ -480,7 +549,7 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
          qp_solver: Optional[Callable[[Problem], Tuple[np.ndarray, int]]] = None,
          u_init: Optional[np.ndarray] = None, tr_u: float = 0.1, tr_x: float = 20.0,
          max_outer: int = 20, tol: float = 1e-6, rho_reject: float = 0.1, rho_expand: float = 0.7,
-         step=rk4_step, qp_options: Optional[dict] = None, model=None) -> ScvxResult:
+         step=rk4_step, qp_options: Optional[dict] = None, model=None, certify: bool = False) -> ScvxResult:
     """Trust-region successive convexification of
 
         minimise 1/2 sum_k [u_k' R u_k + x_{k+1}' Q_{k+1} x_{k+1}]   s.t.  x_{k+1} = F(x_k, u_k),  u_lo <= u_k <= u_hi.
@@ -489,7 +558,8 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     A step is accepted when actual / predicted cost decrease >= rho_reject (trust radii halve
     otherwise, double above rho_expand); stops when the accepted correction is below `tol`.
     model: a Model (relative_circular(), crtbp(...)) whose step replaces `step`; not both.  Or a StageModel (relative_elliptic(...),
-    relative_tabulated(...)): a time-dependent model, whose stages read the node table of the grid (N, dt, 4 sub-intervals)."""
+    relative_tabulated(...)): a time-dependent model, whose stages read the node table of the grid (N, dt, 4 sub-intervals).
+    certify: the result carries adjoint() at the returned trajectory (ScvxResult.certificate); nothing else changes."""
     step = _resolve(model, step)
     tm = _timed(model)
     x0 = np.asarray(x0, np.float64)
@@ -536,8 +606,9 @@ def scvx(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         if rec["accepted"] and step_norm <= tol:
             converged = True
             break
+    cert = adjoint(x0, ub, xb, dt, Q, R, QN, u_lo, u_hi, step, model=tm) if certify else None
     return ScvxResult(u=ub, x=xb, cost=J, outer_iterations=len(hist), accepted=accepted, converged=converged,
-                      history=hist)
+                      history=hist, certificate=cert)
 
 
 def correction_qp_batch(xb: np.ndarray, ub: np.ndarray, x0: np.ndarray, dt: float, Q, R, QN, u_lo, u_hi,
@@ -630,7 +701,8 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
                tr_u: float = 0.1, tr_x: float = 20.0, max_outer: int = 20, tol: float = 1e-6,
                rho_reject: float = 0.1, rho_expand: float = 0.7, step=rk4_step,
                qp_options: Optional[dict] = None, linearise_on: Optional[str] = None,
-               qp_data_on_device: bool = False, outer_on_device: bool = False, model=None) -> List[ScvxResult]:
+               qp_data_on_device: bool = False, outer_on_device: bool = False, model=None,
+               certify: bool = False) -> List[ScvxResult]:
     """scvx() for B initial conditions x0 (B, n) at once: the same trust-region loop per trajectory (own trust radii,
     own accept / reject decisions, own stop), but ONE batched QP solve per outer iteration -- per-instance dynamics,
     bounds and linear term (correction_qp_batch).  A trajectory that has stopped keeps its place in the batch with a
@@ -644,7 +716,9 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
     agrees with the host loop to the QP tolerance, not bit for bit.
     model: a Model whose step replaces `step` (not both); linearise_on then evaluates model.rhs_torch, and outer_on_device runs the
     kernels of that model (DeviceOuterStep(model=...), the admm_scvx_*_model_device entry points).  Or a StageModel, a
-    time-dependent model (4 sub-intervals per stage): the same three routes, the device one through admm_scvx_*_stage_device."""
+    time-dependent model (4 sub-intervals per stage): the same three routes, the device one through admm_scvx_*_stage_device.
+    certify: every result carries its trajectory's ScvxCertificate -- adjoint() on the host routes; with outer_on_device
+    DeviceOuterStep.certify() (one more device call after the loop, one more host copy); nothing else changes."""
     step = _resolve(model, step)
     tm = _timed(model)
     x0 = np.atleast_2d(np.asarray(x0, np.float64))
@@ -670,7 +744,7 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
             z, iters = qp_solver(loop.prepare())
             admm_iters.append(iters)
             n_active = loop.advance(z)
-        return loop.results(admm_iters)
+        return loop.results(admm_iters, loop.certify() if certify else None)
     if qp_solver is None:
         qp_solver = gpu_qp_solver(qp_data_on_device, **(qp_options or dict(rho=0.5, eps_abs=1e-8, eps_rel=1e-8, max_iter=20000,
                                                                            check_interval=25)))
@@ -700,8 +774,17 @@ def scvx_batch(x0: np.ndarray, N: int, dt: float, Q, R, QN, u_lo, u_hi,
         ub[take], xb[take] = u_new[take], x_new[take]
         for b, rec in records.items():
             hist[b].append(dict(iteration=it, admm_iterations=admm_iters, **rec))
+    cert = adjoint(x0, ub, xb, dt, Q, R, QN, u_lo, u_hi, step, model=tm) if certify else None
     return [ScvxResult(u=ub[b], x=xb[b], cost=float(J[b]), outer_iterations=len(hist[b]), accepted=int(accepted[b]),
-                       converged=bool(converged[b]), history=hist[b]) for b in range(Bn)]
+                       converged=bool(converged[b]), history=hist[b], certificate=_certificate_row(cert, b)) for b in range(Bn)]
+
+
+def _certificate_row(cert: Optional[ScvxCertificate], b: int) -> Optional[ScvxCertificate]:
+    """Trajectory b of a batched certificate of NumPy arrays (None: None)."""
+    if cert is None:
+        return None
+    return ScvxCertificate(*(None if a is None else a[b] for a in (cert.nu, cert.primer, cert.grad, cert.dJdx0)), float(cert.stat[b]),
+                           int(cert.n_bound[b]))
 
 
 class DeviceOuterStep:
@@ -710,6 +793,8 @@ class DeviceOuterStep:
     rk4_step) through admm_scvx_*_device; with a Model: its kind and parameters in an admm_scvx_dynamics, through
     admm_scvx_*_model_device (ADMM_HIP_HAS_SCVX_MODELS; rc is then not used); with a StageModel: its node table
     of the grid (N, dt, substeps), uploaded once, in an admm_scvx_stage_dynamics, through admm_scvx_*_stage_device (§2.8.3).
+    certify() adds the costates and the optimality certificate of the nonlinear problem at the current reference
+    (admm_scvx_adjoint_device; ADMM_HIP_HAS_SCVX_ADJOINT; §2.8.4), whatever the model.
     Every call is queued on torch's current stream; advance() alone waits -- for the count of trajectories still active."""
 
     STATE_F64 = ("ub", "xb", "u_cand", "x_cand", "J", "tr_u", "tr_x")
@@ -805,6 +890,29 @@ class DeviceOuterStep:
         return DeviceProblem(N=self.N, A=self.A, B=self.B, Q=self.Qt, R=self.Rt, QN=self.QNt, x0=self.dx0, lo=self.lo, hi=self.hi,
                              q=self.q, name=f"scvx_correction_batch{self.batch}_N{self.N}")
 
+    def certify(self, costates: bool = True) -> ScvxCertificate:
+        """The ScvxCertificate of the current reference (ub, xb) as CUDA tensors (batch axis first): prepare() about it, then
+        admm_scvx_adjoint_device on what prepare wrote -- so A, B, lo, hi, q are REWRITTEN, as by prepare().  costates=False: nu and
+        primer are not written (None).  Queued on torch's current stream; nothing waits."""
+        import ctypes as C
+
+        import torch
+
+        from . import _abi
+        from .solver import _check, _stream
+        self.prepare()
+        Bn, N = self.batch, self.N
+
+        def f64(*shape):
+            return torch.empty(shape, dtype=torch.float64, device=self.device)
+        t = dict(nu=f64(Bn, N, 6) if costates else None, primer=f64(Bn, N, 3) if costates else None, grad=f64(Bn, N, 3),
+                 dJdx0=f64(Bn, 6), stat=f64(Bn), n_bound=torch.empty(Bn, dtype=torch.int32, device=self.device))
+        out = _abi.CScvxAdjointOut(**{k: self.ptr(v) for k, v in t.items() if v is not None})
+        _check(self._lib, self._lib.admm_scvx_adjoint_device(self.device.index or 0, N, Bn, C.byref(self.params), self.ptr(self.t["ub"]),
+                                                             self.ptr(self.A), self.ptr(self.B), self.ptr(self.q), C.byref(out),
+                                                             _stream(self.device)))
+        return ScvxCertificate(**t)
+
     def advance(self, z) -> int:
         """Candidate, costs and decisions from the QP solutions z (B, N * 9): a CUDA tensor (or a NumPy array, uploaded).  Returns the
         number of trajectories still active."""
@@ -820,10 +928,14 @@ class DeviceOuterStep:
                    C.byref(n_active))
         return int(n_active.value)
 
-    def results(self, admm_iterations) -> List[ScvxResult]:
-        """The loop's state as scvx_batch returns it (one copy of each tensor to the host)."""
+    def results(self, admm_iterations, certificate: Optional[ScvxCertificate] = None) -> List[ScvxResult]:
+        """The loop's state as scvx_batch returns it (one copy of each tensor to the host).  certificate: what certify() returned;
+        each result then carries its trajectory's part (one more copy to the host)."""
         from ._abi import SCVX_HISTORY_FIELDS
         h = {k: v.cpu().numpy() for k, v in self.t.items()}
+        if certificate is not None:
+            certificate = ScvxCertificate(*(None if v is None else v.cpu().numpy() for v in (certificate.nu, certificate.primer, certificate.grad, certificate.dJdx0, certificate.stat,
+                                                                                                   certificate.n_bound)))
         out = []
         for b in range(self.batch):
             hist = []
@@ -832,5 +944,6 @@ class DeviceOuterStep:
                 rec["accepted"] = bool(rec["accepted"])
                 hist.append(dict(iteration=it + 1, admm_iterations=int(admm_iterations[it]), **rec))
             out.append(ScvxResult(u=h["ub"][b], x=h["xb"][b], cost=float(h["J"][b]), outer_iterations=len(hist),
-                                  accepted=int(h["accepted"][b]), converged=bool(h["converged"][b]), history=hist))
+                                  accepted=int(h["accepted"][b]), converged=bool(h["converged"][b]), history=hist,
+                                  certificate=_certificate_row(certificate, b)))
         return out

@@ -126,6 +126,9 @@ _SIGNATURES = {
                                                  C.POINTER(_abi.CScvxState)] + [c_double_p] * 5 + [C.c_void_p]),
     "admm_scvx_advance_stage_device": (C.c_int, [C.c_int32, C.POINTER(_abi.CScvxStageDynamics), C.POINTER(_abi.CScvxParams), c_double_p, c_double_p,
                                                  C.POINTER(_abi.CScvxState), c_int32_p, C.c_void_p]),
+    # costates and the optimality certificate of the nonlinear problem (ADMM_HIP_HAS_SCVX_ADJOINT): no handle, no model
+    "admm_scvx_adjoint_device": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(_abi.CScvxParams)] + [c_double_p] * 4 +
+                                 [C.POINTER(_abi.CScvxAdjointOut), C.c_void_p]),
     # receding-horizon step on the device (ADMM_HIP_HAS_MPC)
     "admm_mpc_advance": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p]),
     "admm_mpc_advance_device": (C.c_int, [C.c_void_p, C.POINTER(_abi.CMpcStep), c_double_p, c_double_p, C.c_void_p]),

@@ -451,6 +451,30 @@ int admm_scvx_prepare_stage_device(int32_t device, const admm_scvx_stage_dynamic
 int admm_scvx_advance_stage_device(int32_t device, const admm_scvx_stage_dynamics* dynamics, const admm_scvx_params* params, const double* x0,
                                    const double* z, admm_scvx_state* state, int32_t* n_active, void* hip_stream);
 
+/* Costates and a first-order optimality certificate of the NONLINEAR problem the SCvx loop works on (new
+ * symbols, announced by ADMM_HIP_HAS_SCVX_ADJOINT -- no struct or signature changed, ABI version unchanged): one backward sweep
+ * over ub and the A, B, q that admm_scvx_prepare_device (any model) wrote about the reference (ub, xb) -- q = (qu_k, qx_k) =
+ * (R ub_k, Q xb_{k+1}).  It needs no handle and no model.  Per trajectory b (device arrays, layouts as above; any output may be
+ * NULL, not all; a NULL output is neither computed into memory nor stored):
+ *   nu      (batch, N, 6)  nu[b, k] = nu_{k+1}, the costate of stage k's dynamics: nu_N = -qx_{N-1},
+ *                          nu_{k+1} = A_{k+1}' nu_{k+2} - qx_k for k = N-2 .. 0
+ *   primer  (batch, N, 3)  B_k' nu_{k+1}
+ *   grad    (batch, N, 3)  qu_k - primer_k = dJ/du_k at fixed x0 (J: the cost of scvx.trajectory_cost; symmetric weights)
+ *   dJdx0   (batch, 6)     -A_0' nu_1 = dJ/dx_0 at fixed u
+ *   stat    (batch)        the maximum over (k, j) of the violation of component (k, j), with exact comparisons: 0 if
+ *                          u_lo_j == u_hi_j; max(-g, 0) if ub == u_lo_j; max(g, 0) if ub == u_hi_j; |g| otherwise (g = grad).
+ *                          NaN if any entry of the trajectory's grad is a NaN
+ *   n_bound (batch) int32  the number of components with ub == u_lo_j or ub == u_hi_j
+ * Every dot product is one fma chain in ascending index whose accumulator starts from the subtracted term (0 where there is none).
+ * Of params only u_lo and u_hi are read.  Queued on the caller's stream, no host synchronisation.  ADMM_ERR_INVALID names the
+ * argument, before the first HIP call or launch: N or batch < 1; NULL params, ub, A, B, q or out; every field of out NULL; a pointer
+ * that is not memory of `device` or whose allocation ends early.  Values are not scanned. */
+#define ADMM_HIP_HAS_SCVX_ADJOINT 1
+typedef struct { double *nu, *primer, *grad, *dJdx0, *stat; int32_t* n_bound; } admm_scvx_adjoint_out; /* device; any may be NULL, not all */
+int admm_scvx_adjoint_device(int32_t device, int32_t N, int32_t batch, const admm_scvx_params* params,
+                             const double* ub, const double* A, const double* B, const double* q,
+                             const admm_scvx_adjoint_out* out, void* hip_stream);
+
 /* Receding-horizon (MPC) step on the device (new symbols, announced by ADMM_HIP_HAS_MPC -- no struct or
  * signature changed): apply the first control, propagate the plant, move the window one stage.  Per QP b, in this order:
  *   1. the state is brought into the (z, y) pair and w into memory, as admm_get does
