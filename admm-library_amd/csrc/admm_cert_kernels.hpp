@@ -14,6 +14,7 @@
 #pragma once
 
 #include "admm_cert.hpp"
+#include "admm_select.hpp"
 
 #include <cstddef>
 #include <cstdint>
@@ -206,13 +207,13 @@ template <int NX, int NU>
 inline void launch_cert_dim(const CertLaunch& l) {
   const dim3 grid((l.pitch + CERT_THREADS - 1) / CERT_THREADS, l.S), block(CERT_THREADS);
   const dim3 cols(l.pitch / 64), wave(64);
-#define CERT_PASS(HQ, PB)                                                                                              \
-  hipLaunchKernelGGL((cert_pass_kernel<NX, NU, HQ, PB>), grid, block, 0, l.stream, l.z, l.y, l.q, l.x0, l.AB, l.QR, l.fuel, \
-                     l.seg_start, l.cin, l.cseg, l.part, l.nu, l.rho, l.N, l.pitch)
-  if (l.has_q) CERT_PASS(true, false); else CERT_PASS(false, false);
+  auto pass = [&](auto HQ, auto PB) {
+    hipLaunchKernelGGL((cert_pass_kernel<NX, NU, HQ(), PB()>), grid, block, 0, l.stream, l.z, l.y, l.q, l.x0, l.AB, l.QR, l.fuel,
+                       l.seg_start, l.cin, l.cseg, l.part, l.nu, l.rho, l.N, l.pitch);
+  };
+  with_flags(pass, l.has_q, false);       // (HASQ, second pass)
   hipLaunchKernelGGL((cert_link_kernel<NX>), cols, wave, 0, l.stream, l.cseg, l.Phi, l.cin, l.S, l.pitch);
-  if (l.has_q) CERT_PASS(true, true); else CERT_PASS(false, true);
-#undef CERT_PASS
+  with_flags(pass, l.has_q, true);
   hipLaunchKernelGGL(cert_finalize_kernel, cols, wave, 0, l.stream, l.part, l.out, l.S, l.pitch);
 }
 

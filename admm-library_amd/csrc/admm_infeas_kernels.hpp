@@ -170,13 +170,13 @@ template <int NX, int NU>
 inline void launch_infeas_dim(const InfeasLaunch& l) {
   const dim3 grid((l.pitch + CERT_THREADS - 1) / CERT_THREADS, l.S), block(CERT_THREADS);
   const dim3 cols(l.pitch / 64), wave(64);
-#define INFEAS_PASS(PB)                                                                                                    \
-  hipLaunchKernelGGL((infeas_pass_kernel<NX, NU, PB>), grid, block, 0, l.stream, l.y, l.y0, l.x0, l.AB, l.bnd, l.seg_start, \
-                     l.cin, l.cseg, l.part, l.nu, l.span, l.pitch)
-  INFEAS_PASS(false);
+  auto pass = [&](auto PB) {
+    hipLaunchKernelGGL((infeas_pass_kernel<NX, NU, PB()>), grid, block, 0, l.stream, l.y, l.y0, l.x0, l.AB, l.bnd, l.seg_start,
+                       l.cin, l.cseg, l.part, l.nu, l.span, l.pitch);
+  };
+  pass(std::false_type{});
   hipLaunchKernelGGL((cert_link_kernel<NX>), cols, wave, 0, l.stream, l.cseg, l.Phi, l.cin, l.S, l.pitch);
-  INFEAS_PASS(true);
-#undef INFEAS_PASS
+  pass(std::true_type{});
   hipLaunchKernelGGL(infeas_finalize_kernel, cols, wave, 0, l.stream, l.part, l.out, l.eps, l.S, l.pitch);
 }
 

@@ -2,6 +2,7 @@
 #include "admm_runtime.hpp"
 #include "admm_cert.hpp"
 #include "admm_infeas.hpp"
+#include "admm_select.hpp"
 
 namespace admm {
 
@@ -177,12 +178,10 @@ int launch_xscan_mfma(admm_handle* h, bool forward_form, bool with_finalize) {
     const double* W = forward_form ? h->scanWBd : h->scanWd;
     const int* rows = forward_form ? h->scan_rowsB : h->scan_rows;
     const admm::FinArgs fa = fin_args(h, 0, h->S);
-#define GEMV(NC) hipLaunchKernelGGL((admm::xscan_gemv_kernel<NC>), grid, block, 0, h->stream, W, rows, h->scan_in, h->scan_out, \
-                                    M, h->fac.scanK, h->pitch, fa)
-    if (h->batch == 1) GEMV(1);
-    else if (h->batch == 2) GEMV(2);
-    else GEMV(4);
-#undef GEMV
+    admm::with_int<1, 2, 4>(h->batch == 1 ? 1 : h->batch == 2 ? 2 : 4, [&](auto NC) {
+      hipLaunchKernelGGL((admm::xscan_gemv_kernel<NC()>), grid, block, 0, h->stream, W, rows, h->scan_in, h->scan_out, M,
+                         h->fac.scanK, h->pitch, fa);
+    });
     return ADMM_OK;
   }
   const int mtiles = h->fac.scanM / 16, ngroups = mtiles / admm::SCAN_MT;
@@ -232,21 +231,14 @@ int ensure_zy(admm_handle* h) {
 int launch_z(admm_handle* h, bool resid) {
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, h->zchunks), block(Z_THREADS);
   const bool relax = h->opt.alpha != 1.0;
-#define ZL(RS, RX)                                                                                       \
-  do {                                                                                                   \
-    if (h->has_soc)                                                                                      \
-      hipLaunchKernelGGL((admm::zdual_soc_kernel<RS, RX>), grid, block, 0, h->stream, h->w, h->z, h->y,  \
-                         h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L, h->zrows, h->pitch, h->nb, h->m); \
-    else                                                                                                 \
-      hipLaunchKernelGGL((admm::zdual_kernel<RS, RX>), grid, block, 0, h->stream, h->w, h->z, h->y,      \
-                         h->lo, h->hi, h->part, h->opt.alpha, h->L, h->zrows, h->pitch);                 \
-  } while (0)
-  if (resid) {
-    if (relax) ZL(true, true); else ZL(true, false);
-  } else {
-    if (relax) ZL(false, true); else ZL(false, false);
-  }
-#undef ZL
+  admm::with_flags([&](auto RS, auto RX) {
+    if (h->has_soc)
+      hipLaunchKernelGGL((admm::zdual_soc_kernel<RS(), RX()>), grid, block, 0, h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub,
+                         h->kap, h->part, h->opt.alpha, h->L, h->zrows, h->pitch, h->nb, h->m);
+    else
+      hipLaunchKernelGGL((admm::zdual_kernel<RS(), RX()>), grid, block, 0, h->stream, h->w, h->z, h->y, h->lo, h->hi, h->part,
+                         h->opt.alpha, h->L, h->zrows, h->pitch);
+  }, resid, relax);
   return ADMM_OK;
 }
 

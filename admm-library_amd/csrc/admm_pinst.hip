@@ -6,7 +6,7 @@
 #include "admm_pinst_launch.hpp"
 
 #define ADMM_PINST_DIMS_G0(X) X(6, 3) X(2, 1) X(4, 2) X(3, 2)
-ADMM_PINST_GROUP(g0, ADMM_PINST_DIMS_G0)
+ADMM_PINST_GROUP(g0, ADMM_PINST_DIMS_G0, launch_dim)
 
 namespace admm {
 
@@ -60,7 +60,7 @@ void launch_pv_to_zy_soc(hipStream_t stream, const double* v, double* z, double*
 }
 
 void launch_to_tiled(hipStream_t stream, const double* src, double* dst, int batch, int N, int E, int n, int pitch, int nr, int nc) {
-  const int qpw = n <= 2 ? 32 : (n <= 4 ? 16 : (n <= 8 ? 8 : 4));                 // PscanShape<n>::QPW
+  const int qpw = pscan_qpw(n);
   const size_t tiles = (size_t)N * (pitch / qpw);
   hipLaunchKernelGGL(to_tiled_kernel, dim3((unsigned)std::min<size_t>(tiles, 1u << 20)), dim3(256), 0, stream, src, dst, batch, N, E, qpw, pitch, nr, nc);
 }

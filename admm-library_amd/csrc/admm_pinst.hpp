@@ -606,7 +606,8 @@ constexpr int PSCAN_D = 8;        // steps whose operands are prefetched as one 
 #define ADMM_PSCAN_WIDE_D 2
 #endif
 template <int NX> struct PscanDepth { static constexpr int D = NX > 8 ? ADMM_PSCAN_WIDE_D : PSCAN_D; };   // ... (wide shapes: 2 n doubles per lane and step, a group of 8 steps is more loads than a wave keeps in flight -- measured at n = 12, 64 QPs, 64 segments: 118 us with groups of 8, 102 with 4, 93 with 2)
-template <int NX> struct PscanShape { static constexpr int QPW = NX <= 2 ? 32 : (NX <= 4 ? 16 : (NX <= 8 ? 8 : 4)); };
+constexpr int pscan_qpw(int n) { return n <= 2 ? 32 : (n <= 4 ? 16 : (n <= 8 ? 8 : 4)); }
+template <int NX> struct PscanShape { static constexpr int QPW = pscan_qpw(NX); };
 
 // ---- operand layout of the rows-over-lanes kernels ----
 // Batch-minor (every other array of the library): element e of stage k of QP col at [(k * E + e) * pitch + col].  A wave of the

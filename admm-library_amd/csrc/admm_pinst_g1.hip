@@ -4,4 +4,4 @@
 #include "admm_pinst_launch.hpp"
 
 #define ADMM_PINST_DIMS_G1(X) X(1, 1) X(2, 2) X(4, 1) X(6, 1) X(6, 2) X(6, 4)
-ADMM_PINST_GROUP(g1, ADMM_PINST_DIMS_G1)
+ADMM_PINST_GROUP(g1, ADMM_PINST_DIMS_G1, launch_dim)

@@ -291,6 +291,24 @@ def test_no_spills_at_headline_shapes(built):
     assert len(spilled) <= 12, spilled
 
 
+def test_compiled_kernel_set_matches_the_manifest(built):
+    """Which kernel forms get compiled is decided in the launchers (admm_select.hpp: every flag combination a launch lambda
+    sees is instantiated).  tests/golden/kernel_counts.json holds, per translation unit and kernel family, the number of
+    instantiations; a change of the compiled set has to show as an edit of that file
+    (python tools/kernel_set_diff.py build/obj --counts)."""
+    import collections
+    import glob
+    import json
+    import __graft_entry__ as ge
+    ge.build_library()          # incremental, as above
+    got = {}
+    for f in sorted(glob.glob(os.path.join(ge.ROOT, "build", "obj", "*.resource_usage.txt"))):
+        names = [r["name"] for r in ge.parse_resource_usage(open(f).read())]
+        got[os.path.basename(f).split(".")[0]] = dict(collections.Counter(n.split("<")[0] for n in names))
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "kernel_counts.json")))
+    assert got == want
+
+
 def test_host_factor_does_not_depend_on_the_thread_count(built):
     """csrc/admm_factor.cpp runs its per-stage / per-segment loops on host threads (ADMM_FACTOR_THREADS, read once per
     process): every stage is computed by exactly one thread with the same arithmetic, so the records -- plain, alternating
