@@ -3,6 +3,7 @@
 // every compute entry point returns ADMM_ERR_NO_DEVICE.
 #include "admm_runtime.hpp"
 #include "admm_cert.hpp"
+#include "admm_consensus.hpp"
 #include "admm_infeas.hpp"
 
 
@@ -169,9 +170,10 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
 // dev_src (admm_setup_device): p is a DeviceProblem's view -- small arrays on the host, the per-instance ones device memory, checked by
 // the device-side findings `scan`
 // fuel (admm_setup_fuel): the weights of the minimum-fuel term, in unorm's shape; NULL = none
+// group (admm_setup_consensus): QPs per scenario group, 0 = a handle without groups
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
                         admm_exchange_fn ts_fn, void* ts_ctx, bool dev_src = false, const DeviceScan* scan = nullptr,
-                        const double* fuel = nullptr) {
+                        const double* fuel = nullptr, int group = 0) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   g_warn.clear();
@@ -187,6 +189,19 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     if (o.precision_mode != ADMM_PRECISION_FP64)
       return fail(ADMM_ERR_UNSUPPORTED, "precision_mode " + std::to_string(o.precision_mode) + ": a fuel term is not supported by the MFMA forms (use ADMM_PRECISION_FP64)");
     if (ts_n) return fail(ADMM_ERR_UNSUPPORTED, "a fuel term is not supported on time-sharded handles");
+  }
+  if (group) {
+    // the group projection exists as the standalone z kernel of the one-lane fp64 path of batch-shared dynamics only
+    if (group < 1 || p->batch % group != 0)
+      return fail(ADMM_ERR_INVALID, "admm_setup_consensus: group_size " + std::to_string(group) + " must be >= 1 and divide batch = " + std::to_string(p->batch));
+    if (p->time_varying == 2) return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_consensus: scenario consensus needs batch-shared dynamics (time_varying = 0 or 1)");
+    if (o.precision_mode != ADMM_PRECISION_FP64)
+      return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_consensus: precision_mode " + std::to_string(o.precision_mode) + ": scenario consensus is not supported by the MFMA forms (use ADMM_PRECISION_FP64)");
+    if (p->m > admm::CONS_MAX_M)
+      return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_consensus: m = " + std::to_string(p->m) + " exceeds " + std::to_string(admm::CONS_MAX_M) +
+                                        " control rows (the LDS arrays of the group projection are sized for the compiled shapes)");
+    // (no time-sharded form: admm_setup_timeshard takes no group size, so the combination cannot be asked for here)
+    o.flags |= ADMM_FLAG_UNFUSED;      // the (z, y) pair, never the v-form: the v -> (z, y) read-out kernels know only the per-QP prox
   }
   if (ts_n) {
     if (ts_n < 1 || ts_rank < 0 || ts_rank >= ts_n) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: need 0 <= rank < nranks");
@@ -222,6 +237,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   h->pitch = ((p->batch + 63) / 64) * 64;
   h->has_q = p->q != nullptr;
   h->has_soc = problem_has_soc(p) || fuel != nullptr;      // a fuel handle runs the SOC forms with or without a thrust bound
+  h->cons_G = group;
   if (fuel) {
     h->has_fuel = true;
     h->fuel.resize(p->N);
@@ -278,14 +294,18 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   {
     int zr = o.zrows;
     if (zr == 0) {
-      const int col_groups = (h->pitch / 2 + Z_THREADS - 1) / Z_THREADS;
-      int chunks = (h->num_cus + col_groups - 1) / col_groups;
+      const int col_groups = h->cons_G ? admm::consensus_col_groups(h->batch, h->cons_G, h->m)      // whole groups per workgroup
+                                       : (h->pitch / 2 + Z_THREADS - 1) / Z_THREADS;
+      // (the consensus kernel synchronises per block and holds two workgroups per CU, whose barriers then overlap; a group wider
+      //  than a workgroup's tile is walked by ONE workgroup, tile by tile, and wants twice as many, shorter chunks: DESIGN.md §2.12)
+      const int wg_per_cu = !h->cons_G ? 1 : admm::consensus_wide(h->cons_G, h->m) ? 4 : 2;
+      int chunks = (wg_per_cu * h->num_cus + col_groups - 1) / col_groups;
       if (chunks < 1) chunks = 1;
       zr = (h->L + chunks - 1) / chunks;
       zr = ((zr + 3) / 4) * 4;
       if (zr < 4) zr = 4;
     }
-    if (h->has_soc) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk
+    if (h->has_soc || h->cons_G) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk
     h->zrows = zr;
     h->zchunks = (h->L + zr - 1) / zr;
   }
@@ -522,6 +542,40 @@ int admm_setup(admm_handle** out, const admm_problem* p, const admm_options* o) 
 int admm_setup_fuel(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel) {
   return setup_common(out, p, o, 0, 0, nullptr, nullptr, false, nullptr, fuel);
 }
+
+// Scenario consensus: admm_setup_fuel with groups of group_size adjacent QPs sharing their control rows.
+int admm_setup_consensus(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, int32_t group_size) {
+  if (out) *out = nullptr;
+  if (group_size < 1) return fail(ADMM_ERR_INVALID, "admm_setup_consensus: group_size " + std::to_string(group_size) + " must be >= 1 and divide batch");
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, false, nullptr, fuel, group_size);
+}
+
+// the control rows of each group's z, (ngroups, N, m): column g * G of the rows j < m of every block (consensus_gather_kernel)
+static int consensus_common(admm_handle* h, double* ubar, bool dev, void* hip_stream) {
+  const char* fn = dev ? "admm_get_consensus_device" : "admm_get_consensus";
+  if (!h || !ubar) return fail(ADMM_ERR_INVALID, "NULL argument");
+  if (!h->cons_G) return fail(ADMM_ERR_INVALID, std::string(fn) + ": the handle has no scenario groups (set it up with admm_setup_consensus)");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  const int ngroups = h->batch / h->cons_G;
+  if (dev && (rc = check_device_ptr(h->device, ubar, sizeof(double) * (size_t)ngroups * h->N * h->m, fn, "ubar"))) return rc;
+  if ((rc = ensure_zy(h))) return rc;                   // the state as the (z, y) pair, as admm_get reads it
+  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
+  const size_t count = (size_t)ngroups * h->N * h->m;
+  admm::launch_consensus_gather(h->stream, h->z, dev ? ubar : h->stage, ngroups, h->cons_G, h->N, h->nb, h->m, h->pitch);
+  HIP_TRY(hipGetLastError());
+  if (!dev) return download_d2h(h, ubar, h->stage, sizeof(double) * count);
+  if (!hip_stream) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
+  return ADMM_OK;
+}
+
+int admm_get_consensus(admm_handle* h, double* ubar) { return consensus_common(h, ubar, false, nullptr); }
+int admm_get_consensus_device(admm_handle* h, double* ubar, void* hip_stream) { return consensus_common(h, ubar, true, hip_stream); }
 
 int admm_get_fuel(admm_handle* h, double* fuel) {
   if (!h || !fuel) return fail(ADMM_ERR_INVALID, "NULL argument");
@@ -1223,6 +1277,8 @@ static int infeasibility_common(admm_handle* h, int32_t span, double eps, double
   if (!std::isfinite(eps) || eps < 0.0) return fail(ADMM_ERR_INVALID, std::string(fn) + ": eps must be finite and >= 0");
   if (h->pinst) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2)");
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle");
+  if (h->cons_G)
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a scenario-consensus handle (a per-QP Farkas certificate is not the coupled problem's)");
   if (h->opt.precision_mode == ADMM_PRECISION_MIXED)
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with precision_mode MIXED (the fp32 phase would put rounding "
                 "noise into the dual's difference)");

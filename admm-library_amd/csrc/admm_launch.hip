@@ -1,6 +1,7 @@
 // admm_launch.hip -- solver runtime: kernel launches, the time-shard exchange, iteration forms and their schedule, graph capture (admm_runtime.hpp)
 #include "admm_runtime.hpp"
 #include "admm_cert.hpp"
+#include "admm_consensus.hpp"
 #include "admm_infeas.hpp"
 #include "admm_select.hpp"
 
@@ -25,6 +26,20 @@ static __global__ __launch_bounds__(64) void infeas_flags_kernel(const double* _
 
 void launch_infeas_flags(hipStream_t stream, const double* flag_row, int* dst, int count) {
   hipLaunchKernelGGL(infeas_flags_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, flag_row, dst, count);
+}
+
+// read-out of a consensus handle: out[g][k][j] = z[(k nb + j) pitch + g G], the control rows of each group's first QP
+static __global__ __launch_bounds__(64) void consensus_gather_kernel(const double* __restrict__ z, double* __restrict__ out, int count,
+                                                                    int G, int N, int nb, int m, int pitch) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= count) return;
+  const int j = i % m, k = (i / m) % N, g = i / (m * N);
+  out[i] = z[((size_t)k * nb + j) * pitch + (size_t)g * G];
+}
+
+void launch_consensus_gather(hipStream_t stream, const double* z, double* out, int ngroups, int G, int N, int nb, int m, int pitch) {
+  const int count = ngroups * N * m;
+  hipLaunchKernelGGL(consensus_gather_kernel, dim3((count + 63) / 64), dim3(64), 0, stream, z, out, count, G, N, nb, m, pitch);
 }
 
 namespace rt {
@@ -229,6 +244,11 @@ int ensure_zy(admm_handle* h) {
 }
 
 int launch_z(admm_handle* h, bool resid) {
+  if (h->cons_G) {                               // scenario consensus: the control rows are projected once per group
+    admm::launch_consensus(admm::ConsLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L,
+                                            h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->cons_G, h->batch, resid});
+    return ADMM_OK;
+  }
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, h->zchunks), block(Z_THREADS);
   const bool relax = h->opt.alpha != 1.0;
   admm::with_flags([&](auto RS, auto RX) {

@@ -60,6 +60,7 @@ struct admm_handle {
   bool has_soc = false;          // some stage has a finite thrust-magnitude bound, or the handle has a fuel term
   bool has_fuel = false;         // set up by admm_setup_fuel with weights: cost term sum_k fuel[k] ||u_k||_2
   std::vector<double> fuel;      // its N per-stage weights (the records and h->kap hold fuel[k] / rho)
+  int cons_G = 0;                // scenario consensus (admm_setup_consensus): group size, 0 = a handle without groups
   admm_options opt{};
   admm::Factor fac;
   // host copy of the shared problem data (the caller's pointers are never kept): admm_set_rho refactors from it

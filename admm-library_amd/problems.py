@@ -43,6 +43,10 @@ class Problem:
     # Where finite, the box of the control rows must be (-inf, inf).
     unorm: Optional[np.ndarray] = None
     name: str = ""
+    # scenario consensus: the batch is batch / consensus consecutive groups of `consensus` QPs which share ONE
+    # control profile (u_{b,k} equal within a group; x0 and q stay per QP).  None = every QP on its own.  Batch-shared dynamics only.
+    # (keyword only in practice: it sits before `fuel`, which stays the last field)
+    consensus: Optional[int] = None
     # minimum-fuel cost  + sum_k fuel_k ||u_k||_2  (fuel >= 0: scalar, or (N,) when the box is per stage); None = off.
     # Where positive, the box of the control rows must be (-inf, inf).  Batch-shared dynamics only.
     fuel: Optional[np.ndarray] = None
@@ -144,6 +148,12 @@ class Problem:
             pos = np.broadcast_to(fu, (lo_u.shape[0],)) > 0
             if np.any(np.isfinite(lo_u[pos])) or np.any(np.isfinite(hi_u[pos])):
                 raise ValueError("control rows must be unbounded (-inf, inf) where fuel is positive")
+        if self.consensus is not None:
+            G = int(self.consensus)
+            if G != self.consensus or G < 1 or self.batch % G != 0:
+                raise ValueError("consensus (the group size) must be an integer >= 1 that divides batch")
+            if self.per_instance:
+                raise ValueError("consensus needs batch-shared dynamics (A, B LTI or LTV)")
         for a in (self.A, self.B, self.Q, self.R, self.QN, self.x0):
             # (stacks of hundreds of MB -- per-instance dynamics -- are left to the library's own threaded check at admm_setup /
             #  admm_update_problem, which Solver reports as the same ValueError: NumPy's pass over 7 GB costs 0.4 s per call)
@@ -170,6 +180,7 @@ class DeviceProblem:
     q: Optional["torch.Tensor"] = None
     unorm: Optional["torch.Tensor"] = None      # 0-d, or (N,) with per-stage bounds
     name: str = ""
+    consensus: Optional[int] = None             # Problem's field; scenario consensus has no device-memory setup (Solver refuses it)
     fuel: Optional["torch.Tensor"] = None       # Problem's field; the device entry points have no fuel term (Solver refuses it)
 
     n = Problem.n
@@ -194,7 +205,7 @@ class DeviceProblem:
             return None if a is None else torch.as_tensor(np.ascontiguousarray(a, np.float64), device=device)
         return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
                    unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name,
-                   fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)))
+                   fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)), consensus=p.consensus)
 
     def validate(self) -> None:
         """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
@@ -202,6 +213,8 @@ class DeviceProblem:
         if self.fuel is not None:
             raise ValueError("fuel: the minimum-fuel term has no device-memory form (its weights are at most N doubles): "
                              "give a Problem with NumPy arrays")
+        if self.consensus is not None:
+            raise ValueError("consensus: scenario consensus has no device-memory setup: give a Problem with NumPy arrays")
         dev = self.x0.device if torch.is_tensor(self.x0) else None
         for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
             a = getattr(self, name)
@@ -343,6 +356,30 @@ def cw_rendezvous_fuel(N: int = 1000, batch: int = 1, seed0: int = SEED0, u_max:
     p = cw_rendezvous(N=N, batch=batch, seed0=seed0, u_max=u_max, thrust_norm=True)
     f = 2.0 * np.pi / N if fuel is None else float(fuel)
     return dataclasses.replace(p, fuel=np.float64(f), name=f"cw_rendezvous_fuel_N{N}_b{batch}")
+
+
+def cw_rendezvous_scenarios(N: int = 1000, groups: int = 1, group_size: int = 8, spread: float = 0.05, seed0: int = SEED0,
+                            u_max: float = 0.2, thrust_norm: bool = False, pos_box=None) -> Problem:
+    """Scenario clouds of cw_rendezvous for consensus: `groups` nominal starts x0_g -- instance g of
+    cw_rendezvous, the same seeding -- each dispersed into `group_size` scenarios x0_g + spread * box * U(-1, 1)^6 (box: the
+    generator's own x0 box; scenario s of group g is drawn from default_rng(seed0 + 1000003 (g + 1) + s)), with
+    Problem.consensus = group_size: one thrust profile per group.  pos_box (km; a scalar or one value per axis, inf = open):
+    |position| <= pos_box on the state rows of every stage -- a corridor every scenario must respect (x_1 of every scenario has
+    to fit: the controls cannot tell the scenarios apart); chosen a little above the nominal trajectory's excursion, the dispersed
+    cloud makes it active.  None leaves the states open, and the consensus profile is then the solution for the group's mean x0."""
+    p = cw_rendezvous(N=N, batch=groups, seed0=seed0, u_max=u_max, thrust_norm=thrust_norm)
+    box = np.array([0.3, 2.0, 1.0, 0.1, 0.1, 0.1])
+    x0 = np.empty((groups * group_size, 6))
+    for g in range(groups):
+        for s in range(group_size):
+            rng = np.random.default_rng(seed0 + 1000003 * (g + 1) + s)
+            x0[g * group_size + s] = p.x0[g] + spread * box * rng.uniform(-1.0, 1.0, 6)
+    lo, hi = p.lo.copy(), p.hi.copy()
+    if pos_box is not None:
+        pb = np.broadcast_to(np.asarray(pos_box, np.float64), (3,))
+        lo[3:6], hi[3:6] = -pb, pb
+    return dataclasses.replace(p, x0=x0, lo=lo, hi=hi, consensus=int(group_size),
+                               name=f"cw_rendezvous_scenarios_N{N}_g{groups}x{group_size}")
 
 
 def cw_formation(N: int = 1000, batch: int = 1, seed0: int = SEED0, u_max: float = 0.2) -> Problem:

@@ -86,6 +86,10 @@ _SIGNATURES = {
     "admm_setup_fuel": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p]),
     "admm_set_fuel": (C.c_int, [C.c_void_p, c_double_p]),
     "admm_get_fuel": (C.c_int, [C.c_void_p, c_double_p]),
+    # scenario consensus (ADMM_HIP_HAS_CONSENSUS): groups of QPs sharing one control profile
+    "admm_setup_consensus": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p, C.c_int32]),
+    "admm_get_consensus": (C.c_int, [C.c_void_p, c_double_p]),
+    "admm_get_consensus_device": (C.c_int, [C.c_void_p, c_double_p, C.c_void_p]),
     # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
     "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
     "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
@@ -299,7 +303,13 @@ class Solver:
             _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
         elif timeshard is None:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
-            if problem.fuel is not None:
+            if problem.consensus is not None:
+                if problem.fuel is not None:
+                    keep["fuel"] = _abi.marshal_fuel(problem)
+                _check(self._lib, self._lib.admm_setup_consensus(C.byref(self._h), C.byref(cp), C.byref(co),
+                                                                 dptr(keep["fuel"]) if "fuel" in keep else c_double_p(),
+                                                                 int(problem.consensus)))
+            elif problem.fuel is not None:
                 keep["fuel"] = _abi.marshal_fuel(problem)
                 _check(self._lib, self._lib.admm_setup_fuel(C.byref(self._h), C.byref(cp), C.byref(co), dptr(keep["fuel"])))
             else:
@@ -308,6 +318,8 @@ class Solver:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
             if problem.fuel is not None:
                 raise AdmmError(2, "a fuel term is not supported on time-sharded handles")
+            if problem.consensus is not None:
+                raise AdmmError(2, "scenario consensus is not supported on time-sharded handles")
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -533,6 +545,16 @@ class Solver:
         nu = np.empty((self.batch, N, n)) if costates else None
         _check(self._lib, self._lib.admm_get_certificate(self._h, *[dptr(o) for o in outs], dptr(nu)))
         return Certificate(outs[0], outs[1], outs[2], nu)
+
+    def consensus(self) -> np.ndarray:
+        """admm_get_consensus: the control profile of each scenario group, (batch / group_size, N, m) -- the control rows of the
+        group's z (equal, bit for bit, across the QPs of a group).  Only on a solver whose Problem has `consensus` set."""
+        p = self.problem
+        if getattr(p, "consensus", None) is None:
+            raise AdmmError(1, "admm_get_consensus: the handle has no scenario groups (set Problem.consensus)")
+        out = np.empty((self.batch // int(p.consensus), p.N, p.m))
+        _check(self._lib, self._lib.admm_get_consensus(self._h, dptr(out)))
+        return out
 
     def infeasibility(self, span: int = 10, eps: float = 1e-6, costates: bool = False) -> Infeasibility:
         """admm_probe_infeasibility: runs `span` iterations (as run(span) does) and turns the drift of the scaled dual over them

@@ -224,6 +224,34 @@ int admm_setup_fuel(admm_handle** out, const admm_problem* p, const admm_options
 int admm_set_fuel(admm_handle* h, const double* fuel);
 int admm_get_fuel(admm_handle* h, double* fuel);
 
+/* Scenario consensus (new symbols, announced by ADMM_HIP_HAS_CONSENSUS -- no struct or signature changed, ABI
+ * version unchanged): the batch is batch / group_size consecutive groups of group_size QPs (QP b belongs to group b / group_size),
+ * and the QPs of a group share ONE control profile:
+ *
+ *     minimise  sum_{b in g} [ 1/2 w_b'P w_b + q_b'w_b + sum_k fuel_k ||u_{b,k}|| ]
+ *     s.t.      each b's dynamics from its own x0,  lo <= w_b <= hi (and ||u|| <= unorm_k),  u_{b,k} = ubar_{g,k} for all b in g
+ *
+ * -- open-loop robust guidance over a cloud of initial conditions: the state box holds for EVERY scenario, not for their mean.
+ * Global-consensus ADMM: only the z-update changes; the control rows of a stage are projected once per group, on the group's
+ * mean of v (box clip, or the shrink-and-scale of the thrust bound / fuel term), and written to every QP of the group.
+ *
+ * admm_setup_consensus: admm_setup_fuel (fuel may be NULL) with the group size.  ADMM_ERR_INVALID: group_size < 1 or not a divisor
+ *   of batch.  ADMM_ERR_UNSUPPORTED: time_varying = 2, precision_mode other than ADMM_PRECISION_FP64, m > 6.  (A time-sharded form
+ *   cannot be asked for: admm_setup_timeshard takes no group size.)  Refused before a device is looked for, nothing allocated.  The handle runs the unfused one-lane fp64 path
+ *   (ADMM_FLAG_UNFUSED is set internally: admm_get_path reports alternating = alt_requested = 0).  Everything else works as on any
+ *   handle -- admm_solve*, admm_run / admm_iterate, admm_step_z, the adaptive rule and admm_set_rho, admm_update_problem*,
+ *   admm_update_instances*, admm_set_state* / admm_get*, admm_set_fuel, admm_get_certificate* (per QP, mu_b = rho y_b),
+ *   ADMM_FLAG_GRAPH, admm_profile with fused_path = 0 -- except admm_probe_infeasibility* and admm_mpc_advance* (a per-QP Farkas
+ *   certificate and a per-QP plant step are not the coupled problem's) and admm_profile with fused_path != 0 (the fused kernels
+ *   carry the per-QP z-update): ADMM_ERR_UNSUPPORTED, the handle unchanged.
+ * admm_get_consensus: the control rows of each group's z, (batch / group_size) x N x m doubles, group-major.  Brings the state into
+ *   the (z, y) pair first, as admm_get does.  ADMM_ERR_INVALID on a handle without groups.
+ * admm_get_consensus_device: ubar is device memory of the handle's GPU, under the rules of admm_get_certificate_device. */
+#define ADMM_HIP_HAS_CONSENSUS 1
+int admm_setup_consensus(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, int32_t group_size);
+int admm_get_consensus(admm_handle* h, double* ubar);
+int admm_get_consensus_device(admm_handle* h, double* ubar, void* hip_stream);
+
 /* Warm start / test hook: overwrite device state.  Any pointer may be NULL
  * (left unchanged).  Each is L*batch and must be finite (ADMM_ERR_INVALID otherwise, nothing uploaded). */
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y);
