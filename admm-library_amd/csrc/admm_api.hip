@@ -167,12 +167,12 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
   return ADMM_OK;
 }
 
-// dev_src (admm_setup_device): p is a DeviceProblem's view -- small arrays on the host, the per-instance ones device memory, checked by
-// the device-side findings `scan`
+// src = Mem::Device (admm_setup_device): p is a DeviceProblem's view -- small arrays on the host, the per-instance ones device memory,
+// checked by the device-side findings `scan`
 // fuel (admm_setup_fuel): the weights of the minimum-fuel term, in unorm's shape; NULL = none
 // group (admm_setup_consensus): QPs per scenario group, 0 = a handle without groups
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
-                        admm_exchange_fn ts_fn, void* ts_ctx, bool dev_src = false, const DeviceScan* scan = nullptr,
+                        admm_exchange_fn ts_fn, void* ts_ctx, Mem src = Mem::Host, const DeviceScan* scan = nullptr,
                         const double* fuel = nullptr, int group = 0) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
@@ -248,7 +248,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     return fail(ADMM_ERR_UNSUPPORTED, "ADMM_FLAG_ROW_MAJOR: per-instance dynamics only (time_varying = 2)");
   }
   if (p->time_varying == 2) {                    // per-instance dynamics: its own set-up (device factorisation)
-    rc = setup_pinst(h, p, dev_src);
+    rc = setup_pinst(h, p, src);
     if (rc) { std::string keep = g_err; release(h); g_err = keep; return rc; }
     *out = h;
     return ADMM_OK;
@@ -525,8 +525,8 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
     TRY_RELEASE(upload_scan_dense(h->fac.scanW, h->fac.scanM, h->fac.scanK, h->scanWd, h->scan_rows));
     if (h->alt_allowed) TRY_RELEASE(upload_scan_dense(h->fac.scanWB, h->fac.scanM, h->fac.scanK, h->scanWBd, h->scan_rowsB));
   }
-  TRY_RELEASE(upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev_src));
-  if (h->has_q) TRY_RELEASE(upload_transposed(h, p->q, h->q, h->L, 0, 0, dev_src));
+  TRY_RELEASE(upload_transposed(h, src, p->x0, h->x0, h->n));
+  if (h->has_q) TRY_RELEASE(upload_transposed(h, src, p->q, h->q, h->L));
   HIP_TRY_RELEASE(hipStreamSynchronize(h->stream));
 #undef DALLOC_WIN
 #undef TRY_RELEASE
@@ -540,42 +540,37 @@ int admm_setup(admm_handle** out, const admm_problem* p, const admm_options* o) 
 }
 
 int admm_setup_fuel(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel) {
-  return setup_common(out, p, o, 0, 0, nullptr, nullptr, false, nullptr, fuel);
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, Mem::Host, nullptr, fuel);
 }
 
 // Scenario consensus: admm_setup_fuel with groups of group_size adjacent QPs sharing their control rows.
 int admm_setup_consensus(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, int32_t group_size) {
   if (out) *out = nullptr;
   if (group_size < 1) return fail(ADMM_ERR_INVALID, "admm_setup_consensus: group_size " + std::to_string(group_size) + " must be >= 1 and divide batch");
-  return setup_common(out, p, o, 0, 0, nullptr, nullptr, false, nullptr, fuel, group_size);
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, Mem::Host, nullptr, fuel, group_size);
 }
 
 // the control rows of each group's z, (ngroups, N, m): column g * G of the rows j < m of every block (consensus_gather_kernel)
-static int consensus_common(admm_handle* h, double* ubar, bool dev, void* hip_stream) {
-  const char* fn = dev ? "admm_get_consensus_device" : "admm_get_consensus";
+static int consensus_common(admm_handle* h, double* ubar, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_get_consensus_device" : "admm_get_consensus";
   if (!h || !ubar) return fail(ADMM_ERR_INVALID, "NULL argument");
   if (!h->cons_G) return fail(ADMM_ERR_INVALID, std::string(fn) + ": the handle has no scenario groups (set it up with admm_setup_consensus)");
   HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
   int rc;
   const int ngroups = h->batch / h->cons_G;
-  if (dev && (rc = check_device_ptr(h->device, ubar, sizeof(double) * (size_t)ngroups * h->N * h->m, fn, "ubar"))) return rc;
+  const size_t bytes = sizeof(double) * (size_t)ngroups * h->N * h->m;
+  if ((rc = io.check_ptr(ubar, bytes, "ubar"))) return rc;
   if ((rc = ensure_zy(h))) return rc;                   // the state as the (z, y) pair, as admm_get reads it
-  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
-  const size_t count = (size_t)ngroups * h->N * h->m;
-  admm::launch_consensus_gather(h->stream, h->z, dev ? ubar : h->stage, ngroups, h->cons_G, h->N, h->nb, h->m, h->pitch);
+  if ((rc = io.begin())) return rc;
+  admm::launch_consensus_gather(h->stream, h->z, io.dev() ? ubar : h->stage, ngroups, h->cons_G, h->N, h->nb, h->m, h->pitch);
   HIP_TRY(hipGetLastError());
-  if (!dev) return download_d2h(h, ubar, h->stage, sizeof(double) * count);
-  if (!hip_stream) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ADMM_OK;
-  }
-  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
-  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
-  return ADMM_OK;
+  if (!io.dev()) return download_d2h(h, ubar, h->stage, bytes);      // (returns with the copy complete)
+  return io.finish();
 }
 
-int admm_get_consensus(admm_handle* h, double* ubar) { return consensus_common(h, ubar, false, nullptr); }
-int admm_get_consensus_device(admm_handle* h, double* ubar, void* hip_stream) { return consensus_common(h, ubar, true, hip_stream); }
+int admm_get_consensus(admm_handle* h, double* ubar) { return consensus_common(h, ubar, Mem::Host, nullptr); }
+int admm_get_consensus_device(admm_handle* h, double* ubar, void* hip_stream) { return consensus_common(h, ubar, Mem::Device, hip_stream); }
 
 int admm_get_fuel(admm_handle* h, double* fuel) {
   if (!h || !fuel) return fail(ADMM_ERR_INVALID, "NULL argument");
@@ -625,12 +620,12 @@ int admm_setup_device(admm_handle** out, const admm_problem* p, const admm_optio
   // the checks run on the caller's stream (ordered after its writes; the handle and its stream do not exist yet) and synchronise it,
   // so the handle's uploads below read finished data
   unsigned long long* scratch = nullptr;
-  if ((rc = dalloc(&scratch, 8))) return rc;
+  if ((rc = dalloc(&scratch, CHK_SLOTS))) return rc;
   DeviceProblem d;
   rc = prepare_device_problem(dev, static_cast<hipStream_t>(hip_stream), p, "admm_setup_device", scratch, d);
   (void)hipFree(scratch);
   if (rc) return rc;
-  return setup_common(out, &d.hp, &oo, 0, 0, nullptr, nullptr, true, &d.scan);
+  return setup_common(out, &d.hp, &oo, 0, 0, nullptr, nullptr, Mem::Device, &d.scan);
 }
 
 int admm_setup_timeshard(admm_handle** out, const admm_problem* p, const admm_options* o, int32_t rank, int32_t nranks,
@@ -651,71 +646,58 @@ int admm_get_window(admm_handle* h, int32_t* stage_lo, int32_t* stage_hi, int32_
   return ADMM_OK;
 }
 
-int admm_update_instances(admm_handle* h, const double* x0, const double* q) {
+// Both forms: everything is checked before anything of the handle is touched; a refused call leaves it as it was.
+static int update_instances_common(admm_handle* h, const double* x0, const double* q, Mem mem, void* hip_stream) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (mem == Mem::Device && h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_update_instances_device: not available on a time-sharded handle");
   HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  if ((x0 || q) && (rc = ensure_w(h))) return rc;   // w of the last x-update belongs to the old instance data
-  if (x0 || q) drop_side_data(h);
-  if (x0 || q) h->alt_state = admm_handle::ALT_NONE;
-  if (x0) {
-    if (!finite_all(x0, (size_t)h->n * h->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
-    if ((rc = upload_transposed(h, x0, h->x0, h->n))) return rc;
-  }
-  if (q) {
-    if (!h->has_q) return fail(ADMM_ERR_INVALID, "handle was set up without q; cannot add one later");
-    if (!finite_all(q, (size_t)h->L * h->batch)) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
-    if ((rc = upload_transposed(h, q, h->q, h->L))) return rc;
-  }
-  return ADMM_OK;
-}
-
-
-// The device-memory form (ABI v9): everything is checked before anything is written.
-int admm_update_instances_device(admm_handle* h, const double* x0, const double* q, void* hip_stream) {
-  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
-  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_update_instances_device: not available on a time-sharded handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const char* fn = "admm_update_instances_device";
+  CallerIO io(h, mem == Mem::Device ? "admm_update_instances_device" : "admm_update_instances", mem, hip_stream);
   const size_t nx = (size_t)h->n * h->batch, nq = (size_t)h->L * h->batch;
-  int rc;
-  if ((x0 && (rc = check_device_ptr(h->device, x0, nx * sizeof(double), fn, "x0"))) ||
-      (q && (rc = check_device_ptr(h->device, q, nq * sizeof(double), fn, "q"))))
-    return rc;
+  int rc, bad;
+  if ((rc = io.check_ptr(x0, nx * sizeof(double), "x0")) || (rc = io.check_ptr(q, nq * sizeof(double), "q"))) return rc;
   if (!x0 && !q) return ADMM_OK;
-  if ((rc = check_scratch(h)) || (rc = wait_for_caller(h, hip_stream))) return rc;
-  HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, 2 * sizeof(unsigned long long), h->stream));
-  if ((x0 && (rc = scan_finite(h->stream, x0, nx, h->chk_d))) || (q && (rc = scan_finite(h->stream, q, nq, h->chk_d + 1)))) return rc;
-  unsigned long long found[2];
-  HIP_TRY(hipMemcpyAsync(found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (x0 && found[0] != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
+  if ((rc = io.begin()) || (rc = io.check_finite({{x0, nx, "x0"}, {q, nq, "q"}}, &bad))) return rc;
+  if (bad == 0) return fail(ADMM_ERR_INVALID, "non-finite entry in x0");
   if (q && !h->has_q) return fail(ADMM_ERR_INVALID, "handle was set up without q; cannot add one later");
-  if (q && found[1] != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
+  if (bad == 1) return fail(ADMM_ERR_INVALID, "non-finite entry in q");
   if ((rc = ensure_w(h))) return rc;                 // w of the last x-update belongs to the old instance data
   drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
-  if (x0 && (rc = upload_transposed(h, x0, h->x0, h->n, 0, 0, true))) return rc;
-  if (q && (rc = upload_transposed(h, q, h->q, h->L, 0, 0, true))) return rc;
+  if (x0 && (rc = upload_transposed(h, mem, x0, h->x0, h->n))) return rc;
+  if (q && (rc = upload_transposed(h, mem, q, h->q, h->L))) return rc;
   return ADMM_OK;
 }
 
-int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y) {
+int admm_update_instances(admm_handle* h, const double* x0, const double* q) {
+  return update_instances_common(h, x0, q, Mem::Host, nullptr);
+}
+int admm_update_instances_device(admm_handle* h, const double* x0, const double* q, void* hip_stream) {
+  return update_instances_common(h, x0, q, Mem::Device, hip_stream);
+}
+
+// Both forms: all three are checked before any is written.
+static int set_state_common(admm_handle* h, const double* w, const double* z, const double* y, Mem mem, void* hip_stream) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (mem == Mem::Device && h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_set_state_device: not available on a time-sharded handle");
   HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  // the device code is compiled with -fno-honor-nans on the premise that nothing non-finite gets in
+  CallerIO io(h, mem == Mem::Device ? "admm_set_state_device" : "admm_set_state", mem, hip_stream);
   const size_t cnt = (size_t)h->L * h->batch;
-  if ((w && !finite_all(w, cnt)) || (z && !finite_all(z, cnt)) || (y && !finite_all(y, cnt)))
-    return fail(ADMM_ERR_INVALID, "non-finite entry in w, z or y");
+  int rc, bad;
+  if ((rc = io.check_ptr(w, cnt * sizeof(double), "w")) || (rc = io.check_ptr(z, cnt * sizeof(double), "z")) ||
+      (rc = io.check_ptr(y, cnt * sizeof(double), "y")))
+    return rc;
+  if (!w && !z && !y) return ADMM_OK;
+  // the device code is compiled with -fno-honor-nans on the premise that nothing non-finite gets in
+  if ((rc = io.begin()) || (rc = io.check_finite({{w, cnt, "w"}, {z, cnt, "z"}, {y, cnt, "y"}}, &bad))) return rc;
+  if (bad >= 0) return fail(ADMM_ERR_INVALID, "non-finite entry in w, z or y");
   if (w) {
-    if ((rc = upload_transposed(h, w, h->w, h->L))) return rc;
+    if ((rc = upload_transposed(h, mem, w, h->w, h->L))) return rc;
     h->w_stale = false;
   }
   if (z || y) {
     if ((rc = ensure_zy(h))) return rc;        // keep the one that is not overwritten
-    if (z && (rc = upload_transposed(h, z, h->z, h->L))) return rc;
-    if (y && (rc = upload_transposed(h, y, h->y, h->L))) return rc;
+    if (z && (rc = upload_transposed(h, mem, z, h->z, h->L))) return rc;
+    if (y && (rc = upload_transposed(h, mem, y, h->y, h->L))) return rc;
     h->zy_valid = true;
     h->v_valid = false;                         // an arbitrary (z, y) pair need not be of the form (clip(v), v - clip(v))
     drop_side_data(h);
@@ -724,41 +706,11 @@ int admm_set_state(admm_handle* h, const double* w, const double* z, const doubl
   return ADMM_OK;
 }
 
-// The device-memory form (ABI v9): all three are checked before any is written.
+int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y) {
+  return set_state_common(h, w, z, y, Mem::Host, nullptr);
+}
 int admm_set_state_device(admm_handle* h, const double* w, const double* z, const double* y, void* hip_stream) {
-  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
-  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_set_state_device: not available on a time-sharded handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const char* fn = "admm_set_state_device";
-  const size_t cnt = (size_t)h->L * h->batch;
-  int rc;
-  if ((w && (rc = check_device_ptr(h->device, w, cnt * sizeof(double), fn, "w"))) ||
-      (z && (rc = check_device_ptr(h->device, z, cnt * sizeof(double), fn, "z"))) ||
-      (y && (rc = check_device_ptr(h->device, y, cnt * sizeof(double), fn, "y"))))
-    return rc;
-  if (!w && !z && !y) return ADMM_OK;
-  if ((rc = check_scratch(h)) || (rc = wait_for_caller(h, hip_stream))) return rc;
-  HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, sizeof(unsigned long long), h->stream));
-  for (const double* a : {w, z, y})
-    if (a && (rc = scan_finite(h->stream, a, cnt, h->chk_d))) return rc;
-  unsigned long long found = 0;
-  HIP_TRY(hipMemcpyAsync(&found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  if (found != ~0ull) return fail(ADMM_ERR_INVALID, "non-finite entry in w, z or y");
-  if (w) {
-    if ((rc = upload_transposed(h, w, h->w, h->L, 0, 0, true))) return rc;
-    h->w_stale = false;
-  }
-  if (z || y) {
-    if ((rc = ensure_zy(h))) return rc;        // keep the one that is not overwritten
-    if (z && (rc = upload_transposed(h, z, h->z, h->L, 0, 0, true))) return rc;
-    if (y && (rc = upload_transposed(h, y, h->y, h->L, 0, 0, true))) return rc;
-    h->zy_valid = true;
-    h->v_valid = false;
-    drop_side_data(h);
-    h->alt_state = admm_handle::ALT_NONE;
-  }
-  return ADMM_OK;
+  return set_state_common(h, w, z, y, Mem::Device, hip_stream);
 }
 
 int admm_step_x(admm_handle* h) {
@@ -1072,44 +1024,27 @@ int admm_get_residuals(admm_handle* h, double* r, double* s, double* nw, double*
   return ADMM_OK;
 }
 
-int admm_get(admm_handle* h, double* w, double* z, double* y) {
+// Device form: the read-out kernels write the caller's arrays on the handle's stream, after what the caller had queued on hip_stream;
+// hip_stream then waits for them (no host synchronisation), or, with hip_stream = NULL, this call does.
+static int get_common(admm_handle* h, double* w, double* z, double* y, Mem mem, void* hip_stream) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (mem == Mem::Device && h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_get_device: not available on a time-sharded handle");
   HIP_TRY(hipSetDevice(h->device));
-  int rc;
-  if (w && (rc = ensure_w(h))) return rc;
-  if ((z || y) && (rc = ensure_zy(h))) return rc;
-  if (w && (rc = download_transposed(h, h->w, w, h->L))) return rc;
-  if (z && (rc = download_transposed(h, h->z, z, h->L))) return rc;
-  if (y && (rc = download_transposed(h, h->y, y, h->L))) return rc;
-  return ADMM_OK;
-}
-
-// The device-memory form (ABI v9): the read-out kernels write the caller's arrays on the handle's stream, after what the caller had
-// queued on hip_stream; hip_stream then waits for them (no host synchronisation), or, with hip_stream = NULL, this call does.
-int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_stream) {
-  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
-  if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_get_device: not available on a time-sharded handle");
-  HIP_TRY(hipSetDevice(h->device));
-  const char* fn = "admm_get_device";
+  CallerIO io(h, mem == Mem::Device ? "admm_get_device" : "admm_get", mem, hip_stream);
   const size_t bytes = sizeof(double) * (size_t)h->L * h->batch;
   int rc;
-  if ((w && (rc = check_device_ptr(h->device, w, bytes, fn, "w"))) || (z && (rc = check_device_ptr(h->device, z, bytes, fn, "z"))) ||
-      (y && (rc = check_device_ptr(h->device, y, bytes, fn, "y"))))
-    return rc;
+  if ((rc = io.check_ptr(w, bytes, "w")) || (rc = io.check_ptr(z, bytes, "z")) || (rc = io.check_ptr(y, bytes, "y"))) return rc;
   if (w && (rc = ensure_w(h))) return rc;
   if ((z || y) && (rc = ensure_zy(h))) return rc;
-  if ((rc = wait_for_caller(h, hip_stream))) return rc;
-  if (w && (rc = download_transposed(h, h->w, w, h->L, true))) return rc;
-  if (z && (rc = download_transposed(h, h->z, z, h->L, true))) return rc;
-  if (y && (rc = download_transposed(h, h->y, y, h->L, true))) return rc;
-  if (!hip_stream) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ADMM_OK;
-  }
-  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
-  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
-  return ADMM_OK;
+  if ((rc = io.begin())) return rc;
+  if (w && (rc = download_transposed(h, mem, h->w, w, h->L))) return rc;
+  if (z && (rc = download_transposed(h, mem, h->z, z, h->L))) return rc;
+  if (y && (rc = download_transposed(h, mem, h->y, y, h->L))) return rc;
+  return io.dev() ? io.finish() : ADMM_OK;      // (a host download returns with the copy complete)
 }
+
+int admm_get(admm_handle* h, double* w, double* z, double* y) { return get_common(h, w, z, y, Mem::Host, nullptr); }
+int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_stream) { return get_common(h, w, z, y, Mem::Device, hip_stream); }
 
 // ---- certificate (kernels in admm_cert_kernels.hpp) ----
 
@@ -1183,18 +1118,17 @@ static int cert_prepare(admm_handle* h, bool want_nu) {
   return ADMM_OK;
 }
 
-static int certificate_common(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, bool dev, void* hip_stream) {
-  const char* fn = dev ? "admm_get_certificate_device" : "admm_get_certificate";
+static int certificate_common(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_get_certificate_device" : "admm_get_certificate";
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
   if (h->pinst) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2)");
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle");
   HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
   int rc;
   const size_t bsz = sizeof(double) * (size_t)h->batch, nusz = bsz * (size_t)h->N * h->n;
-  if (dev && ((obj && (rc = check_device_ptr(h->device, obj, bsz, fn, "obj"))) ||
-              (feas_dyn && (rc = check_device_ptr(h->device, feas_dyn, bsz, fn, "feas_dyn"))) ||
-              (stat && (rc = check_device_ptr(h->device, stat, bsz, fn, "stat"))) ||
-              (nu && (rc = check_device_ptr(h->device, nu, nusz, fn, "nu")))))
+  if ((rc = io.check_ptr(obj, bsz, "obj")) || (rc = io.check_ptr(feas_dyn, bsz, "feas_dyn")) || (rc = io.check_ptr(stat, bsz, "stat")) ||
+      (rc = io.check_ptr(nu, nusz, "nu")))
     return rc;
   admm::CertLaunch l{};
   l.n = h->n; l.m = h->m;
@@ -1202,7 +1136,7 @@ static int certificate_common(admm_handle* h, double* obj, double* feas_dyn, dou
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": no certificate kernel for this (n, m)");
   if ((rc = ensure_zy(h))) return rc;                   // the state as the (z, y) pair, as admm_get reads it
   if ((rc = cert_prepare(h, nu != nullptr))) return rc;
-  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
+  if ((rc = io.begin())) return rc;
   l.stream = h->stream;
   l.N = h->N; l.S = h->S; l.pitch = h->pitch;
   l.has_q = h->has_q;
@@ -1216,26 +1150,19 @@ static int certificate_common(admm_handle* h, double* obj, double* feas_dyn, dou
   HIP_TRY(hipGetLastError());
   double* dst[3] = {obj, feas_dyn, stat};
   for (int v = 0; v < 3; ++v)
-    if (dst[v])
-      HIP_TRY(hipMemcpyAsync(dst[v], h->cert_out + (size_t)v * h->pitch, bsz, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
-  if (nu && (rc = download_transposed(h, h->cert_nu, nu, h->N * h->n, dev))) return rc;
-  if (!dev || !hip_stream) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ADMM_OK;
-  }
-  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
-  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
-  return ADMM_OK;
+    if (dst[v] && (rc = io.copy_out(dst[v], h->cert_out + (size_t)v * h->pitch, bsz))) return rc;
+  if (nu && (rc = download_transposed(h, mem, h->cert_nu, nu, h->N * h->n))) return rc;
+  return io.finish();
 }
 
 int admm_get_certificate(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu) {
-  return certificate_common(h, obj, feas_dyn, stat, nu, false, nullptr);
+  return certificate_common(h, obj, feas_dyn, stat, nu, Mem::Host, nullptr);
 }
 
 // The device-memory form: the rules of admm_get_device (pointer checks, ordering against hip_stream, no host synchronisation
 // once the operands are on the device).
 int admm_get_certificate_device(admm_handle* h, double* obj, double* feas_dyn, double* stat, double* nu, void* hip_stream) {
-  return certificate_common(h, obj, feas_dyn, stat, nu, true, hip_stream);
+  return certificate_common(h, obj, feas_dyn, stat, nu, Mem::Device, hip_stream);
 }
 
 // ---- infeasibility probe (kernels in admm_infeas_kernels.hpp) ----
@@ -1270,8 +1197,8 @@ static int infeas_prepare(admm_handle* h, bool want_nu, bool want_flag) {
 }
 
 static int infeasibility_common(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
-                                int32_t* infeasible, double* nu, bool dev, void* hip_stream) {
-  const char* fn = dev ? "admm_probe_infeasibility_device" : "admm_probe_infeasibility";
+                                int32_t* infeasible, double* nu, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_probe_infeasibility_device" : "admm_probe_infeasibility";
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
   if (span < 1) return fail(ADMM_ERR_INVALID, std::string(fn) + ": span must be >= 1");
   if (!std::isfinite(eps) || eps < 0.0) return fail(ADMM_ERR_INVALID, std::string(fn) + ": eps must be finite and >= 0");
@@ -1283,14 +1210,11 @@ static int infeasibility_common(admm_handle* h, int32_t span, double eps, double
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with precision_mode MIXED (the fp32 phase would put rounding "
                 "noise into the dual's difference)");
   HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
   int rc;
-  const size_t bsz = sizeof(double) * (size_t)h->batch, nusz = bsz * (size_t)h->N * h->n;
-  if (dev && ((sep && (rc = check_device_ptr(h->device, sep, bsz, fn, "sep"))) ||
-              (drift && (rc = check_device_ptr(h->device, drift, bsz, fn, "drift"))) ||
-              (defect && (rc = check_device_ptr(h->device, defect, bsz, fn, "defect"))) ||
-              (infeasible && (rc = check_device_ptr(h->device, infeasible, sizeof(int32_t) * (size_t)h->batch, fn, "infeasible",
-                                                    sizeof(int32_t), "int32 entries"))) ||
-              (nu && (rc = check_device_ptr(h->device, nu, nusz, fn, "nu")))))
+  const size_t bsz = sizeof(double) * (size_t)h->batch, nusz = bsz * (size_t)h->N * h->n, fsz = sizeof(int32_t) * (size_t)h->batch;
+  if ((rc = io.check_ptr(sep, bsz, "sep")) || (rc = io.check_ptr(drift, bsz, "drift")) || (rc = io.check_ptr(defect, bsz, "defect")) ||
+      (rc = io.check_ptr(infeasible, fsz, "infeasible", sizeof(int32_t), "int32 entries")) || (rc = io.check_ptr(nu, nusz, "nu")))
     return rc;
   admm::InfeasLaunch l{};
   l.n = h->n; l.m = h->m;
@@ -1302,7 +1226,7 @@ static int infeasibility_common(admm_handle* h, int32_t span, double eps, double
   HIP_TRY(hipMemcpyAsync(h->infeas_y0, h->y, sizeof(double) * (size_t)h->L * h->pitch, hipMemcpyDeviceToDevice, h->stream));
   if ((rc = admm_run(h, span, 0))) return rc;
   if ((rc = ensure_zy(h))) return rc;
-  if (dev && (rc = wait_for_caller(h, hip_stream))) return rc;
+  if ((rc = io.begin())) return rc;
   l.stream = h->stream;
   l.N = h->N; l.S = h->S; l.pitch = h->pitch;
   l.span = (double)span; l.eps = eps;
@@ -1313,34 +1237,27 @@ static int infeasibility_common(admm_handle* h, int32_t span, double eps, double
   l.nu = nu ? h->cert_nu : nullptr;
   admm::launch_infeas(l, false);
   HIP_TRY(hipGetLastError());
-  const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   double* dst[3] = {sep, drift, defect};
   for (int v = 0; v < 3; ++v)
-    if (dst[v]) HIP_TRY(hipMemcpyAsync(dst[v], h->infeas_out + (size_t)v * h->pitch, bsz, kind, h->stream));
+    if (dst[v] && (rc = io.copy_out(dst[v], h->infeas_out + (size_t)v * h->pitch, bsz))) return rc;
   if (infeasible) {                                     // the flag as int32
     admm::launch_infeas_flags(h->stream, h->infeas_out + (size_t)3 * h->pitch, h->infeas_flag, h->batch);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(infeasible, h->infeas_flag, sizeof(int32_t) * (size_t)h->batch, kind, h->stream));
+    if ((rc = io.copy_out(infeasible, h->infeas_flag, fsz))) return rc;
   }
-  if (nu && (rc = download_transposed(h, h->cert_nu, nu, h->N * h->n, dev))) return rc;
-  if (!dev || !hip_stream) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ADMM_OK;
-  }
-  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
-  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
-  return ADMM_OK;
+  if (nu && (rc = download_transposed(h, mem, h->cert_nu, nu, h->N * h->n))) return rc;
+  return io.finish();
 }
 
 int admm_probe_infeasibility(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
                              int32_t* infeasible, double* nu) {
-  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, false, nullptr);
+  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, Mem::Host, nullptr);
 }
 
 // The device-memory form: the rules of admm_get_certificate_device.
 int admm_probe_infeasibility_device(admm_handle* h, int32_t span, double eps, double* sep, double* drift, double* defect,
                                     int32_t* infeasible, double* nu, void* hip_stream) {
-  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, true, hip_stream);
+  return infeasibility_common(h, span, eps, sep, drift, defect, infeasible, nu, Mem::Device, hip_stream);
 }
 
 int admm_get_info(admm_handle* h, int32_t* iters, int32_t* status, double* r, double* s) {

@@ -66,7 +66,8 @@ int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes) {
 }
 
 // QP-major host array (batch x rows) -> batch-minor device array (rows x pitch)
-int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr, int nc, bool dev) {
+int upload_transposed(admm_handle* h, Mem mem, const double* src, double* dst, int rows, int nr, int nc) {
+  const bool dev = mem == Mem::Device;
   if (rows == h->L && windowed(h)) {
     if (dev) return fail(ADMM_ERR_UNSUPPORTED, "internal: device-memory source on a time-sharded handle");
     // a state-sized array of a handle that holds a stage window only: rows [r0, r0 + Lw) of every QP's vector (a strided 2-D
@@ -95,7 +96,8 @@ int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, 
 }
 
 // QP-major host operand (batch x N x E) -> the wide shapes' tiled device layout
-int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr, int nc, bool dev) {
+int upload_tiled(admm_handle* h, Mem mem, const double* src, double* dst, int E, int nr, int nc) {
+  const bool dev = mem == Mem::Device;
   const size_t rows = (size_t)h->N * E;
   const double* staged = src;
   if (!dev) {
@@ -110,7 +112,8 @@ int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr, 
   return ADMM_OK;
 }
 
-int download_transposed(admm_handle* h, const double* src, double* dst, int rows, bool dev) {
+int download_transposed(admm_handle* h, Mem mem, const double* src, double* dst, int rows) {
+  const bool dev = mem == Mem::Device;
   if (rows == h->L && windowed(h)) {          // the window's rows only; the caller's other rows are left alone
     if (dev) return fail(ADMM_ERR_UNSUPPORTED, "internal: device-memory destination on a time-sharded handle");
     const size_t r0 = win_row0(h), Lw = win_rows(h);
@@ -262,21 +265,34 @@ int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, 
   return ADMM_OK;
 }
 
-// check_finite_kernel over a[0, count) on s; slot receives the smallest offending index (it must hold ~0 beforehand)
-int scan_finite(hipStream_t s, const double* a, size_t count, unsigned long long* slot) {
-  const size_t blocks = std::min<size_t>((count + admm::CHECK_THREADS - 1) / admm::CHECK_THREADS, 8192);
-  if (!blocks) return ADMM_OK;
-  hipLaunchKernelGGL(admm::check_finite_kernel, dim3((unsigned)blocks), dim3(admm::CHECK_THREADS), 0, s, a, count, slot);
-  HIP_TRY(hipGetLastError());
+// check_finite_kernel over every array given, on s: slot i receives the smallest offending index of arrays[i] (admm_runtime.hpp)
+int finite_scan_begin(hipStream_t s, unsigned long long* slots, const FiniteArg* arrays, size_t count) {
+  if (count > (size_t)CHK_SLOTS) return fail(ADMM_ERR_INVALID, "internal: more arrays than result slots of the finite check");
+  HIP_TRY(hipMemsetAsync(slots, 0xff, CHK_SLOTS * sizeof(unsigned long long), s));
+  for (size_t i = 0; i < count; ++i) {
+    const FiniteArg& a = arrays[i];
+    const size_t blocks = std::min<size_t>((a.count + admm::CHECK_THREADS - 1) / admm::CHECK_THREADS, 8192);
+    if (a.ptr && blocks) {
+      hipLaunchKernelGGL(admm::check_finite_kernel, dim3((unsigned)blocks), dim3(admm::CHECK_THREADS), 0, s, a.ptr, a.count, slots + i);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return ADMM_OK;
+}
+
+int finite_scan_end(hipStream_t s, const unsigned long long* slots, unsigned long long (&found)[CHK_SLOTS]) {
+  HIP_TRY(hipMemcpyAsync(found, slots, sizeof found, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
   return ADMM_OK;
 }
 
 // The checks of a problem whose arrays are device memory of `device`, on stream s (ordered after the caller's writes): the pointers,
-// then the small arrays copied to the host and the per-instance ones read once on the device (slots: scratch[0..5] = A, B, box,
-// thrust-magnitude stage, x0, q).  Fills d; returns with s synchronised.  The data checks themselves are validate_problem(&d.hp,
+// then the small arrays copied to the host and the per-instance ones read once on the device (result slots of scratch: Slot below).  Fills d; returns with s synchronised.  The data checks themselves are validate_problem(&d.hp,
 // &d.scan): the caller's.
 int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, const char* fn, unsigned long long* scratch,
                            DeviceProblem& d) {
+  enum Slot { SLOT_A, SLOT_B, SLOT_BOX, SLOT_UN, SLOT_X0, SLOT_Q, SLOT_COUNT };      // (BOX, UN: check_bounds_kernel writes both)
+  static_assert(SLOT_COUNT <= CHK_SLOTS && SLOT_UN == SLOT_BOX + 1, "result slots of the device-side checks");
   int rc;
   if ((rc = validate_dims(p))) return rc;
   const size_t n = p->n, m = p->m, N = p->N, B = p->batch, nb = n + m, L = N * nb;
@@ -300,44 +316,83 @@ int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, con
   if (p->time_varying != 2 && ((rc = to_host(p->A, nA, d.A, &d.hp.A)) || (rc = to_host(p->B, nB, d.B, &d.hp.B)))) return rc;
   if (p->stage_bounds != 2 && ((rc = to_host(p->lo, nbnd, d.lo, &d.hp.lo)) || (rc = to_host(p->hi, nbnd, d.hi, &d.hp.hi)))) return rc;
   if (p->unorm && (rc = to_host(p->unorm, nun, d.un, &d.hp.unorm))) return rc;
-  HIP_TRY(hipMemsetAsync(scratch, 0xff, 6 * sizeof(unsigned long long), s));
-  if (p->time_varying == 2 && ((rc = scan_finite(s, p->A, nA, scratch)) || (rc = scan_finite(s, p->B, nB, scratch + 1)))) return rc;
+  FiniteArg scans[SLOT_COUNT] = {};
+  if (p->time_varying == 2) { scans[SLOT_A] = {p->A, nA, "A"}; scans[SLOT_B] = {p->B, nB, "B"}; }
+  scans[SLOT_X0] = {p->x0, n * B, "x0"};
+  scans[SLOT_Q] = {p->q, L * B, "q"};
+  if ((rc = finite_scan_begin(s, scratch, scans, SLOT_COUNT))) return rc;
   if (p->stage_bounds == 2) {
     const size_t blocks = std::min<size_t>((nbnd + admm::CHECK_THREADS - 1) / admm::CHECK_THREADS, 8192);
     hipLaunchKernelGGL(admm::check_bounds_kernel, dim3((unsigned)blocks), dim3(admm::CHECK_THREADS), 0, s, p->lo, p->hi, nbnd, p->unorm,
-                       (int)nb, (int)m, (int)N, scratch + 2);
+                       (int)nb, (int)m, (int)N, scratch + SLOT_BOX);
     HIP_TRY(hipGetLastError());
   }
-  if ((rc = scan_finite(s, p->x0, n * B, scratch + 4))) return rc;
-  if (p->q && (rc = scan_finite(s, p->q, L * B, scratch + 5))) return rc;
-  unsigned long long found[6];
-  HIP_TRY(hipMemcpyAsync(found, scratch, sizeof found, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const unsigned long long none = ~0ull;
+  unsigned long long found[CHK_SLOTS];
+  if ((rc = finite_scan_end(s, scratch, found))) return rc;
+  const unsigned long long none = CHK_NONE;
   d.scan = DeviceScan{};
-  d.scan.ab_bad = found[0] != none || found[1] != none;
-  if (found[2] != none) {
-    d.scan.bnd_bad = (size_t)found[2];
-    HIP_TRY(hipMemcpy(&d.scan.bnd_lo, p->lo + found[2], sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&d.scan.bnd_hi, p->hi + found[2], sizeof(double), hipMemcpyDeviceToHost));
+  d.scan.ab_bad = found[SLOT_A] != none || found[SLOT_B] != none;
+  if (found[SLOT_BOX] != none) {
+    d.scan.bnd_bad = (size_t)found[SLOT_BOX];
+    HIP_TRY(hipMemcpy(&d.scan.bnd_lo, p->lo + found[SLOT_BOX], sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&d.scan.bnd_hi, p->hi + found[SLOT_BOX], sizeof(double), hipMemcpyDeviceToHost));
   }
-  if (found[3] != none) d.scan.un_stage = (size_t)found[3];
-  d.scan.x0_bad = found[4] != none;
-  d.scan.q_bad = found[5] != none;
-  return ADMM_OK;
-}
-
-// the handle's stream waits for what the caller has queued on its stream so far (NULL: the caller vouches for its data)
-int wait_for_caller(admm_handle* h, void* hip_stream) {
-  if (!hip_stream) return ADMM_OK;
-  if (!h->ext_ev) HIP_TRY(hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(h->ext_ev, static_cast<hipStream_t>(hip_stream)));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->ext_ev, 0));
+  if (found[SLOT_UN] != none) d.scan.un_stage = (size_t)found[SLOT_UN];
+  d.scan.x0_bad = found[SLOT_X0] != none;
+  d.scan.q_bad = found[SLOT_Q] != none;
   return ADMM_OK;
 }
 
 int check_scratch(admm_handle* h) {
-  return h->chk_d ? ADMM_OK : dalloc(&h->chk_d, 8);
+  return h->chk_d ? ADMM_OK : dalloc(&h->chk_d, CHK_SLOTS);
+}
+
+// ---- CallerIO: the caller-array contract of the host and *_device forms of a handle call (admm_runtime.hpp) ----
+
+int CallerIO::check_ptr(const void* ptr, size_t bytes, const char* name, size_t elem, const char* unit) const {
+  return dev() && ptr ? check_device_ptr(h->device, ptr, bytes, fn, name, elem, unit) : ADMM_OK;
+}
+
+int CallerIO::begin() {
+  if (!asked) return ADMM_OK;                    // (a host call; no stream given: the caller vouches for its data)
+  if (!h->ext_ev) HIP_TRY(hipEventCreateWithFlags(&h->ext_ev, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(h->ext_ev, asked));
+  HIP_TRY(hipStreamWaitEvent(h->stream, h->ext_ev, 0));
+  ordered = asked;
+  return ADMM_OK;
+}
+
+int CallerIO::check_finite(std::initializer_list<FiniteArg> arrays, int* bad) {
+  *bad = -1;
+  bool any = false;
+  for (const FiniteArg& a : arrays) any = any || a.ptr;
+  if (!any) return ADMM_OK;
+  unsigned long long found[CHK_SLOTS];
+  int rc;
+  if (dev() && ((rc = check_scratch(h)) || (rc = finite_scan_begin(h->stream, h->chk_d, arrays.begin(), arrays.size())) ||
+                (rc = finite_scan_end(h->stream, h->chk_d, found))))
+    return rc;
+  int i = 0;
+  for (const FiniteArg& a : arrays) {
+    if (a.ptr && (dev() ? found[i] != CHK_NONE : !finite_all(a.ptr, a.count))) { *bad = i; break; }
+    ++i;
+  }
+  return ADMM_OK;
+}
+
+int CallerIO::copy_out(void* dst, const void* src, size_t bytes) {
+  HIP_TRY(hipMemcpyAsync(dst, src, bytes, dev() ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+  return ADMM_OK;
+}
+
+int CallerIO::finish() {
+  if (!ordered) {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ADMM_OK;
+  }
+  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
+  HIP_TRY(hipStreamWaitEvent(ordered, h->ext_ev, 0));
+  return ADMM_OK;
 }
 
 

@@ -28,8 +28,6 @@ int chunk_count(const admm_handle* h, int arrays) {
   return std::max(1, std::min(want, h->N / MPC_MIN_BLOCKS_PER_CHUNK));
 }
 
-struct DevArgs { const double *du, *dx, *x_meas, *q_tail; double *u, *x; };
-
 int bad(const char* fn, const std::string& what) { return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + what); }
 
 // what can be checked without a HIP call and without reading a per-QP array
@@ -51,8 +49,8 @@ int check_step(const char* fn, const admm_handle* h, const admm_mpc_step* s) {
   return ADMM_OK;
 }
 
-// the step itself on the handle's stream; every per-QP array of `d` is device memory (or NULL)
-int advance(admm_handle* h, const admm_mpc_step* s, const DevArgs& d) {
+// the step itself on the handle's stream; every per-QP array of `s`, u and x are device memory (or NULL)
+int advance(admm_handle* h, const admm_mpc_step* s, double* u, double* x) {
   int rc;
   admm::MpcArrays arr{};
   const int wzy_tail = s->tail == ADMM_MPC_TAIL_ZERO ? admm::MPC_ZERO : admm::MPC_KEEP;
@@ -69,20 +67,20 @@ int advance(admm_handle* h, const admm_mpc_step* s, const DevArgs& d) {
   if ((rc = ensure_w(h)) || (rc = ensure_zy(h))) return rc;
   double* const arrays[4] = {h->w, h->z, h->y, h->q};
   for (int a = 0; a < arr.count; ++a) { arr.a[a] = arrays[a]; arr.tail[a] = wzy_tail; }
-  if (d.q_tail) arr.tail[3] = admm::MPC_FILL;
+  if (s->q_tail) arr.tail[3] = admm::MPC_FILL;
   const admm::MpcGeom g{h->N, h->n, h->m, h->nb, h->batch, h->pitch, chunks};
   admm::MpcPlant plant{};
   if (!s->x_meas) {
     std::memcpy(plant.A, s->Ap ? s->Ap : h->pA.data(), sizeof(double) * h->n * h->n);      // (stage 0 of time-varying dynamics)
     std::memcpy(plant.B, s->Bp ? s->Bp : h->pB.data(), sizeof(double) * h->n * h->m);
   }
-  const admm::MpcStep step{h->x0, h->mpc_xn, d.du, d.dx, d.x_meas, d.u, d.x};
+  const admm::MpcStep step{h->x0, h->mpc_xn, s->du, s->dx, s->x_meas, u, x};
   const unsigned step_blocks = (unsigned)((h->pitch + admm::MPC_THREADS - 1) / admm::MPC_THREADS);
   hipLaunchKernelGGL(admm::mpc_edges_kernel, dim3(step_blocks, 1 + (unsigned)(arr.count * (chunks - 1))), dim3(admm::MPC_THREADS), 0,
                      h->stream, arr, g, step, plant, h->mpc_edge);
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(admm::mpc_shift_kernel, dim3((unsigned)column_blocks(h), (unsigned)chunks, (unsigned)arr.count),
-                     dim3(admm::MPC_THREADS), 0, h->stream, arr, g, (const double*)h->mpc_edge, d.q_tail);
+                     dim3(admm::MPC_THREADS), 0, h->stream, arr, g, (const double*)h->mpc_edge, s->q_tail);
   HIP_TRY(hipGetLastError());
   // the flags admm_update_instances and admm_set_state(w, z, y) leave
   h->w_stale = false;
@@ -93,75 +91,54 @@ int advance(admm_handle* h, const admm_mpc_step* s, const DevArgs& d) {
   return ADMM_OK;
 }
 
+// Both forms.  The host form stages its inputs into mpc_io; from there on it is the device form on the staged pointers.
+int advance_common(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_mpc_advance_device" : "admm_mpc_advance";
+  int rc, bad_in;
+  if ((rc = check_step(fn, h, s))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  const size_t B = h->batch, nu = B * h->m, nx = B * h->n, nq = B * h->nb;
+  const FiniteArg in[4] = {{s->du, nu, "du"}, {s->dx, nx, "dx"}, {s->x_meas, nx, "x_meas"}, {s->q_tail, nq, "q_tail"}};
+  for (const FiniteArg& a : in)
+    if ((rc = io.check_ptr(a.ptr, a.count * sizeof(double), a.name))) return rc;
+  if ((rc = io.check_ptr(u_applied, nu * sizeof(double), "u_applied")) || (rc = io.check_ptr(x_next, nx * sizeof(double), "x_next"))) return rc;
+  // one pass over each input, one synchronisation for all of them (device form: none without an input)
+  if ((rc = io.begin()) || (rc = io.check_finite({in[0], in[1], in[2], in[3]}, &bad_in))) return rc;
+  if (bad_in >= 0) return bad(fn, std::string("non-finite entry in ") + in[bad_in].name);
+  admm_mpc_step d = *s;                          // the step with its per-QP arrays in device memory
+  double *u = u_applied, *x = x_next;
+  if (!io.dev()) {
+    // the small per-QP arrays cross through one device buffer: du | dx or x_meas | q_tail | u_applied | x_next
+    if (!h->mpc_io && (rc = dalloc(&h->mpc_io, 2 * nu + 2 * nx + nq))) return rc;
+    double *du_d = h->mpc_io, *dx_d = du_d + nu, *qt_d = dx_d + nx, *u_d = qt_d + nq, *x_d = u_d + nu;
+    const double* xin = s->x_meas ? s->x_meas : s->dx;
+    if ((s->du && (rc = upload_h2d(h, du_d, s->du, sizeof(double) * nu))) || (xin && (rc = upload_h2d(h, dx_d, xin, sizeof(double) * nx))) ||
+        (s->q_tail && (rc = upload_h2d(h, qt_d, s->q_tail, sizeof(double) * nq))))
+      return rc;
+    d.du = s->du ? du_d : nullptr; d.dx = s->dx ? dx_d : nullptr; d.x_meas = s->x_meas ? dx_d : nullptr; d.q_tail = s->q_tail ? qt_d : nullptr;
+    u = u_applied ? u_d : nullptr; x = x_next ? x_d : nullptr;
+  }
+  if ((rc = advance(h, &d, u, x))) return rc;
+  if (!io.dev()) {
+    if (u && (rc = download_d2h(h, u_applied, u, sizeof(double) * nu))) return rc;
+    if (x && (rc = download_d2h(h, x_next, x, sizeof(double) * nx))) return rc;
+  }
+  return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
 
 int admm_mpc_advance(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next) {
-  const char* fn = "admm_mpc_advance";
-  int rc;
-  if ((rc = check_step(fn, h, s))) return rc;
-  const size_t B = h->batch, nu = B * h->m, nx = B * h->n, nq = B * h->nb;
-  if (s->du && !finite_all(s->du, nu)) return bad(fn, "non-finite entry in du");
-  if (s->dx && !finite_all(s->dx, nx)) return bad(fn, "non-finite entry in dx");
-  if (s->x_meas && !finite_all(s->x_meas, nx)) return bad(fn, "non-finite entry in x_meas");
-  if (s->q_tail && !finite_all(s->q_tail, nq)) return bad(fn, "non-finite entry in q_tail");
-  HIP_TRY(hipSetDevice(h->device));
-  // the small per-QP arrays cross through one device buffer: du | dx or x_meas | q_tail | u_applied | x_next
-  if (!h->mpc_io && (rc = dalloc(&h->mpc_io, 2 * nu + 2 * nx + nq))) return rc;
-  double *du_d = h->mpc_io, *dx_d = du_d + nu, *qt_d = dx_d + nx, *u_d = qt_d + nq, *x_d = u_d + nu;
-  const double* xin = s->x_meas ? s->x_meas : s->dx;
-  if ((s->du && (rc = upload_h2d(h, du_d, s->du, sizeof(double) * nu))) || (xin && (rc = upload_h2d(h, dx_d, xin, sizeof(double) * nx))) ||
-      (s->q_tail && (rc = upload_h2d(h, qt_d, s->q_tail, sizeof(double) * nq))))
-    return rc;
-  const DevArgs d{s->du ? du_d : nullptr, s->dx ? dx_d : nullptr, s->x_meas ? dx_d : nullptr, s->q_tail ? qt_d : nullptr,
-                  u_applied ? u_d : nullptr, x_next ? x_d : nullptr};
-  if ((rc = advance(h, s, d))) return rc;
-  if (u_applied && (rc = download_d2h(h, u_applied, u_d, sizeof(double) * nu))) return rc;
-  if (x_next && (rc = download_d2h(h, x_next, x_d, sizeof(double) * nx))) return rc;
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return ADMM_OK;
+  return advance_common(h, s, u_applied, x_next, Mem::Host, nullptr);
 }
 
 // The device-memory form: du, dx, x_meas, q_tail, u_applied, x_next are device memory of the handle's GPU (Ap, Bp stay host arrays),
 // under the rules of admm_update_instances_device for the inputs and of admm_get_device for the outputs.
 int admm_mpc_advance_device(admm_handle* h, const admm_mpc_step* s, double* u_applied, double* x_next, void* hip_stream) {
-  const char* fn = "admm_mpc_advance_device";
-  int rc;
-  if ((rc = check_step(fn, h, s))) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t B = h->batch, nu = B * h->m, nx = B * h->n, nq = B * h->nb;
-  const struct { const double* ptr; size_t count; const char* name; } in[4] = {
-      {s->du, nu, "du"}, {s->dx, nx, "dx"}, {s->x_meas, nx, "x_meas"}, {s->q_tail, nq, "q_tail"}};
-  bool any_input = false;
-  for (const auto& a : in) {
-    if (a.ptr && (rc = check_device_ptr(h->device, a.ptr, a.count * sizeof(double), fn, a.name))) return rc;
-    any_input = any_input || a.ptr;
-  }
-  if ((u_applied && (rc = check_device_ptr(h->device, u_applied, nu * sizeof(double), fn, "u_applied"))) ||
-      (x_next && (rc = check_device_ptr(h->device, x_next, nx * sizeof(double), fn, "x_next"))))
-    return rc;
-  if ((rc = wait_for_caller(h, hip_stream))) return rc;
-  if (any_input) {                               // one pass over each, one synchronisation for all of them
-    if ((rc = check_scratch(h))) return rc;
-    HIP_TRY(hipMemsetAsync(h->chk_d, 0xff, 4 * sizeof(unsigned long long), h->stream));
-    for (int i = 0; i < 4; ++i)
-      if (in[i].ptr && (rc = scan_finite(h->stream, in[i].ptr, in[i].count, h->chk_d + i))) return rc;
-    unsigned long long found[4];
-    HIP_TRY(hipMemcpyAsync(found, h->chk_d, sizeof found, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int i = 0; i < 4; ++i)
-      if (in[i].ptr && found[i] != ~0ull) return bad(fn, std::string("non-finite entry in ") + in[i].name);
-  }
-  const DevArgs d{s->du, s->dx, s->x_meas, s->q_tail, u_applied, x_next};
-  if ((rc = advance(h, s, d))) return rc;
-  if (!hip_stream) {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ADMM_OK;
-  }
-  HIP_TRY(hipEventRecord(h->ext_ev, h->stream));
-  HIP_TRY(hipStreamWaitEvent(static_cast<hipStream_t>(hip_stream), h->ext_ev, 0));
-  return ADMM_OK;
+  return advance_common(h, s, u_applied, x_next, Mem::Device, hip_stream);
 }
 
 }  // extern "C"

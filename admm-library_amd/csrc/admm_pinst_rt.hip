@@ -40,7 +40,7 @@ int pinst_fill_rho(admm_handle* h, double rho) {
 }
 
 // shared weights as row-major device arrays + A, B per instance, into the given buffers (the handle's, or the trial set)
-int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, double* Bd, double* Qd, double* Rd, double* QNd, bool dev) {
+int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, double* Bd, double* Qd, double* Rd, double* QNd, Mem mem) {
   const int n = h->n, m = h->m;
   std::vector<double> Q((size_t)n * n), R((size_t)m * m), QN((size_t)n * n);
   for (int i = 0; i < n; ++i)
@@ -55,24 +55,24 @@ int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, dou
   int rc;
   const bool rowmaj = (h->opt.flags & ADMM_FLAG_ROW_MAJOR) != 0;        // the caller's blocks are row-major: transposed on the device
   if (h->pi_tiled) {
-    if ((rc = upload_tiled(h, p->A, Ad, n * n, rowmaj ? n : 0, n, dev))) return rc;
-    if ((rc = upload_tiled(h, p->B, Bd, n * m, rowmaj ? n : 0, m, dev))) return rc;
+    if ((rc = upload_tiled(h, mem, p->A, Ad, n * n, rowmaj ? n : 0, n))) return rc;
+    if ((rc = upload_tiled(h, mem, p->B, Bd, n * m, rowmaj ? n : 0, m))) return rc;
     return ADMM_OK;
   }
-  if ((rc = upload_transposed(h, p->A, Ad, h->N * n * n, rowmaj ? n : 0, n, dev))) return rc;
-  if ((rc = upload_transposed(h, p->B, Bd, h->N * n * m, rowmaj ? n : 0, m, dev))) return rc;
+  if ((rc = upload_transposed(h, mem, p->A, Ad, h->N * n * n, rowmaj ? n : 0, n))) return rc;
+  if ((rc = upload_transposed(h, mem, p->B, Bd, h->N * n * m, rowmaj ? n : 0, m))) return rc;
   return ADMM_OK;
 }
 
 // the box (per instance or shared) and the thrust-magnitude bounds
-int pinst_upload_bounds(admm_handle* h, const admm_problem* p, bool dev) {
+int pinst_upload_bounds(admm_handle* h, const admm_problem* p, Mem mem) {
   int rc;
   if (h->pbounds) {
-    if ((rc = upload_transposed(h, p->lo, h->lod, h->L, 0, 0, dev))) return rc;
-    if ((rc = upload_transposed(h, p->hi, h->hid, h->L, 0, 0, dev))) return rc;
+    if ((rc = upload_transposed(h, mem, p->lo, h->lod, h->L))) return rc;
+    if ((rc = upload_transposed(h, mem, p->hi, h->hid, h->L))) return rc;
     if (h->lodT) {                                  // the sweeps of the wide shapes read the box as tiles, staged with the operands
-      if ((rc = upload_tiled(h, p->lo, h->lodT, h->nb, 0, 0, dev))) return rc;
-      if ((rc = upload_tiled(h, p->hi, h->hidT, h->nb, 0, 0, dev))) return rc;
+      if ((rc = upload_tiled(h, mem, p->lo, h->lodT, h->nb))) return rc;
+      if ((rc = upload_tiled(h, mem, p->hi, h->hidT, h->nb))) return rc;
     }
     std::vector<double> ub(h->N, INFINITY);         // thrust-magnitude bound per stage (shared by the batch)
     if (p->unorm)
@@ -86,10 +86,10 @@ int pinst_upload_bounds(admm_handle* h, const admm_problem* p, bool dev) {
   return ADMM_OK;
 }
 
-int pinst_upload(admm_handle* h, const admm_problem* p, bool dev) {
+int pinst_upload(admm_handle* h, const admm_problem* p, Mem mem) {
   int rc;
-  if ((rc = pinst_upload_dynamics(h, p, h->Ad, h->Bd, h->Qd, h->Rd, h->QNd, dev))) return rc;
-  return pinst_upload_bounds(h, p, dev);
+  if ((rc = pinst_upload_dynamics(h, p, h->Ad, h->Bd, h->Qd, h->Rd, h->QNd, mem))) return rc;
+  return pinst_upload_bounds(h, p, mem);
 }
 
 // Trial buffers (see admm_handle): K / S always, A / B / weights when the problem data change.
@@ -149,7 +149,7 @@ int pinst_segments(admm_handle* h) {
   return ADMM_OK;
 }
 
-int setup_pinst(admm_handle* h, const admm_problem* p, bool dev) {
+int setup_pinst(admm_handle* h, const admm_problem* p, Mem mem) {
   const admm_options& o = h->opt;
   if (o.precision_mode != ADMM_PRECISION_FP64) return fail(ADMM_ERR_UNSUPPORTED, "precision_mode: the MFMA forms need batch-shared dynamics");
   if (o.flags & (ADMM_FLAG_UNFUSED | ADMM_FLAG_GRAPH))
@@ -278,9 +278,9 @@ int setup_pinst(admm_handle* h, const admm_problem* p, bool dev) {
   // (found by the full-horizon optimality certificate of round 3; the second large handle of a process, whose allocations are fast).
   HIP_TRY(hipStreamSynchronize(h->stream));
   HIP_TRY(hipHostMalloc((void**)&h->h_nconv, sizeof(int), hipHostMallocDefault));
-  if ((rc = pinst_upload(h, p, dev))) return rc;
-  if ((rc = upload_transposed(h, p->x0, h->x0, n, 0, 0, dev))) return rc;
-  if (h->has_q && (rc = upload_transposed(h, p->q, h->q, (int)L, 0, 0, dev))) return rc;
+  if ((rc = pinst_upload(h, p, mem))) return rc;
+  if ((rc = upload_transposed(h, mem, p->x0, h->x0, n))) return rc;
+  if (h->has_q && (rc = upload_transposed(h, mem, p->q, h->q, (int)L))) return rc;
   if ((rc = pinst_fill_rho(h, o.rho))) return rc;
   rc = pinst_factor(h);
   if (rc == ADMM_ERR_NUMERIC && h->S > 1 && h->auto_segments) {      // conditioning bound hit: sweep the whole horizon per lane

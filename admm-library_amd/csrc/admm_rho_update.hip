@@ -225,7 +225,7 @@ int admm_update_problem(admm_handle* h, const admm_problem* p) {
   HIP_TRY(hipSetDevice(h->device));
   int rc;
   if ((rc = validate_problem(p))) return rc;
-  return update_problem_checked(h, p, false);
+  return update_problem_checked(h, p, Mem::Host);
 }
 
 // The device-memory form (ABI v9): the same update, from arrays in the handle's GPU memory.  Everything is checked before anything of
@@ -238,11 +238,14 @@ int admm_update_problem_device(admm_handle* h, const admm_problem* p, void* hip_
   HIP_TRY(hipSetDevice(h->device));
   int rc;
   DeviceProblem d;
-  if ((rc = check_scratch(h)) || (rc = validate_dims(p)) || (rc = wait_for_caller(h, hip_stream)) ||
-      (rc = prepare_device_problem(h->device, h->stream, p, "admm_update_problem_device", h->chk_d, d)))
+  // (of the contract only begin(): prepare_device_problem has the pointer and data checks of a whole problem and returns with the
+  //  stream synchronised, and the call has no result to hand back)
+  CallerIO io(h, "admm_update_problem_device", Mem::Device, hip_stream);
+  if ((rc = check_scratch(h)) || (rc = validate_dims(p)) || (rc = io.begin()) ||
+      (rc = prepare_device_problem(h->device, h->stream, p, io.fn, h->chk_d, d)))
     return rc;
   if ((rc = validate_problem(&d.hp, &d.scan))) return rc;
-  return update_problem_checked(h, &d.hp, true);
+  return update_problem_checked(h, &d.hp, Mem::Device);
 }
 
 }  // extern "C"
@@ -250,8 +253,8 @@ int admm_update_problem_device(admm_handle* h, const admm_problem* p, void* hip_
 namespace admm {
 namespace rt {
 
-// admm_update_problem after validate_problem: dev = the per-instance arrays of p (A, B, box, x0, q) are device memory
-int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
+// admm_update_problem after validate_problem: mem = where the per-instance arrays of p (A, B, box, x0, q) live
+int update_problem_checked(admm_handle* h, const admm_problem* p, Mem mem) {
   int rc;
   if (p->N != h->N || p->n != h->n || p->m != h->m || p->batch != h->batch)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: N, n, m, batch must equal those of admm_setup");
@@ -269,7 +272,7 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
     // with the rho it has; only if every factor exists and meets the conditioning bound is anything of the handle replaced
     // (pointer swaps) -- "on failure the handle is unchanged" holds for this mode as for shared dynamics.
     if ((rc = pinst_alloc_trial(h, true))) return rc;
-    if ((rc = pinst_upload_dynamics(h, p, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2, dev))) return rc;
+    if ((rc = pinst_upload_dynamics(h, p, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2, mem))) return rc;
     int not_pd = 0, grown = 0;
     if ((rc = pinst_try(h, h->Ad2, h->Bd2, h->Qd2, h->Rd2, h->QNd2, h->rho_d, nullptr, &not_pd, &grown))) return rc;
     if (not_pd) return fail(ADMM_ERR_NUMERIC, "problem update refused: R + rho I + B'PB is not positive definite for " + std::to_string(not_pd) + " QP(s)");
@@ -285,9 +288,9 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
     std::swap(h->Ad, h->Ad2); std::swap(h->Bd, h->Bd2); std::swap(h->Kd, h->Kd2); std::swap(h->Sd, h->Sd2);      // commit
     std::swap(h->Qd, h->Qd2); std::swap(h->Rd, h->Rd2); std::swap(h->QNd, h->QNd2);
     h->stage_bounds = p->stage_bounds;
-    if ((rc = pinst_upload_bounds(h, p, dev))) return rc;
-    if ((rc = upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev))) return rc;
-    if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L, 0, 0, dev))) return rc;
+    if ((rc = pinst_upload_bounds(h, p, mem))) return rc;
+    if ((rc = upload_transposed(h, mem, p->x0, h->x0, h->n))) return rc;
+    if (h->has_q && (rc = upload_transposed(h, mem, p->q, h->q, h->L))) return rc;
     return pinst_segments(h);                    // transfer matrices of the new factor
   }
   admm::Factor f;
@@ -311,8 +314,8 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev) {
   h->fac = std::move(f);
   if ((rc = upload_factor(h))) return rc;
   if ((rc = upload_bounds(h, p))) return rc;
-  if ((rc = upload_transposed(h, p->x0, h->x0, h->n, 0, 0, dev))) return rc;
-  if (h->has_q && (rc = upload_transposed(h, p->q, h->q, h->L, 0, 0, dev))) return rc;
+  if ((rc = upload_transposed(h, mem, p->x0, h->x0, h->n))) return rc;
+  if (h->has_q && (rc = upload_transposed(h, mem, p->q, h->q, h->L))) return rc;
   destroy_graph(h);
   return ADMM_OK;
 }

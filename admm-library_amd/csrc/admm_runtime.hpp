@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <string>
 #include <thread>
@@ -294,11 +295,12 @@ int enqueue_one(admm_handle* h, bool resid, bool use_graph, int remaining, int i
 // ---- host <-> device transfers, validation, uploads of the factor, handle lifetime (admm_hostio.hip)
 int upload_h2d(admm_handle* h, void* dst, const void* src, size_t bytes);
 int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes);   // ... and back; returns with the copy complete
-// dev: the caller's array (src of an upload, dst of a download) is device memory of the handle's GPU instead of host memory; it is
-// then read / written by the layout kernels directly, and a download returns with its kernel queued on the handle's stream
-int upload_tiled(admm_handle* h, const double* src, double* dst, int E, int nr = 0, int nc = 0, bool dev = false);   // per-instance operand (batch x N x E) -> tiled layout; nr x nc: row-major source blocks
-int upload_transposed(admm_handle* h, const double* src, double* dst, int rows, int nr = 0, int nc = 0, bool dev = false);   // nr x nc: the rows are stacks of row-major blocks
-int download_transposed(admm_handle* h, const double* src, double* dst, int rows, bool dev = false);
+// Where the caller's array (src of an upload, dst of a download) lives.  Mem::Device: memory of the handle's GPU; it is then read /
+// written by the layout kernels directly, and a download returns with its kernel queued on the handle's stream
+enum class Mem { Host, Device };
+int upload_tiled(admm_handle* h, Mem mem, const double* src, double* dst, int E, int nr = 0, int nc = 0);   // per-instance operand (batch x N x E) -> tiled layout; nr x nc: row-major source blocks
+int upload_transposed(admm_handle* h, Mem mem, const double* src, double* dst, int rows, int nr = 0, int nc = 0);   // nr x nc: the rows are stacks of row-major blocks
+int download_transposed(admm_handle* h, Mem mem, const double* src, double* dst, int rows);
 bool finite_all(const double* a, size_t cnt);
 int validate_options(const admm_options* o);
 // What the device-side checks of a *_device call found in the caller's large arrays; validate_problem reads these instead of
@@ -321,11 +323,45 @@ int validate_dims(const admm_problem* p);
 int validate_problem(const admm_problem* p, const DeviceScan* d = nullptr);
 int check_device_ptr(int device, const void* ptr, size_t bytes, const char* fn, const char* name, size_t elem = sizeof(double),
                      const char* unit = "doubles");   // elem, unit: the array's element (alignment, the count the message names)
-int scan_finite(hipStream_t s, const double* a, size_t count, unsigned long long* slot);
+// The device-side finite check: CHK_SLOTS result slots (admm_handle::chk_d), slot i the smallest offending index of arrays[i] or
+// CHK_NONE.  finite_scan_begin sets every slot to CHK_NONE and queues one pass per array given (ptr = NULL: none); a caller may queue checks
+// of its own into free slots; finite_scan_end copies the slots back and synchronises s: one synchronisation for all of them.
+struct FiniteArg { const double* ptr; size_t count; const char* name; };
+constexpr int CHK_SLOTS = 8;
+constexpr unsigned long long CHK_NONE = ~0ull;
+int finite_scan_begin(hipStream_t s, unsigned long long* slots, const FiniteArg* arrays, size_t count);
+int finite_scan_end(hipStream_t s, const unsigned long long* slots, unsigned long long (&found)[CHK_SLOTS]);
 int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, const char* fn, unsigned long long* scratch,
                            DeviceProblem& d);
-int wait_for_caller(admm_handle* h, void* hip_stream);
 int check_scratch(admm_handle* h);
+
+// The caller-array contract of a handle call that exists in a host and a *_device form: both forms are ONE body
+// that goes through this object wherever the caller's arrays are named.  Mem::Host: the arrays are host memory, hip_stream is
+// ignored.  Mem::Device: they are memory of the handle's GPU, written / read in the order of hip_stream (NULL: the caller vouches
+// for its data, and a call with results returns with them complete).
+struct CallerIO {
+  admm_handle* h;
+  const char* fn;                // the entry point, as the messages name it
+  Mem mem;
+  CallerIO(admm_handle* h_, const char* fn_, Mem mem_, void* hip_stream)
+      : h(h_), fn(fn_), mem(mem_), asked(mem_ == Mem::Device ? static_cast<hipStream_t>(hip_stream) : nullptr) {}
+  bool dev() const { return mem == Mem::Device; }
+  // device call: ptr (NULL: not given) is memory of the handle's GPU, aligned to elem, its allocation at least `bytes` long
+  int check_ptr(const void* ptr, size_t bytes, const char* name, size_t elem = sizeof(double), const char* unit = "doubles") const;
+  // the handle's stream waits for what the caller has queued on its stream so far
+  int begin();
+  // *bad = index of the first array given (ptr != NULL) that holds a non-finite entry, -1 if none does.  Host call: finite_all.
+  // Device call, after begin(): one pass per array on the handle's stream and one synchronisation; none at all with no array given.
+  int check_finite(std::initializer_list<FiniteArg> arrays, int* bad);
+  // a device-resident result to the caller's array, queued on the handle's stream (a host copy is complete after finish())
+  int copy_out(void* dst, const void* src, size_t bytes);
+  // Host call, or no stream given: returns with the handle's stream idle.  Otherwise the caller's stream waits for what the handle's
+  // stream holds, without a host synchronisation.
+  int finish();
+ private:
+  hipStream_t asked;             // the caller's stream of a device call
+  hipStream_t ordered = nullptr; // ... once begin() has ordered the handle's stream after it (and h->ext_ev exists): finish() hands over to this one only
+};
 void set_mixed_form(admm_handle* h, bool fp32);
 void warn_alt_gate(const admm::Factor& f, double rho, const char* when);
 double scan_growth(const admm::Factor& f);
@@ -344,14 +380,14 @@ inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fue
 int pinst_factor(admm_handle* h, bool only_marked = false);
 int pinst_fill_rho(admm_handle* h, double rho);
 int pinst_upload_dynamics(admm_handle* h, const admm_problem* p, double* Ad, double* Bd, double* Qd, double* Rd, double* QNd,
-                          bool dev = false);   // dev: A, B are device memory (the weights are host arrays either way)
-int pinst_upload_bounds(admm_handle* h, const admm_problem* p, bool dev = false);   // dev: a per-instance box is device memory
-int pinst_upload(admm_handle* h, const admm_problem* p, bool dev = false);
+                          Mem mem);   // mem: where A, B live (the weights are host arrays either way)
+int pinst_upload_bounds(admm_handle* h, const admm_problem* p, Mem mem);   // mem: where a per-instance box lives
+int pinst_upload(admm_handle* h, const admm_problem* p, Mem mem);
 int pinst_alloc_trial(admm_handle* h, bool dynamics);
 int pinst_try(admm_handle* h, const double* Ad, const double* Bd, const double* Qd, const double* Rd, const double* QNd,
               const double* rhov, const int* todo, int* n_not_pd, int* n_grown);
 int pinst_segments(admm_handle* h);
-int setup_pinst(admm_handle* h, const admm_problem* p, bool dev = false);
+int setup_pinst(admm_handle* h, const admm_problem* p, Mem mem);
 
 // ---- refactors: background candidates of the adaptive rule, rho changes (admm_rho_update.hip)
 admm_problem shared_problem(const admm_handle* h);
@@ -360,7 +396,7 @@ void spec_reap(admm_handle* h, bool all);
 std::unique_ptr<SpecFactor> spec_take(admm_handle* h, double rho);
 void spec_start(admm_handle* h);
 int set_rho_internal(admm_handle* h, double rho_new);
-int update_problem_checked(admm_handle* h, const admm_problem* p, bool dev);
+int update_problem_checked(admm_handle* h, const admm_problem* p, Mem mem);
 
 // ---- the stage window of the big per-stage arrays (see admm_handle::wk0)
 inline size_t win_row0(const admm_handle* h) { return (size_t)h->wk0 * h->nb; }                       // first stacked row held

@@ -179,7 +179,8 @@ void admm_default_options(admm_options* o);
 int admm_setup(admm_handle** out, const admm_problem* p, const admm_options* o);
 
 /* Replace the per-instance data (x0: n*batch, q: L*batch or NULL = keep) of an
- * existing handle without refactoring. */
+ * existing handle without refactoring.  Both arrays are checked before anything is written; on
+ * ADMM_ERR_INVALID the handle is unchanged. */
 int admm_update_instances(admm_handle* h, const double* x0, const double* q);
 
 /* Change rho on an existing handle: refactors the KKT system on the host, re-uploads the

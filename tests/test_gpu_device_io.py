@@ -231,6 +231,109 @@ def test_device_checks_of_instances_and_state(gpu):
             np.testing.assert_array_equal(a, b)
 
 
+def test_host_checks_of_instances_and_state(gpu):
+    """The host twin of test_device_checks_of_instances_and_state, through the C ABI (the Python wrapper would refuse a non-finite entry
+    itself; a MATLAB or C host does not): everything is checked before anything of the handle is touched, so a refused call
+    leaves it bit for bit as it was -- x0 in particular, which is fine in the two calls that are refused for their q."""
+    lib = pkg.load_library()
+    INVALID = CODE["ADMM_ERR_INVALID"]
+    p = pkg.random_instances(N=30, n=6, m=3, batch=70, seed=23)
+    noq = pkg.random_instances(N=30, n=6, m=3, batch=70, seed=23, with_q=False)
+    assert p.q is not None and noq.q is None
+    x0 = np.ascontiguousarray(p.x0 * 2.0)
+    q_nan = np.ascontiguousarray(p.q).copy()
+    q_nan.reshape(-1)[123] = float("nan")
+    q_ok = np.ascontiguousarray(p.q)
+    z = np.zeros((p.batch, p.L))
+    y = z.copy()
+    y[5, 7] = float("-inf")
+    o = _opts(dict(rho=0.3))
+    with pkg.Solver(p, o) as s, pkg.Solver(p, o) as twin, pkg.Solver(noq, o) as s_noq, pkg.Solver(noq, o) as twin_noq:
+        for h in (s, twin, s_noq, twin_noq):
+            h.iterate(4)
+        assert lib.admm_update_instances(s._h, _abi.dptr(x0), _abi.dptr(q_nan)) == INVALID       # x0 is fine, q is not
+        assert lib.admm_last_error().decode() == "non-finite entry in q"
+        assert lib.admm_update_instances(s_noq._h, _abi.dptr(x0), _abi.dptr(q_ok)) == INVALID    # x0 is fine, q cannot be taken
+        assert "handle was set up without q" in lib.admm_last_error().decode()
+        for h in (s, s_noq):
+            assert lib.admm_set_state(h._h, None, _abi.dptr(z), _abi.dptr(y)) == INVALID
+            assert lib.admm_last_error().decode() == "non-finite entry in w, z or y"
+        for h in (s, twin, s_noq, twin_noq):
+            h.iterate(5)
+        for h, t in ((s, twin), (s_noq, twin_noq)):
+            for a, b in zip(h.get(), t.get()):
+                np.testing.assert_array_equal(a, b)
+
+
+def _ip(t):
+    return C.cast(C.c_void_p(t.data_ptr()), _abi.c_int32_p)
+
+
+@pytest.mark.parametrize("mode", ["stream", "null_stream"])
+def test_host_and_device_forms_of_every_pair_are_bit_equal(gpu, mode):
+    """One short call sequence on two handles, one through host arrays and one through device tensors -- every paired entry point:
+    admm_update_instances, admm_set_state, admm_get, admm_get_certificate, admm_probe_infeasibility, admm_mpc_advance, and on a
+    handle with 10 groups of 7 admm_get_consensus -- with hip_stream torch's current (side) stream, or NULL.  Every output and
+    the state after 3 more iterations are equal bit for bit.  batch 70 in a pitch of 128: pad columns the transposes must not leak."""
+    lib = pkg.load_library()
+    p = pkg.random_ltv(N=30, n=6, m=3, batch=70, seed=61)
+    rng = np.random.default_rng(62)
+    B, L, N, n, m = p.batch, p.L, p.N, p.n, p.m
+    x0 = p.x0 * 0.5 + 0.01
+    q = rng.standard_normal((B, L)) * 0.01
+    w, z, y = (rng.standard_normal((B, L)) * s for s in (0.1, 0.1, 0.01))
+    du, dx, qt = rng.standard_normal((B, m)) * 0.01, rng.standard_normal((B, n)) * 0.01, rng.standard_normal((B, p.nb)) * 0.01
+    t = lambda a: torch.as_tensor(a, device=DEV)           # noqa: E731
+    empty = lambda *shape, dtype=torch.float64: torch.empty(shape, dtype=dtype, device=DEV)      # noqa: E731
+    host = lambda *ts: [a.cpu().numpy() for a in ts]        # noqa: E731  (on the current stream, behind the library's writes)
+
+    def same(got, ref, what):
+        for k, (a, b) in enumerate(zip(got, ref)):
+            np.testing.assert_array_equal(a, np.asarray(b).reshape(a.shape), err_msg=f"{what}[{k}]")
+
+    side = torch.cuda.Stream(DEV)
+    opt = pkg.Options(rho=0.3, segments=3)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side if mode == "stream" else torch.cuda.current_stream(DEV)):
+        assert bool(_stream().value) == (mode == "stream")
+        with pkg.Solver(p, opt) as sh, pkg.Solver(p, opt) as sd:
+            for s in (sh, sd):
+                s.iterate(4)
+            sh.update_instances(x0, q)
+            sd.update_instances(t(x0), t(q))
+            sh.set_state(w, z, y)
+            sd.set_state(t(w), t(z), t(y))
+            sh.iterate(3)
+            sd.iterate(3, sync=False)
+            same(host(*sd.get_device()), sh.get(), "get")
+            ch = sh.certificate(costates=True)
+            outs = [empty(B), empty(B), empty(B), empty(B, N, n)]
+            assert lib.admm_get_certificate_device(sd._h, *[_dp(o) for o in outs], _stream()) == 0, lib.admm_last_error().decode()
+            same(host(*outs), (ch.obj, ch.feas_dyn, ch.stat, ch.nu), "certificate")
+            ih = sh.infeasibility(span=2, eps=1e-6, costates=True)
+            outs, flag, nu = [empty(B), empty(B), empty(B)], empty(B, dtype=torch.int32), empty(B, N, n)
+            assert lib.admm_probe_infeasibility_device(sd._h, 2, 1e-6, *[_dp(o) for o in outs], _ip(flag), _dp(nu), _stream()) == 0
+            same(host(*outs, flag, nu), (ih.sep, ih.drift, ih.defect, ih.infeasible, ih.nu), "infeasibility")
+            same(host(*sd.mpc_advance(du=t(du), dx=t(dx), q_tail=t(qt), tail="zero")), sh.mpc_advance(du=du, dx=dx, q_tail=qt, tail="zero"), "mpc")
+            sh.iterate(3)
+            sd.iterate(3, sync=False)
+            same(host(*sd.get_device()), sh.get(), "state after the sequence")
+            same(sd.get(), sh.get(), "state, host read-out of the device handle")
+        pc = dataclasses.replace(p, consensus=7)
+        with pkg.Solver(pc, opt) as sh, pkg.Solver(pc, opt) as sd:
+            sh.update_instances(x0, q)
+            sd.update_instances(t(x0), t(q))
+            sh.set_state(z=z, y=y)
+            sd.set_state(z=t(z), y=t(y))
+            sh.iterate(3)
+            sd.iterate(3, sync=False)
+            ubar = empty(10, N, m)
+            assert lib.admm_get_consensus_device(sd._h, _dp(ubar), _stream()) == 0, lib.admm_last_error().decode()
+            same(host(ubar), [sh.consensus()], "consensus")
+            same(host(*sd.get_device()), sh.get(), "state of the consensus handle")
+    torch.cuda.synchronize()
+
+
 def test_numeric_refusal_through_the_device_path_leaves_the_handle_unchanged(gpu):
     from test_gpu_guards import _sensitive_instances
     p = _sensitive_instances()
