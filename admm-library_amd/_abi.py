@@ -182,6 +182,11 @@ def marshal_fuel(p: Problem):
     return np.array(np.broadcast_to(np.asarray(p.fuel, np.float64), (p.N,) if p.lo.ndim >= 2 else (1,)), np.float64)
 
 
+def marshal_soft(p: Problem):
+    """The weights of p.soft as admm_setup_soft / admm_set_soft read them: the shape of p.lo -- (n + m,) or (N, n + m)."""
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(p.soft, np.float64), p.lo.shape), np.float64)
+
+
 def marshal_device_problem(p, row_major: bool = False):
     """marshal_problem of a DeviceProblem (validated here): the CProblem holds device pointers.  The layout work marshal_problem does
     on the host -- column-major matrices, the broadcast of unorm -- is done by torch on the tensors' GPU (copies on the current

@@ -5,6 +5,7 @@
 #include "admm_cert.hpp"
 #include "admm_consensus.hpp"
 #include "admm_infeas.hpp"
+#include "admm_soft.hpp"
 
 
 using namespace admm::rt;
@@ -171,9 +172,10 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
 // checked by the device-side findings `scan`
 // fuel (admm_setup_fuel): the weights of the minimum-fuel term, in unorm's shape; NULL = none
 // group (admm_setup_consensus): QPs per scenario group, 0 = a handle without groups
+// soft (admm_setup_soft): the weights of the soft box, in lo's shape; NULL = none
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
                         admm_exchange_fn ts_fn, void* ts_ctx, Mem src = Mem::Host, const DeviceScan* scan = nullptr,
-                        const double* fuel = nullptr, int group = 0) {
+                        const double* fuel = nullptr, int group = 0, const double* soft = nullptr) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   g_warn.clear();
@@ -202,6 +204,17 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
                                         " control rows (the LDS arrays of the group projection are sized for the compiled shapes)");
     // (no time-sharded form: admm_setup_timeshard takes no group size, so the combination cannot be asked for here)
     o.flags |= ADMM_FLAG_UNFUSED;      // the (z, y) pair, never the v-form: the v -> (z, y) read-out kernels know only the per-QP prox
+  }
+  if (soft) {
+    // the soft prox exists as the standalone z kernel of the one-lane fp64 path of batch-shared dynamics only
+    if (p->time_varying == 2) return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_soft: soft constraints need batch-shared dynamics (time_varying = 0 or 1)");
+    if (o.precision_mode != ADMM_PRECISION_FP64)
+      return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_soft: precision_mode " + std::to_string(o.precision_mode) + ": soft constraints are not supported by the MFMA forms (use ADMM_PRECISION_FP64)");
+    std::vector<double> fk;
+    if (fuel) { fk.resize(p->N); for (int k = 0; k < p->N; ++k) fk[k] = fuel[p->stage_bounds ? k : 0]; }
+    if ((rc = validate_soft(p, soft, false, fuel ? fk.data() : nullptr))) return rc;
+    // (no time-sharded or consensus form: neither admm_setup_timeshard nor admm_setup_consensus takes weights)
+    o.flags |= ADMM_FLAG_UNFUSED;      // the (z, y) pair, never the v-form: the v -> (z, y) read-out kernels know only the hard prox
   }
   if (ts_n) {
     if (ts_n < 1 || ts_rank < 0 || ts_rank >= ts_n) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: need 0 <= rank < nranks");
@@ -238,6 +251,11 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   h->has_q = p->q != nullptr;
   h->has_soc = problem_has_soc(p) || fuel != nullptr;      // a fuel handle runs the SOC forms with or without a thrust bound
   h->cons_G = group;
+  if (soft) {
+    h->has_soft = true;
+    h->soft.resize(h->L);
+    for (int e = 0; e < h->L; ++e) h->soft[e] = soft[(p->stage_bounds ? (size_t)(e / h->nb) * h->nb : 0) + e % h->nb];
+  }
   if (fuel) {
     h->has_fuel = true;
     h->fuel.resize(p->N);
@@ -305,7 +323,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
       zr = ((zr + 3) / 4) * 4;
       if (zr < 4) zr = 4;
     }
-    if (h->has_soc || h->cons_G) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk
+    if (h->has_soc || h->cons_G) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk (also with soft weights)
     h->zrows = zr;
     h->zchunks = (h->L + zr - 1) / zr;
   }
@@ -493,6 +511,10 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   TRY_RELEASE(dalloc(&h->hi, L));
   TRY_RELEASE(dalloc(&h->ub, (size_t)h->N));
   TRY_RELEASE(dalloc(&h->kap, (size_t)h->N));
+  if (h->has_soft) {
+    TRY_RELEASE(dalloc(&h->soft_d, L));
+    TRY_RELEASE(dalloc(&h->skap_d, L));
+  }
   TRY_RELEASE(dalloc(&h->recB, h->fac.recB.size()));
   TRY_RELEASE(dalloc(&h->recF, h->fac.recF.size()));
   TRY_RELEASE(dalloc(&h->recS, h->fac.recS.size()));
@@ -550,6 +572,67 @@ int admm_setup_consensus(admm_handle** out, const admm_problem* p, const admm_op
   return setup_common(out, p, o, 0, 0, nullptr, nullptr, Mem::Host, nullptr, fuel, group_size);
 }
 
+// Soft box constraints: admm_setup_fuel with a weight per row of the box; the z-update is zdual_soft_kernel.
+int admm_setup_soft(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, const double* soft) {
+  if (out) *out = nullptr;
+  if (!soft) return fail(ADMM_ERR_INVALID, "admm_setup_soft: soft must not be NULL (admm_setup / admm_setup_fuel set up a handle without weights)");
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, Mem::Host, nullptr, fuel, 0, soft);
+}
+
+int admm_get_soft(admm_handle* h, double* soft) {
+  if (!h || !soft) return fail(ADMM_ERR_INVALID, "NULL argument");
+  for (int e = 0; e < h->L; ++e) soft[e] = h->has_soft ? h->soft[e] : INFINITY;
+  return ADMM_OK;
+}
+
+// New weights on a soft handle: nothing of the handle is written before every check has passed.  The state is the (z, y) pair
+// already (such a handle never enters the v-form); the factor does not depend on the weights, so only kappa is refreshed.
+int admm_set_soft(admm_handle* h, const double* soft) {
+  if (!h || !soft) return fail(ADMM_ERR_INVALID, "NULL argument");
+  g_warn.clear();
+  if (!h->has_soft) return fail(ADMM_ERR_INVALID, "admm_set_soft: soft weights cannot be added to a handle (set it up with admm_setup_soft)");
+  HIP_TRY(hipSetDevice(h->device));
+  const admm_problem p = shared_problem(h);
+  int rc;
+  if ((rc = validate_soft(&p, soft, false, fuel_of(h)))) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));   // kernels of the old weights are done before kappa changes
+  for (int e = 0; e < h->L; ++e) h->soft[e] = soft[(h->stage_bounds ? (size_t)(e / h->nb) * h->nb : 0) + e % h->nb];
+  h->infeas_valid = false;                    // the probe's bound table opens the rows with a finite weight
+  return upload_kappa(h);
+}
+
+// penalty, largest violation and violated rows of every QP at the handle's z (soft_report_kernel)
+static int soft_report_common(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_get_soft_report_device" : "admm_get_soft_report";
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (!penalty && !max_violation && !n_violated) return fail(ADMM_ERR_INVALID, std::string(fn) + ": at least one output must be given");
+  if (!h->has_soft) return fail(ADMM_ERR_INVALID, std::string(fn) + ": the handle has no soft weights (set it up with admm_setup_soft)");
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  int rc;
+  const size_t bsz = sizeof(double) * (size_t)h->batch, csz = sizeof(int32_t) * (size_t)h->batch;
+  if ((rc = io.check_ptr(penalty, bsz, "penalty")) || (rc = io.check_ptr(max_violation, bsz, "max_violation")) ||
+      (rc = io.check_ptr(n_violated, csz, "n_violated", sizeof(int32_t), "int32 entries")))
+    return rc;
+  if (!h->soft_out && ((rc = dalloc(&h->soft_out, (size_t)2 * h->pitch)) || (rc = dalloc(&h->soft_cnt, (size_t)h->pitch)))) return rc;
+  if ((rc = ensure_zy(h))) return rc;                   // the state as the (z, y) pair, as admm_get reads it
+  if ((rc = io.begin())) return rc;
+  admm::launch_soft_report(h->stream, h->z, h->lo, h->hi, h->soft_d, h->soft_out, h->soft_out + h->pitch, h->soft_cnt, h->L, h->pitch,
+                           h->batch);
+  HIP_TRY(hipGetLastError());
+  if (penalty && (rc = io.copy_out(penalty, h->soft_out, bsz))) return rc;
+  if (max_violation && (rc = io.copy_out(max_violation, h->soft_out + h->pitch, bsz))) return rc;
+  if (n_violated && (rc = io.copy_out(n_violated, h->soft_cnt, csz))) return rc;
+  return io.finish();
+}
+
+int admm_get_soft_report(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated) {
+  return soft_report_common(h, penalty, max_violation, n_violated, Mem::Host, nullptr);
+}
+int admm_get_soft_report_device(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated, void* hip_stream) {
+  return soft_report_common(h, penalty, max_violation, n_violated, Mem::Device, hip_stream);
+}
+
 // the control rows of each group's z, (ngroups, N, m): column g * G of the rows j < m of every block (consensus_gather_kernel)
 static int consensus_common(admm_handle* h, double* ubar, Mem mem, void* hip_stream) {
   const char* fn = mem == Mem::Device ? "admm_get_consensus_device" : "admm_get_consensus";
@@ -588,6 +671,11 @@ int admm_set_fuel(admm_handle* h, const double* fuel) {
   const admm_problem p = shared_problem(h);
   int rc;
   if ((rc = validate_fuel(&p, fuel, false))) return rc;
+  if (h->has_soft) {                          // a stage that gains a fuel weight must not hold a finite soft weight on its control rows
+    std::vector<double> fk(h->N);
+    for (int k = 0; k < h->N; ++k) fk[k] = fuel[h->stage_bounds ? k : 0];
+    if ((rc = validate_soft(&p, h->soft.data(), true, fk.data()))) return rc;
+  }
   if ((rc = ensure_w(h))) return rc;          // w of the last x-update belongs to the old records
   if ((rc = ensure_zy(h))) return rc;
   h->zy_valid = true;
@@ -1188,6 +1276,9 @@ static int infeas_prepare(admm_handle* h, bool want_nu, bool want_flag) {
       std::copy(h->plo.begin() + o, h->plo.begin() + o + nb, bd.begin() + (size_t)k * rbd);
       std::copy(h->phi.begin() + o, h->phi.begin() + o + nb, bd.begin() + (size_t)k * rbd + nb);
       bd[(size_t)k * rbd + 2 * nb] = h->pun.empty() ? INFINITY : h->pun[h->stage_bounds ? k : 0];
+      if (h->has_soft)                      // a row with a finite weight can be violated at a price: open for feasibility
+        for (int j = 0; j < nb; ++j)
+          if (h->soft[(size_t)k * nb + j] < INFINITY) { bd[(size_t)k * rbd + j] = -INFINITY; bd[(size_t)k * rbd + nb + j] = INFINITY; }
     }
     HIP_TRY(hipMemcpyAsync(h->infeas_bnd, bd.data(), sizeof(double) * bd.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

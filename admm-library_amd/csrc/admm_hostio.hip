@@ -449,7 +449,7 @@ void release(admm_handle* h) {
     if (*b) *b += win_bias_m(h);
   double** bufs[] = {&h->w, &h->z, &h->y, &h->v, &h->q, &h->dbuf, &h->scan_in, &h->scan_out, &h->scanWp,
                      &h->part, &h->resid, &h->lo, &h->hi, &h->ub, &h->kap, &h->recB, &h->recF, &h->recS, &h->stage,
-                     &h->recFE, &h->recBE, &h->mvec, &h->scanWpB, &h->wu, &h->xbnd};
+                     &h->recFE, &h->recBE, &h->mvec, &h->scanWpB, &h->wu, &h->xbnd, &h->soft_d, &h->skap_d, &h->soft_out};
   for (auto b : bufs)
     if (*b) { (void)hipFree(*b); *b = nullptr; }
   {
@@ -492,6 +492,7 @@ void release(admm_handle* h) {
                      &h->cert_nu, &h->infeas_y0, &h->infeas_bnd, &h->infeas_part, &h->infeas_out, &h->mpc_edge, &h->mpc_xn, &h->mpc_io})
     if (*b) { (void)hipFree(*b); *b = nullptr; }
   if (h->infeas_flag) { (void)hipFree(h->infeas_flag); h->infeas_flag = nullptr; }
+  if (h->soft_cnt) { (void)hipFree(h->soft_cnt); h->soft_cnt = nullptr; }
   if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
   delete h;
 }
@@ -536,7 +537,7 @@ int upload_factor(admm_handle* h) {
       HIP_TRY(hipMemcpy(h->recMB64, h->fac.recMB64.data(), h->fac.recMB64.size(), hipMemcpyHostToDevice));
     }
   }
-  if (h->has_fuel && (rc = upload_kappa(h))) return rc;             // kappa = weight / rho follows every refactor
+  if ((h->has_fuel || h->has_soft) && (rc = upload_kappa(h))) return rc;   // kappa = weight / rho follows every refactor
   if (h->alt_allowed) {
     // (the refactored records go into the allocation of admm_setup: its slack stays zero, and still covers them)
     if ((rc = check_record_alloc("refactor, recFE", h->recFE_bytes, h->fac.recFE.size() / h->fac.RFE, sizeof(double) * h->fac.RFE))) return rc;
@@ -577,6 +578,13 @@ int upload_kappa(admm_handle* h) {
   if (h->has_fuel)
     for (int k = 0; k < h->N; ++k) kap[k] = h->fuel[k] / h->fac.rho;
   HIP_TRY(hipMemcpyAsync(h->kap, kap.data(), sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
+  std::vector<double> skap;                   // soft box: weight / rho per stacked row, an IEEE division (inf / rho = inf, 0 / rho = 0)
+  if (h->has_soft) {
+    skap.resize(h->L);
+    for (int e = 0; e < h->L; ++e) skap[e] = h->soft[e] / h->fac.rho;
+    HIP_TRY(hipMemcpyAsync(h->skap_d, skap.data(), sizeof(double) * h->L, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->soft_d, h->soft.data(), sizeof(double) * h->L, hipMemcpyHostToDevice, h->stream));
+  }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return ADMM_OK;
 }
@@ -620,6 +628,22 @@ int validate_fuel(const admm_problem* p, const double* fuel, bool per_stage) {
     for (int j = 0; j < p->m; ++j)
       if (std::isfinite(p->lo[o + j]) || std::isfinite(p->hi[o + j]))
         return fail(ADMM_ERR_INVALID, "control rows must be unbounded (-inf, inf) where fuel is positive");
+  }
+  return ADMM_OK;
+}
+
+int validate_soft(const admm_problem* p, const double* soft, bool expanded, const double* fuel) {
+  const int nb = p->n + p->m;
+  const size_t cnt = (size_t)nb * ((expanded || p->stage_bounds) ? p->N : 1);
+  for (size_t e = 0; e < cnt; ++e)
+    if (!(soft[e] >= 0.0)) return fail(ADMM_ERR_INVALID, "soft entries must be >= 0 (+inf = a hard row) and not NaN");
+  for (int k = 0; k < p->N; ++k) {
+    const bool ball = p->unorm && std::isfinite(p->unorm[p->stage_bounds ? k : 0]);
+    if (!ball && !(fuel && fuel[k] > 0.0)) continue;
+    const size_t o = (expanded || p->stage_bounds) ? (size_t)k * nb : 0;
+    for (int j = 0; j < p->m; ++j)
+      if (soft[o + j] != INFINITY)
+        return fail(ADMM_ERR_INVALID, "soft entries of the control rows must be +inf where unorm is finite or fuel is positive");
   }
   return ADMM_OK;
 }

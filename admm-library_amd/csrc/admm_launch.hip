@@ -4,6 +4,7 @@
 #include "admm_consensus.hpp"
 #include "admm_infeas.hpp"
 #include "admm_select.hpp"
+#include "admm_soft.hpp"
 
 namespace admm {
 
@@ -247,6 +248,11 @@ int launch_z(admm_handle* h, bool resid) {
   if (h->cons_G) {                               // scenario consensus: the control rows are projected once per group
     admm::launch_consensus(admm::ConsLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L,
                                             h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->cons_G, h->batch, resid});
+    return ADMM_OK;
+  }
+  if (h->has_soft) {                             // soft box: the prox of weight dist(., [lo, hi]) per row (admm_soft_kernels.hpp)
+    admm::launch_soft(admm::SoftLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->skap_d, h->ub, h->kap, h->part, h->opt.alpha, h->L,
+                                       h->zrows, h->zchunks, h->pitch, h->nb, h->m, resid, h->has_soc});
     return ADMM_OK;
   }
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, h->zchunks), block(Z_THREADS);

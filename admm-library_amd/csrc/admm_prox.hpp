@@ -62,6 +62,15 @@ ADMM_PROX_FN double clip_lo(double v, double lo) { return fmax(v, lo); }
 ADMM_PROX_FN double clip_hi(double v, double hi) { return fmin(v, hi); }
 ADMM_PROX_FN double clip(double v, double lo, double hi) { return clip_hi(clip_lo(v, lo), hi); }
 
+// Soft box: the prox of  kap dist(., [lo, hi])  at v, kap = s / rho >= 0 the row's weight over rho.  Inside the
+// box, or outside by at most kap, the projection c itself; further out, v moved kap towards the box.  A SELECT on |e| <= kap,
+// not v - clip(e, -kap, kap): with kap = +inf the result is c, the bits of clip(); with kap = 0 it is v wherever v != c.
+ADMM_PROX_FN double soft_clip(double v, double lo, double hi, double kap) {
+  const double c = clip(v, lo, hi);
+  const double e = v - c;
+  return fabs(e) <= kap ? c : (e > 0.0 ? v - kap : v + kap);
+}
+
 // the relaxed x-update output w^ from w and the old z
 template <bool RELAX>
 ADMM_PROX_FN double relaxed(double alpha, double w, double zo) {

@@ -265,6 +265,8 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, Mem mem) {
     if ((rc = validate_fuel(p, h->fuel.data(), true))) return rc;
   } else if (problem_has_soc(p) != h->has_soc)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: a thrust-magnitude bound cannot be added to or removed from a handle");
+  // soft weights stay in force, per stacked row; the control rows of the new problem's thrust / fuel stages must still be hard
+  if (h->has_soft && (rc = validate_soft(p, h->soft.data(), true, fuel_of(h)))) return rc;
   if ((p->time_varying == 2) != h->pinst || (h->pinst && (p->stage_bounds == 2) != h->pbounds))
     return fail(ADMM_ERR_INVALID, "admm_update_problem: per-instance dynamics / bounds cannot be added to or removed from a handle");
   if (h->pinst) {

@@ -62,6 +62,12 @@ struct admm_handle {
   bool has_fuel = false;         // set up by admm_setup_fuel with weights: cost term sum_k fuel[k] ||u_k||_2
   std::vector<double> fuel;      // its N per-stage weights (the records and h->kap hold fuel[k] / rho)
   int cons_G = 0;                // scenario consensus (admm_setup_consensus): group size, 0 = a handle without groups
+  // soft box constraints (admm_setup_soft): the weights per stacked row (+inf = hard), their device copy, weight / rho
+  // beside it (refreshed wherever h->kap is: upload_kappa), and the report's results, allocated on the first admm_get_soft_report* call
+  bool has_soft = false;
+  std::vector<double> soft;      // [L]
+  double *soft_d = nullptr, *skap_d = nullptr, *soft_out = nullptr;      // [L], [L], [2][pitch] penalty | max violation
+  int* soft_cnt = nullptr;       // [pitch] violated rows
   admm_options opt{};
   admm::Factor fac;
   // host copy of the shared problem data (the caller's pointers are never kept): admm_set_rho refactors from it
@@ -374,6 +380,10 @@ void keep_shared(admm_handle* h, const admm_problem* p);
 bool problem_has_soc(const admm_problem* p);
 int validate_fuel(const admm_problem* p, const double* fuel, bool per_stage);
 int upload_kappa(admm_handle* h);
+// soft weights against a validated problem: cnt entries, >= 0, no NaN (+inf = hard), and +inf on the control rows of a stage with a
+// finite thrust bound or a positive fuel weight.  expanded = false: `soft` has lo's shape (nb entries with stage_bounds = 0, else nb N);
+// true: L entries (a handle's own copy).  fuel: N per-stage weights or NULL.
+int validate_soft(const admm_problem* p, const double* soft, bool expanded, const double* fuel);
 inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fuel.data() : nullptr; }
 
 // ---- per-instance dynamics (admm_pinst_rt.hip)

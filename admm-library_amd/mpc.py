@@ -77,7 +77,7 @@ def _noise(noise, steps, batch, n, m):
 
 
 def mpc_batch(problem: Problem, steps: int, options=None, plant=None, noise=None, tail: str = "copy", on_device: bool = True,
-              qp_solver=None, replay=None) -> MpcResult:
+              qp_solver=None, replay=None, on_step=None) -> MpcResult:
     """The closed loop over `steps` steps for a batch of QPs on one handle.
 
     plant = (Ap, Bp): the true plant (None: the model's A_0, B_0).  noise: see _noise.  tail: what the new last stage of the
@@ -86,7 +86,9 @@ def mpc_batch(problem: Problem, steps: int, options=None, plant=None, noise=None
     set_state).  replay = X of an earlier run: the recorded x+ are fed back (as x_meas on the device route) instead of
     evaluating the plant, so that two routes whose plant arithmetic rounds differently walk through the same QPs.
     qp_solver(problem, z0, y0) -> (w, z, y, iterations, converged): a stand-in for the handle (CPU tests drive the loop with
-    the oracle); it implies the host route, and z0 = y0 = None asks for a cold start."""
+    the oracle); it implies the host route, and z0 = y0 = None asks for a cold start.
+    on_step(t, solver, info): called after the solve of step t, before the step is taken, on the handle itself -- read-outs of the
+    window's solution (Solver.soft_report(), .certificate(), .infeasibility(), ...).  Not with qp_solver."""
     if tail not in TAILS:
         raise ValueError(f"tail must be one of {TAILS}, got {tail!r}")
     if steps < 1:
@@ -132,6 +134,10 @@ def mpc_batch(problem: Problem, steps: int, options=None, plant=None, noise=None
             info = s.solve()                        # (from the handle's state: zeros at step 0, the shifted solution afterwards)
             t1 = time.perf_counter()
             iters[t], nconv[t] = info.iters_run, info.n_converged
+            t2 = t1
+            if on_step is not None:
+                on_step(t, s, info)
+                t2 = time.perf_counter()            # (the read-outs belong to neither figure)
             if on_device:
                 kw = dict(x_meas=np.ascontiguousarray(replay[t + 1])) if replay is not None else \
                     dict(plant=None if plant is None else (Ap, Bp), dx=None if dx is None else dx[t])
@@ -143,5 +149,5 @@ def mpc_batch(problem: Problem, steps: int, options=None, plant=None, noise=None
                     q = shift_horizon(q, nb, tail)
                 s.update_instances(X[t + 1], q)
                 s.set_state(shift_horizon(w, nb, tail), shift_horizon(z, nb, tail), shift_horizon(y, nb, tail))
-            solve_ms[t], step_ms[t] = (t1 - t0) * 1e3, (time.perf_counter() - t1) * 1e3
+            solve_ms[t], step_ms[t] = (t1 - t0) * 1e3, (time.perf_counter() - t2) * 1e3
     return MpcResult(X, U, iters, nconv, solve_ms, step_ms)

@@ -47,6 +47,10 @@ class Problem:
     # control profile (u_{b,k} equal within a group; x0 and q stay per QP).  None = every QP on its own.  Batch-shared dynamics only.
     # (keyword only in practice: it sits before `fuel`, which stays the last field)
     consensus: Optional[int] = None
+    # soft box: weights s >= 0 in the shape of lo / hi ((n + m,), or (N, n + m) with per-stage bounds); the cost gains
+    # sum_rows s_i max(lo_i - w_i, 0, w_i - hi_i) and the row's box is no longer enforced absolutely.  +inf = a hard row, 0 = its box is
+    # ignored.  None = every row hard.  +inf on the control rows where unorm is finite or fuel positive.  Batch-shared dynamics only.
+    soft: Optional[np.ndarray] = None
     # minimum-fuel cost  + sum_k fuel_k ||u_k||_2  (fuel >= 0: scalar, or (N,) when the box is per stage); None = off.
     # Where positive, the box of the control rows must be (-inf, inf).  Batch-shared dynamics only.
     fuel: Optional[np.ndarray] = None
@@ -148,6 +152,24 @@ class Problem:
             pos = np.broadcast_to(fu, (lo_u.shape[0],)) > 0
             if np.any(np.isfinite(lo_u[pos])) or np.any(np.isfinite(hi_u[pos])):
                 raise ValueError("control rows must be unbounded (-inf, inf) where fuel is positive")
+        if self.soft is not None:
+            so = np.asarray(self.soft, np.float64)
+            if self.per_instance or self.lo.ndim == 3:
+                raise ValueError("soft needs batch-shared dynamics and a batch-shared box (A, B LTI or LTV)")
+            if so.shape not in ((n + m,), self.lo.shape):
+                raise ValueError("soft must have the shape of lo / hi: (n+m,), or (N, n+m) together with per-stage bounds")
+            if np.any(np.isnan(so)) or np.any(so < 0):
+                raise ValueError("soft must be >= 0 (inf = a hard row) and contain no NaN")
+            if self.consensus is not None:
+                raise ValueError("soft cannot be combined with consensus")
+            su = np.broadcast_to(so, self.lo.shape).reshape(-1, n + m)[:, :m]
+            hard = np.zeros(su.shape[0], bool)
+            if self.unorm is not None:
+                hard |= np.isfinite(np.broadcast_to(np.asarray(self.unorm, np.float64), hard.shape))
+            if self.fuel is not None:
+                hard |= np.broadcast_to(np.asarray(self.fuel, np.float64), hard.shape) > 0
+            if np.any(su[hard] != np.inf):
+                raise ValueError("soft must be inf on the control rows where unorm is finite or fuel is positive")
         if self.consensus is not None:
             G = int(self.consensus)
             if G != self.consensus or G < 1 or self.batch % G != 0:
@@ -181,6 +203,7 @@ class DeviceProblem:
     unorm: Optional["torch.Tensor"] = None      # 0-d, or (N,) with per-stage bounds
     name: str = ""
     consensus: Optional[int] = None             # Problem's field; scenario consensus has no device-memory setup (Solver refuses it)
+    soft: Optional["torch.Tensor"] = None       # Problem's field; soft constraints have no device-memory setup (Solver refuses it)
     fuel: Optional["torch.Tensor"] = None       # Problem's field; the device entry points have no fuel term (Solver refuses it)
 
     n = Problem.n
@@ -205,7 +228,8 @@ class DeviceProblem:
             return None if a is None else torch.as_tensor(np.ascontiguousarray(a, np.float64), device=device)
         return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
                    unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name,
-                   fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)), consensus=p.consensus)
+                   fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)), consensus=p.consensus,
+                   soft=None if p.soft is None else t(np.asarray(p.soft, np.float64)))
 
     def validate(self) -> None:
         """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
@@ -215,6 +239,8 @@ class DeviceProblem:
                              "give a Problem with NumPy arrays")
         if self.consensus is not None:
             raise ValueError("consensus: scenario consensus has no device-memory setup: give a Problem with NumPy arrays")
+        if self.soft is not None:
+            raise ValueError("soft: soft constraints have no device-memory setup: give a Problem with NumPy arrays")
         dev = self.x0.device if torch.is_tensor(self.x0) else None
         for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
             a = getattr(self, name)
@@ -506,3 +532,38 @@ def cw_formation_instances(N: int = 200, batch: int = 64, seed0: int = SEED0, u_
         lo[i] = np.concatenate([-um, [-np.inf] * 12])[None]
         hi[i] = np.concatenate([um, [np.inf] * 12])[None]
     return dataclasses.replace(base, A=A, B=B, lo=lo, hi=hi, name=f"cw_formation_instances_N{N}_b{batch}")
+
+
+def cw_corridor_mpc(N: int = 40, batch: int = 8, corridor: float = 0.25, disturbance: float = 0.05, soft: Optional[float] = None,
+                    seed0: int = SEED0, u_max: float = 0.2, dt: float = 2.0 * np.pi / 200):
+    """A receding-horizon workload for soft constraints: cw_rendezvous' dynamics, weights and input box over a
+    window of N steps of length dt, with a RADIAL CORRIDOR |x| <= corridor (row m of every block: the radial position) on every
+    stage, and a per-step radial disturbance for the closed loop.  Returns (problem, dx): dx is (steps = 3 N, batch, 6), a push of
+    `disturbance` km on the radial position at every step, outwards (scenario b alternates its sign), drawn as
+    disturbance * U(0.5, 1) from default_rng(seed0 + 7919 + b).  The corridor holds x0 with margin; a push of more than the
+    controls can take back in one step (B's radial column times u_max is ~ u_max dt^2 / 2, three orders below `disturbance`) puts
+    the measured state outside the corridor within a few steps, and x_1 of the next window cannot get back inside: the hard window
+    QP has no solution.  soft = None: the hard corridor; a number: that weight on the corridor rows (every other row +inf)."""
+    A, B = cw_matrices(dt)
+    Q = np.diag([1.0, 1.0, 1.0, 0.1, 0.1, 0.1]) * dt
+    R = np.eye(3) * dt
+    QN = np.diag([50.0, 50.0, 50.0, 20.0, 20.0, 20.0])
+    box = np.array([0.5 * corridor, 1.0, 0.5, 0.02, 0.02, 0.02])
+    x0 = np.empty((batch, 6))
+    steps = 3 * N
+    dx = np.zeros((steps, batch, 6))
+    for b in range(batch):
+        rng = np.random.default_rng(seed0 + b)
+        x0[b] = rng.uniform(-box, box)
+        rng = np.random.default_rng(seed0 + 7919 + b)
+        dx[:, b, 0] = (1.0 if b % 2 == 0 else -1.0) * disturbance * rng.uniform(0.5, 1.0, steps)
+    inf = np.inf
+    lo = np.array([-u_max] * 3 + [-corridor] + [-inf] * 5)
+    hi = np.array([u_max] * 3 + [corridor] + [inf] * 5)
+    sw = None
+    if soft is not None:
+        sw = np.full(9, inf)
+        sw[3] = float(soft)
+    p = Problem(N=N, A=A, B=B, Q=Q, R=R, QN=QN, x0=x0, lo=lo, hi=hi, soft=sw,
+                name=f"cw_corridor_mpc_N{N}_b{batch}" + ("" if soft is None else "_soft"))
+    return p, dx

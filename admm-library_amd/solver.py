@@ -90,6 +90,12 @@ _SIGNATURES = {
     "admm_setup_consensus": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p, C.c_int32]),
     "admm_get_consensus": (C.c_int, [C.c_void_p, c_double_p]),
     "admm_get_consensus_device": (C.c_int, [C.c_void_p, c_double_p, C.c_void_p]),
+    # soft box constraints (ADMM_HIP_HAS_SOFT): an exact L1 penalty on box violation per row
+    "admm_setup_soft": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p, c_double_p]),
+    "admm_set_soft": (C.c_int, [C.c_void_p, c_double_p]),
+    "admm_get_soft": (C.c_int, [C.c_void_p, c_double_p]),
+    "admm_get_soft_report": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p]),
+    "admm_get_soft_report_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, C.c_void_p]),
     # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
     "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
     "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
@@ -267,6 +273,16 @@ class Infeasibility:
     nu: object = None
 
 
+@dataclasses.dataclass
+class SoftReport:
+    """Solver.soft_report(): per QP, at the handle's z and over the rows with a finite soft weight: penalty =
+    sum s_i dist_i, max_violation = max dist_i, n_violated = rows with dist_i > 0 (int32).  NumPy arrays, or CUDA tensors with
+    device=True.  The total objective is Certificate.obj + penalty."""
+    penalty: object
+    max_violation: object
+    n_violated: object
+
+
 class Solver:
     """One handle = one batch of QPs on one GPU.
 
@@ -284,7 +300,7 @@ class Solver:
         co = self.options.to_c()
         on_device = isinstance(problem, DeviceProblem)
         if on_device:
-            problem.validate()               # (ValueError for a DeviceProblem with a fuel term: no device-memory form)
+            problem.validate()               # (ValueError for a DeviceProblem with a fuel term, groups or soft weights: no device-memory form)
             if timeshard is not None:
                 raise ValueError("time-sharded handles take host arrays (admm_setup_timeshard has no device-memory form)")
             if co.device < 0:
@@ -303,7 +319,13 @@ class Solver:
             _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
         elif timeshard is None:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
-            if problem.consensus is not None:
+            if problem.soft is not None:         # (validate() has refused soft together with consensus)
+                keep["soft"] = _abi.marshal_soft(problem)
+                if problem.fuel is not None:
+                    keep["fuel"] = _abi.marshal_fuel(problem)
+                _check(self._lib, self._lib.admm_setup_soft(C.byref(self._h), C.byref(cp), C.byref(co),
+                                                            dptr(keep["fuel"]) if "fuel" in keep else c_double_p(), dptr(keep["soft"])))
+            elif problem.consensus is not None:
                 if problem.fuel is not None:
                     keep["fuel"] = _abi.marshal_fuel(problem)
                 _check(self._lib, self._lib.admm_setup_consensus(C.byref(self._h), C.byref(cp), C.byref(co),
@@ -320,6 +342,8 @@ class Solver:
                 raise AdmmError(2, "a fuel term is not supported on time-sharded handles")
             if problem.consensus is not None:
                 raise AdmmError(2, "scenario consensus is not supported on time-sharded handles")
+            if problem.soft is not None:
+                raise ValueError("soft constraints are not supported on time-sharded handles")
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -402,6 +426,8 @@ class Solver:
         else:
             if problem.fuel is not None or getattr(self.problem, "fuel", None) is not None:
                 problem = self._keep_fuel(problem)
+            if problem.soft is not None or getattr(self.problem, "soft", None) is not None:
+                problem = self._keep_soft(problem)
             cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
             t0 = time.perf_counter()
             _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
@@ -438,6 +464,53 @@ class Solver:
         out = np.zeros(self.problem.N)
         _check(self._lib, self._lib.admm_get_fuel(self._h, dptr(out)))
         return out
+
+    def _keep_soft(self, problem):
+        """update_problem on a handle with soft weights: the handle's weights stay in force, per stacked row (admm_update_problem);
+        the problem that becomes self.problem carries them, and the new problem is validated against them."""
+        import dataclasses
+        if getattr(self.problem, "soft", None) is None:
+            raise ValueError("soft weights cannot be added to a handle: set up a new Solver")
+        cur = self.soft()                                                     # (N, n + m)
+        if problem.soft is not None and not np.array_equal(np.broadcast_to(np.asarray(problem.soft, np.float64), cur.shape), cur):
+            raise ValueError("update_problem keeps the handle's soft weights: change them with set_soft")
+        if problem.lo.ndim < 2 and np.any(cur != cur[0]):
+            raise ValueError("per-stage soft weights need per-stage bounds")
+        return dataclasses.replace(problem, soft=cur if problem.lo.ndim >= 2 else cur[0].copy())
+
+    def set_soft(self, soft):
+        """New weights of the soft box (the shape of lo / hi) on a handle set up with Problem.soft: continuation in the penalty, the
+        state kept as a warm start (admm_set_soft)."""
+        import dataclasses
+        if getattr(self.problem, "soft", None) is None:
+            raise AdmmError(1, "admm_set_soft: soft weights cannot be added to a handle (set Problem.soft)")
+        cand = dataclasses.replace(self.problem, soft=np.asarray(soft, np.float64))
+        cand.validate()
+        _check(self._lib, self._lib.admm_set_soft(self._h, dptr(_abi.marshal_soft(cand))))
+        self.problem = cand
+        self._warn()
+
+    def soft(self) -> np.ndarray:
+        """(N, n + m) weights of the soft box in force, per stacked row (inf everywhere on a handle without weights)."""
+        out = np.empty((self.problem.N, self.problem.nb))
+        _check(self._lib, self._lib.admm_get_soft(self._h, dptr(out)))
+        return out
+
+    def soft_report(self, device: bool = False) -> SoftReport:
+        """admm_get_soft_report: penalty, largest violation and number of violated rows of every QP at the handle's z, over the rows
+        with a finite weight, computed on the device.  device=True returns CUDA tensors through admm_get_soft_report_device, ordered
+        on torch's current stream."""
+        if device:
+            import torch
+            dev = f"cuda:{self._device()}"
+            pen, mx = (torch.empty(self.batch, dtype=torch.float64, device=dev) for _ in range(2))
+            cnt = torch.empty(self.batch, dtype=torch.int32, device=dev)
+            _check(self._lib, self._lib.admm_get_soft_report_device(self._h, _tptr(pen), _tptr(mx),
+                                                                   C.cast(C.c_void_p(cnt.data_ptr()), c_int32_p), _stream(dev)))
+            return SoftReport(pen, mx, cnt)
+        pen, mx, cnt = np.empty(self.batch), np.empty(self.batch), np.empty(self.batch, np.int32)
+        _check(self._lib, self._lib.admm_get_soft_report(self._h, dptr(pen), dptr(mx), iptr(cnt)))
+        return SoftReport(pen, mx, cnt)
 
     def set_rho(self, rho: float):
         _check(self._lib, self._lib.admm_set_rho(self._h, float(rho)))

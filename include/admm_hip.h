@@ -253,6 +253,44 @@ int admm_setup_consensus(admm_handle** out, const admm_problem* p, const admm_op
 int admm_get_consensus(admm_handle* h, double* ubar);
 int admm_get_consensus_device(admm_handle* h, double* ubar, void* hip_stream);
 
+/* Soft box constraints (new symbols, announced by ADMM_HIP_HAS_SOFT -- no struct or signature changed, ABI version
+ * unchanged): the box of chosen rows is enforced by an exact L1 penalty instead of absolutely.  `soft` has the shape of lo / hi --
+ * nb entries with stage_bounds = 0, nb N with stage_bounds = 1 --, every entry s >= 0; +inf keeps the row hard, 0 ignores its box.
+ * The cost gains
+ *
+ *     sum_rows s_i max(lo_i - w_i, 0, w_i - hi_i)
+ *
+ * and only the z-update changes: with v = w^ + y and kap_i = s_i / rho,  c = clip(v, lo, hi), e = v - c,
+ * z = |e| <= kap ? c : (e > 0 ? v - kap : v + kap), y = v - z.  The penalty is exact: for s above the row's multiplier in the hard
+ * problem the solutions coincide; where the hard problem has no solution the soft one is the least-violating at that price.
+ * mu = rho y keeps its meaning (rho y in s d dist(z)).  The control rows of a stage with a finite unorm or a positive fuel weight
+ * keep their shrink-and-scale projection: their entries must be +inf.
+ *
+ * admm_setup_soft: admm_setup_fuel (fuel may be NULL) with the weights.  ADMM_ERR_INVALID: soft = NULL, a negative or NaN entry, a
+ *   finite entry on such a control row.  ADMM_ERR_UNSUPPORTED: time_varying = 2, precision_mode other than ADMM_PRECISION_FP64.
+ *   (Time-sharded and consensus forms cannot be asked for: neither set-up call takes weights.)  Refused before a device is looked
+ *   for, nothing allocated.  The handle runs the unfused one-lane fp64 path (ADMM_FLAG_UNFUSED is set internally); the state is
+ *   always the (z, y) pair.  Everything else works as on any handle -- admm_solve*, admm_run / admm_iterate, admm_step_z, the
+ *   adaptive rule and admm_set_rho, q, over-relaxation, admm_update_instances*, admm_set_state* / admm_get*, admm_set_fuel,
+ *   admm_get_certificate*, ADMM_FLAG_GRAPH, admm_mpc_advance* (the weights are window-relative like the per-stage box: nothing
+ *   shifts), admm_profile with fused_path = 0 (fused_path != 0: ADMM_ERR_UNSUPPORTED).  admm_update_problem* keeps the weights, per
+ *   stacked row, and re-checks the control-row rule against the new problem.  admm_probe_infeasibility* treats a row with a finite
+ *   weight as open: a feasible QP is still never flagged.
+ * admm_set_soft: replace the weights (same shape) between iterations -- continuation in the penalty from a warm start.  Every check
+ *   comes first: a refused call changes nothing.  ADMM_ERR_INVALID on a handle set up without weights.
+ * admm_get_soft: the weights in force, one per stacked row (L doubles; +inf everywhere on a handle without weights).
+ * admm_get_soft_report: per QP, on the handle's z and over the rows with a finite weight: penalty = sum s_i dist_i (an fma chain in
+ *   row order), max_violation = max dist_i, n_violated = rows with dist_i > 0.  batch entries each; any pointer may be NULL, not all.
+ *   obj of admm_get_certificate does NOT include the penalty: the total objective is obj + penalty.
+ * admm_get_soft_report_device: the outputs are device memory of the handle's GPU, under the rules of admm_get_certificate_device
+ *   (n_violated: 4-byte alignment). */
+#define ADMM_HIP_HAS_SOFT 1
+int admm_setup_soft(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, const double* soft);
+int admm_set_soft(admm_handle* h, const double* soft);
+int admm_get_soft(admm_handle* h, double* soft);
+int admm_get_soft_report(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated);
+int admm_get_soft_report_device(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated, void* hip_stream);
+
 /* Warm start / test hook: overwrite device state.  Any pointer may be NULL
  * (left unchanged).  Each is L*batch and must be finite (ADMM_ERR_INVALID otherwise, nothing uploaded). */
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y);
@@ -333,7 +371,7 @@ int admm_get_device(admm_handle* h, double* w, double* z, double* y, void* hip_s
  *             the state rows of g + G'nu are zero by construction; B_k' nu_{k+1} is the primer vector
  *   stat      max_k |g^u_k - B_k' nu_{k+1}|_inf: the whole stationarity defect of the original QP (not of the ADMM splitting)
  *   feas_dyn  max_k |x_{k+1} - A_k x_k - B_k u_k|_inf on z
- *   obj       1/2 z'Pz + q'z + sum_k fuel_k ||z_u,k||_2  (the weights of admm_get_fuel)
+ *   obj       1/2 z'Pz + q'z + sum_k fuel_k ||z_u,k||_2  (the weights of admm_get_fuel; NOT the penalty of a soft box: admm_get_soft_report)
  * Any output pointer may be NULL; obj, feas_dyn, stat: batch entries; nu: N*n*batch, QP b at [b*N*n, (b+1)*N*n), stage-major
  * (nu_1 .. nu_N).  The call brings the state into the (z, y) pair exactly as admm_get does and changes nothing else: iterating
  * on gives the same bits as after admm_get.  Only what was asked for is copied out (batch doubles per scalar output).
