@@ -13,9 +13,16 @@ Built only from what the suite already trusts:
                         pins the loop against one oracle_c.solve with the stopping and adaptive rules
   step_x / step_z       admm_ref.factor, x_update, z_update (tests/_fuel_ref.prox with a fuel term)
   certificate           tests/_cert_ref.certificate
+  soft / consensus      tests/_soft_ref.solve, prox, report; tests/_consensus_ref.solve, prox, consensus_of
+  mpc_advance           admm_library_amd.mpc: shift_horizon, plant_step, model_plant
+  infeasibility         tests/_infeas_ref.probe on the handle's problem with the box of every finite-weight row removed
 
 A call the header refuses raises Refused(code) and changes nothing.  `margins` collects every comparison of the stopping and
-adaptive rules the model took, as (what, lhs, threshold): the host test keeps them away from their thresholds.
+adaptive rules the model took, as (what, lhs, threshold): the host test keeps them away from their thresholds -- and those of the
+probe (sep against -eps, the open-row magnitude against eps |mu|_inf); `unclear` lists the probe's decisions mu = 0 and lambda = 0 (a
+number against +inf in sep and defect) that are neither clearly nonzero nor zero by construction: there `defect` is a quotient of two
+rounding errors, and the probe's read-out says so per QP (defect_clear).  `soft_rows` counts, per soft report, the finite-weight rows
+that are neither clearly outside their box, nor clearly inside, nor exactly on a bound with |y| clear of s / rho.
 """
 import dataclasses
 
@@ -24,7 +31,13 @@ import numpy as np
 import admm_ref as ar
 import oracle_c as oc
 import _cert_ref as cr
+import _consensus_ref as cs
 import _fuel_ref as fr
+import _infeas_ref as ir
+import _soft_ref as sr
+from admm_library_amd import mpc
+
+PRECISION_MIXED = 1
 
 INVALID, UNSUPPORTED, NUMERIC = 1, 2, 5
 
@@ -49,10 +62,13 @@ class HandleModel:
         self.resid = None            # (r, s, nw, nz, ny) of the last residual-evaluating iteration
         self.info = None             # dict of the last solve
         self.alternating = alternating
-        self.fused = fused
+        self.fused = fused and problem.soft is None and problem.consensus is None    # (such handles run the unfused path only)
         self.pair_form = True        # the state is held as the (z, y) pair (admm_profile modes 2 / 3 then add one iteration)
         self.iterations = 0          # applied since set-up
         self.margins = []
+        self.probes = 0              # probes so far
+        self.unclear = []            # (probe, what, QP, value, rounding scale) of a zero / nonzero decision that rounding could flip
+        self.soft_rows = []          # per soft report: (rows with a finite weight, rows of none of the three kinds)
         self._subs = None
         self._it = 0
         self._status = np.zeros(B, np.int32)
@@ -76,6 +92,9 @@ class HandleModel:
             outs = [oc.solve(self._sub(b), rho=float(self.rho[b]), z0=self.z[b:b + 1], y0=self.y[b:b + 1], nthreads=1, **kw)
                     for b in range(self.p.batch)]
             self.w, self.z, self.y = (np.concatenate([o[k_] for o in outs]) for k_ in ("w", "z", "y"))
+        elif self.p.soft is not None or self.p.consensus is not None:
+            o = (sr if self.p.soft is not None else cs).solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw)
+            self.w, self.z, self.y = o.w, o.z, o.y
         elif self.p.fuel is not None:
             o = fr.solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw)
             self.w, self.z, self.y = o.w, o.z, o.y
@@ -109,6 +128,8 @@ class HandleModel:
             raise Refused(UNSUPPORTED, "the alternating-direction kernels are not enabled")
         if self.per_qp and mode != 1:
             raise Refused(UNSUPPORTED, "per-instance dynamics: mode 1 only")
+        if (self.p.soft is not None or self.p.consensus is not None) and mode != 0:
+            raise Refused(UNSUPPORTED, "soft and scenario-consensus handles run the unfused path only")
         k = {0: iters, 1: iters, 2: 2 * iters + 1, 3: 1}[mode] + (1 if mode in (2, 3) and self.pair_form else 0)
         self._advance(k, k if residuals else 0)
         if mode == 0:
@@ -138,10 +159,16 @@ class HandleModel:
             raise Refused(UNSUPPORTED, "no standalone z kernel with per-instance bounds")
         lo, hi = self._bounds()
         un = ar.expand_unorm(p.unorm, p.N)
-        if p.fuel is not None:
+        if p.fuel is not None or p.soft is not None or p.consensus is not None:
             wh = self.alpha * self.w + (1.0 - self.alpha) * self.z if self.alpha != 1.0 else self.w
             v = wh + self.y
-            zn = fr.prox(v, lo, hi, un, fr.expand_fuel(p.fuel, p.N) / self.rho, p.m)
+            kap = fr.expand_fuel(p.fuel, p.N) / self.rho
+            if p.soft is not None:
+                zn = sr.prox(v, lo, hi, un, kap, p.m, sr.expand_soft(p.soft, p.N, p.nb) / self.rho)
+            elif p.consensus is not None:
+                zn = cs.prox(v, lo, hi, un, kap, p.m, int(p.consensus))
+            else:
+                zn = fr.prox(v, lo, hi, un, kap, p.m)
             yn = v - zn
         else:
             zn, yn = ar.z_update(self.w, self.z, self.y, lo, hi, self.alpha, None if p.unorm is None else un, p.m)
@@ -199,7 +226,10 @@ class HandleModel:
             raise Refused(INVALID, "lo > hi")
         if (new.q is None) != (p.q is None) or (new.unorm is None) != (p.unorm is None) or new.per_instance != p.per_instance:
             raise Refused(INVALID, "problem class changed")
-        self.p = dataclasses.replace(new, fuel=p.fuel)         # the handle's fuel weights stay in force
+        if p.soft is not None:
+            self._check_soft(new, p.soft, p.fuel)              # the control-row rule against the new problem
+        # the handle's fuel weights, soft weights and groups stay in force
+        self.p = dataclasses.replace(new, fuel=p.fuel, soft=p.soft, consensus=p.consensus)
         self._subs = None
         self.pair_form = True
 
@@ -209,8 +239,93 @@ class HandleModel:
         fuel = np.asarray(fuel, np.float64)
         if not np.all(np.isfinite(fuel)) or np.any(fuel < 0):
             raise Refused(INVALID, "fuel must be finite and >= 0")
+        if self.p.soft is not None:
+            self._check_soft(self.p, self.p.soft, fuel)        # a stage that gains a weight must hold no finite soft weight on its control rows
         self.p = dataclasses.replace(self.p, fuel=fuel.copy())
         self.pair_form = True
+
+    @staticmethod
+    def _check_soft(p, soft, fuel):
+        """validate_soft: no NaN, every weight >= 0, +inf on the control rows of a stage with a finite thrust bound or a positive
+        fuel weight."""
+        sw = sr.expand_soft(soft, p.N, p.nb).reshape(p.N, p.nb)
+        if not np.all(sw >= 0.0):
+            raise Refused(INVALID, "soft entries must be >= 0 (+inf = a hard row) and not NaN")
+        shrink = np.isfinite(ar.expand_unorm(p.unorm, p.N)) | (fr.expand_fuel(fuel, p.N) > 0)
+        if np.any(sw[shrink, :p.m] != np.inf):
+            raise Refused(INVALID, "soft entries of the control rows must be +inf where unorm is finite or fuel is positive")
+
+    def set_soft(self, soft):
+        if self.p.soft is None:
+            raise Refused(INVALID, "soft weights cannot be added to a handle")
+        soft = np.asarray(soft, np.float64)
+        self._check_soft(self.p, soft, self.p.fuel)
+        self.p = dataclasses.replace(self.p, soft=soft.copy())
+
+    def mpc_advance(self, plant=None, du=None, dx=None, x_meas=None, q_tail=None, tail="copy"):
+        """admm_mpc_advance: u = z_u,0 + du, x0 <- x+ (the plant's, or x_meas), w, z, y and q one stage on -> dict(u=, x_next=)."""
+        p = self.p
+        if p.consensus is not None:
+            raise Refused(UNSUPPORTED, "not available on a scenario-consensus handle")
+        if self.per_qp:
+            raise Refused(UNSUPPORTED, "not available with per-instance dynamics")
+        if x_meas is not None and (plant is not None or dx is not None):
+            raise Refused(INVALID, "x_meas replaces the plant: Ap, Bp and dx must be absent with it")
+        if q_tail is not None and p.q is None:
+            raise Refused(INVALID, "q_tail on a handle that was set up without q")
+        given = list(plant or ()) + [a for a in (du, dx, x_meas, q_tail) if a is not None]
+        if any(not np.all(np.isfinite(np.asarray(a, np.float64))) for a in given):
+            raise Refused(INVALID, "non-finite entry in an input")
+        u = self.z[:, :p.m].copy() if du is None else self.z[:, :p.m] + du
+        if x_meas is not None:
+            xn = np.array(x_meas, np.float64)
+        else:
+            Ap, Bp = mpc.model_plant(p) if plant is None else plant
+            xn = mpc.plant_step(p.x0, u, Ap, Bp, dx)
+        q = None if p.q is None else mpc.shift_horizon(p.q, p.nb, tail, q_tail)
+        self.p = dataclasses.replace(p, x0=xn, q=q)
+        self._subs = None
+        self.w, self.z, self.y = (mpc.shift_horizon(a, p.nb, tail) for a in (self.w, self.z, self.y))
+        self.pair_form = True
+        return dict(u=u, x_next=xn.copy())
+
+    def opened(self):
+        """The feasibility problem of the handle: the box of every row with a finite soft weight removed."""
+        p = self.p
+        if p.soft is None:
+            return p
+        fin = np.isfinite(np.broadcast_to(np.asarray(p.soft, np.float64), np.shape(p.lo)))
+        return dataclasses.replace(p, lo=np.where(fin, -np.inf, p.lo), hi=np.where(fin, np.inf, p.hi), soft=None)
+
+    def infeasibility(self, span=10, eps=1e-6, costates=False):
+        """admm_probe_infeasibility: keeps y, runs `span` iterations as run(span, 0) does -> the reference's probe of the two y
+        (nu left out without `costates`)."""
+        span = int(span)
+        if span < 1 or not (np.isfinite(eps) and eps >= 0.0):
+            raise Refused(INVALID, "span must be >= 1, eps finite and >= 0")
+        if self.per_qp or self.p.consensus is not None or self.opt.precision_mode == PRECISION_MIXED:
+            raise Refused(UNSUPPORTED, "per-instance dynamics, scenario consensus and the mixed-precision mode have no probe")
+        y0 = self.y.copy()
+        self._advance(span, 0)                  # (the state afterwards is that of get; run(span, 0); get: a get leaves the form alone)
+        ref = ir.probe(self.opened(), y0, self.y, span, eps)
+        # mu = 0 and lambda = 0 decide between a number and +inf (sep, defect): clear when the value stands out of the rounding of y, or
+        # is zero because every y entry that feeds it is -- state rows for mu (nu, and with it mu, is built from lambda^x alone), every
+        # row for lambda
+        m_, nb = self.p.m, self.p.nb
+        clear = np.ones(self.p.batch, bool)
+        for b in range(self.p.batch):
+            both = np.stack([y0[b], self.y[b]]).reshape(2, self.p.N, nb)
+            noise = 1e-9 * max(1.0, np.abs(both).max()) / span          # (ten times the tolerance of y, over span)
+            for what, v, rows in (("mu_max>0", ref["mu_max"][b], both[:, :, m_:]), ("drift>0", ref["drift"][b], both)):
+                if not (v > noise or (v == 0.0 and not rows.any())):
+                    self.unclear.append((self.probes, what, b, float(v), noise))
+                    clear[b] = False
+            if ref["mu_max"][b] > 0.0:
+                self.margins.append(("open<=eps*mu_max", float(ref["open"][b]), float(eps * ref["mu_max"][b])))
+            if np.isfinite(ref["sep"][b]):
+                self.margins.append(("sep<-eps", float(ref["sep"][b]), -float(eps)))
+        self.probes += 1
+        return dict(ref, costates=bool(costates), eps=float(eps), defect_clear=clear)
 
     # ---- solve ------------------------------------------------------------------------------------------------------------
     def solve_begin(self):
@@ -321,3 +436,27 @@ class HandleModel:
         if self.per_qp:
             raise Refused(UNSUPPORTED, "no certificate with per-instance dynamics")
         return cr.certificate(self.p, self.z, self.y, self.rho)
+
+    def soft_report(self):
+        """admm_get_soft_report -> dict(penalty, max_violation, n_violated, weight_sum: the sum of the finite weights)."""
+        p = self.p
+        if p.soft is None:
+            raise Refused(INVALID, "the handle has no soft weights")
+        pen, mx, cnt = sr.report(p, self.z)
+        sw = sr.expand_soft(p.soft, p.N, p.nb)
+        fin = np.isfinite(sw)
+        # every finite-weight row: outside its box, inside it, or exactly on a bound with |y| away from s / rho
+        lo, hi = self._bounds()
+        z, y = self.z[:, fin], self.y[:, fin]
+        lo, hi, kap = lo[fin], hi[fin], sw[fin] / self.rho
+        clear = 1e-6 * max(1.0, np.abs(self.z).max())
+        outside = np.maximum(lo - z, z - hi) > clear
+        inside = np.minimum(z - lo, hi - z) > clear
+        on = ((z == lo) | (z == hi)) & (np.abs(np.abs(y) - kap) > 1e-6 * np.maximum(np.abs(y), kap))
+        self.soft_rows.append((int(fin.sum()) * p.batch, int((~(outside | inside | on)).sum())))
+        return dict(penalty=pen, max_violation=mx, n_violated=cnt, weight_sum=float(sw[fin].sum()))
+
+    def consensus(self):
+        if self.p.consensus is None:
+            raise Refused(INVALID, "the handle has no scenario groups")
+        return cs.consensus_of(self.p, self.z)

@@ -24,14 +24,14 @@ def pin_terminal(p):
     return p
 
 
-def di_pinned():
-    p = pkg.double_integrator(N=12, batch=6)
+def di_pinned(N=12):
+    p = pkg.double_integrator(N=N, batch=6)
     x0 = np.array([[0.5, 0.0], [1.0, 0.5], [3.0, 0.0], [6.0, 1.0], [10.0, 0.0], [-8.0, -1.0]])
     return pin_terminal(dataclasses.replace(p, x0=x0))
 
 
-def di_position_box():
-    p = per_stage(pkg.double_integrator(N=12, batch=4))
+def di_position_box(N=12):
+    p = per_stage(pkg.double_integrator(N=N, batch=4))
     p.lo[:, p.m] = -1.0
     p.hi[:, p.m] = 1.0
     return dataclasses.replace(p, x0=np.array([[0.9, 0.0], [0.9, 3.0], [0.0, 8.0], [-0.5, -6.0]]))

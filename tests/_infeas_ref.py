@@ -24,7 +24,8 @@ def stage_unorm(p):
 
 
 def probe(p, y_before, y_after, span, eps, dtype=np.float64):
-    """dict(sep, drift, defect, sep_abs, mu_max: (batch,); infeasible: (batch,) int32; nu: (batch, N, n)), as arrays of `dtype`.
+    """dict(sep, drift, defect, sep_abs, mu_max, open: (batch,); infeasible: (batch,) int32; nu: (batch, N, n)), as arrays of `dtype`;
+    open is the largest |mu_i| over the rows whose needed bound is infinite, the left side of the ray test open <= eps |mu|_inf.
 
     dtype=np.longdouble: the same table with every operand (the fp64 data of the problem, both y, span, eps) converted first and
     every operation in extended precision -- what a faithful evaluation is measured against."""
@@ -75,7 +76,39 @@ def probe(p, y_before, y_after, span, eps, dtype=np.float64):
     sep = np.where(ray, sig / safe, inf)
     defect = np.where(mu_max > zero, d_max / safe, np.where(d_max > zero, inf, zero))
     return dict(sep=sep, drift=drift, defect=defect, infeasible=(sep < -eps).astype(np.int32), nu=nu,
-                sep_abs=np.where(ray, sig_abs / safe, zero), mu_max=mu_max)
+                sep_abs=np.where(ray, sig_abs / safe, zero), mu_max=mu_max, open=opn)
+
+
+def check(ref, r, eps, tol=1e-10, flags_exact=False, defect_on=None):
+    """All outputs of a device probe `r` (sep, drift, defect, infeasible, nu or None) against probe()'s `ref`, on the scales of the
+    file header of tests/test_gpu_infeas.py: +inf must match as +inf; a flag may differ from the reference's only where sep sits
+    within the comparison's tolerance of -eps (flags_exact: nowhere).  defect_on: the QPs on which defect is compared (all: where mu and
+    lambda are rounding errors of a stationary y, their quotient is one too).  -> {output: worst error / tolerance}."""
+    on = np.ones(ref["sep"].shape[0], bool) if defect_on is None else np.asarray(defect_on, bool)
+    batch = ref["sep"].shape[0]
+    s_nu = np.maximum(1.0, np.abs(ref["nu"]).reshape(batch, -1).max(axis=1))
+    for name, got in (("sep", r.sep), ("defect", r.defect)):
+        d = np.flatnonzero((np.isinf(got) != np.isinf(ref[name])) & (on | (name == "sep")))
+        assert d.size == 0, (name + ": +inf on other QPs than the reference's", d, got[d], ref[name][d], "mu_max", ref["mu_max"][d],
+                             "drift", r.drift[d], ref["drift"][d])
+    assert np.all(r.sep[np.isinf(r.sep)] > 0)
+    fs, fd = np.isfinite(ref["sep"]), np.isfinite(ref["defect"]) & on
+    ratio_mu = np.where(ref["mu_max"] > 0, s_nu / np.where(ref["mu_max"] > 0, ref["mu_max"], 1.0), 1.0)
+    ratios = {"sep": (np.abs(r.sep - ref["sep"])[fs] / (tol * np.maximum(1.0, ref["sep_abs"])[fs])).max(initial=0.0),
+              "drift": (np.abs(r.drift - ref["drift"]) / (tol * np.maximum(1.0, ref["drift"]))).max(),
+              "defect": (np.abs(r.defect - ref["defect"])[fd] /
+                         (tol * np.maximum(np.maximum(1.0, ref["defect"]), ratio_mu))[fd]).max(initial=0.0)}
+    if r.nu is not None:
+        ratios["nu"] = (np.abs(r.nu - ref["nu"]).reshape(batch, -1).max(axis=1) / (tol * s_nu)).max()
+    print("error / tolerance:", {k: float(f"{v:.3g}") for k, v in ratios.items()}, "finite sep:", int(fs.sum()), "of", batch,
+          "flags:", int(ref["infeasible"].sum()))
+    for name, v in ratios.items():
+        assert v <= 1.0, (name, v)
+    near = fs & (np.abs(ref["sep"] + eps) <= tol * np.maximum(1.0, ref["sep_abs"]))
+    if flags_exact:
+        assert not near.any(), ("a sep within the tolerance of -eps", ref["sep"][near])
+    assert r.infeasible.dtype == np.int32 and np.array_equal(r.infeasible[~near], ref["infeasible"][~near])
+    return ratios
 
 
 def dense_farkas(p, b, nu, open_tol=0.0):

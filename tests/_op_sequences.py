@@ -9,6 +9,12 @@ call, read-out, solve.  The class of every op of a sequence follows a random Eul
 (loops included) over the classes of the kind: EVERY ordered pair of classes occurs as neighbours in every sequence (50 ops with
 seven classes, 37 on the kind without a solve), and read-outs come where the circuit puts them, not after every op -- a read-out
 brings the hidden state of a handle into its normal form.  Within a class the op and its arguments are drawn at random.
+
+A kind with ext=True also draws the receding-horizon step (admm_mpc_advance*, a state change), the infeasibility probe (a class of its
+own, "probe": an iteration call and a read-out at once -- 65 ops with eight classes), and, on a handle with soft weights or scenario
+groups, admm_set_soft, the soft report and the consensus read-out, with the calls such handles refuse in the refused class.  There
+the ops of a class are dealt from a shuffled deck, so that three seeds hold every one.  The kinds without the flag keep their
+sequences to the bit (DIGESTS, asserted by tests/test_handle_model_host.py).
 """
 import dataclasses
 
@@ -17,9 +23,10 @@ import numpy as np
 import admm_library_amd as pkg
 from admm_library_amd import _abi
 
-CLASSES = ("odd", "even", "resid", "change", "refused", "readout", "solve")
+CLASSES = ("odd", "even", "resid", "change", "refused", "readout", "solve", "probe")
 MAX_ITERATIONS = 200           # per sequence: the range over which test_config2_slice_many_iterations holds 1e-10
 SOLVE = dict(eps_abs=1e-2, eps_rel=1e-2, max_iter=12, check_interval=4)
+PROBE_EPS = 1e-6
 ADAPT = dict(adapt_interval=4, adapt_mu=2.0, adapt_tau=2.0, adapt_max=16)
 F = _abi
 
@@ -42,8 +49,62 @@ def _fuel(seed, dN=0):
     return dataclasses.replace(p, fuel=np.where(np.isfinite(p.unorm), w, 0.0))      # a weight only where the controls have no box
 
 
+def _soft_box(batch):
+    def make(seed, dN=0):
+        from test_soft_host import random_soft
+        p = pkg.random_ltv(N=33 + dN, n=6, m=3, batch=batch, seed=seed)
+        return dataclasses.replace(p, soft=random_soft(p))                          # (the weights of every variant: a handle keeps its own)
+    return make
+
+
+SOFT_FUEL_STAGE = 8            # of _soft_fuel: no thrust bound, no fuel weight, an open control box and finite soft weights on it
+
+
+def _soft_fuel(seed, dN=0):
+    """_fuel with soft weights on the state rows, and one stage on which admm_set_fuel must refuse a weight."""
+    from test_soft_host import random_soft
+    p = _fuel(seed, dN)
+    k, m = SOFT_FUEL_STAGE, p.m
+    assert not np.isfinite(p.unorm[k]) and p.fuel[k] == 0.0
+    lo, hi = p.lo.copy(), p.hi.copy()
+    lo[k, :m], hi[k, :m] = -np.inf, np.inf
+    sw = random_soft(p)
+    sw[:, :m] = np.inf
+    sw[k, :m] = 0.3
+    return dataclasses.replace(p, lo=lo, hi=hi, soft=sw)
+
+
+def _consensus(G, fuel=False, **kw):
+    def make(seed, dN=0):
+        p = pkg.random_ltv(**dict(kw, N=kw["N"] + dN, seed=seed, thrust_norm=fuel))
+        if fuel:
+            w = np.random.default_rng(seed + 99).uniform(0.02, 0.3, p.N)
+            p = dataclasses.replace(p, fuel=np.where(np.isfinite(p.unorm), w, 0.0))
+        return dataclasses.replace(p, consensus=G)
+    return make
+
+
+def _di(name):
+    """tests/_infeas_cases.py's problem; the variants of admm_update_problem scale Q, R, QN only (the feasible set stays)."""
+    def make(seed, dN=0):
+        import _infeas_cases as ic
+        p = getattr(ic, name)(N=12 + dN)
+        c = 1.0 + 0.25 * (seed - 10)
+        return dataclasses.replace(p, Q=p.Q * c, R=p.R * c, QN=p.QN * c)
+    return make
+
+
+def _soft_di(seed, dN=0):
+    """di_position_box with the corridor soft (tests/test_gpu_soft.py: no QP is flagged then); admm_set_soft makes it hard again."""
+    p = _di("di_position_box")(seed, dN)
+    sw = np.full(p.lo.shape, np.inf)
+    sw[:, p.m] = 5.0
+    return dataclasses.replace(p, soft=sw)
+
+
 _FIRST = dict(N=33, n=6, m=3, batch=69, with_q=False)
 _THRUST = dict(N=37, n=6, m=3, batch=9, thrust_norm=True)
+_LEAN = dict(N=45, n=6, m=3, batch=67, with_q=False, state_bounds=False)
 
 # make(seed, dN): the problem of variant `seed` (1 = set-up, others = admm_update_problem), dN: another horizon (a refused update)
 # family: path()["kernel_family"] at set-up; alt: profile modes 2 / 3 are drawn; tol: iterates and residuals
@@ -77,7 +138,112 @@ KINDS = {
     "pinst_wide_one_segment": dict(make=_inst(N=20, n=12, m=6, batch=5), opt=dict(rho=0.3, segments=1), pinst=True),
     "pinst_wide_four_segments": dict(make=_inst(N=20, n=12, m=6, batch=5), opt=dict(rho=0.3, segments=4), pinst=True),
 }
+OLD_KINDS = tuple(KINDS)
+
+# The kinds with the receding-horizon step and the probe (ext=True).  soft / consensus: such a handle runs the unfused path only.
+# stationary_rows: the largest share of the probed QPs on which mu or lambda may be a rounding error of a stationary y (rows violated
+# for good hold y = s / rho); elsewhere the committed seeds have none (tests/test_handle_model_host.py).
+KINDS.update({
+    # odd batch with a pad column; chunks of 8 rows, the last short and no multiple of 4; kappa under the adaptive rule
+    "soft_box_relaxed": dict(make=_soft_box(69), opt=dict(rho=0.3, alpha=1.6, segments=4, zrows=8, **ADAPT), ext=True, soft=True,
+                             unfused=True, family="one_lane_fp64", seeds=(2, 4, 8), stationary_rows=0.05),
+    # block-structured chunks (two blocks each); admm_set_fuel and admm_set_soft interleaved
+    "soft_fuel_thrust": dict(make=_soft_fuel, opt=dict(rho=0.3, segments=5, zrows=18), ext=True, soft=True, fuel=True, unfused=True,
+                             family="one_lane_fp64", seeds=(2, 3, 4)),
+    # kappa changing under a captured graph
+    "soft_graph": dict(make=_soft_box(129), opt=dict(rho=0.3, alpha=1.6, segments=4, zrows=8, flags=F.FLAG_GRAPH), ext=True,
+                       soft=True, unfused=True, family="one_lane_fp64", seeds=(3, 4, 7), stationary_rows=0.05),
+    # groups inside one lane pair / wave
+    "consensus_G3": dict(make=_consensus(3, N=33, n=6, m=3, batch=15), opt=dict(rho=0.3, alpha=1.6, segments=4, **ADAPT), ext=True,
+                         consensus=True, unfused=True, family="one_lane_fp64"),
+    # a group across a wave, pad columns; two blocks per chunk
+    "consensus_G65_fuel": dict(make=_consensus(65, fuel=True, N=37, n=6, m=3, batch=195), opt=dict(rho=0.3, segments=5, zrows=18),
+                               ext=True, consensus=True, fuel=True, unfused=True, family="one_lane_fp64"),
+    # a group wider than a workgroup's tile (256 columns at m = 6): the two-pass route
+    "consensus_wide": dict(make=_consensus(300, N=10, n=12, m=6, batch=600), opt=dict(rho=0.3), ext=True, consensus=True,
+                           unfused=True, family="one_lane_fp64"),
+    "one_lane_alt_ext": dict(make=_ltv(N=30, n=4, m=2, batch=300), opt=dict(rho=0.3, segments=4, flags=F.FLAG_NO_MFMA),
+                             family="one_lane_fp64", alt=True, device_io=True, ext=True, seeds=(1, 4, 6)),
+    "lean_xfree_ext": dict(make=_ltv(**_LEAN), opt=dict(rho=0.3, segments=4, flags=F.FLAG_NO_MFMA), family="one_lane_fp64", alt=True,
+                           ext=True, seeds=(2, 4, 5)),
+    "plain_fused_ext": dict(make=_ltv(**_FIRST), opt=dict(rho=0.3, segments=4, flags=F.FLAG_NO_ALTERNATE), ext=True),
+    "unfused_ext": dict(make=_ltv(**_FIRST), opt=dict(rho=0.3, segments=4, flags=F.FLAG_UNFUSED), unfused=True, ext=True,
+                        seeds=(2, 3, 4)),
+    "graph_replay_ext": dict(make=_ltv(**_FIRST), opt=dict(rho=0.3, segments=4, flags=F.FLAG_NO_MFMA | F.FLAG_GRAPH),
+                             family="one_lane_fp64", alt=True, ext=True, seeds=(1, 2, 4)),
+    "mfma_fp64_ext": dict(make=_formation, opt=dict(rho=0.05, precision_mode=F.PRECISION_FP64_MFMA), family="mfma_fp64", alt=True,
+                          ext=True),
+    "fuel_thrust_ext": dict(make=_fuel, opt=dict(rho=0.3, segments=5), fuel=True, ext=True),
+    # flags of both values: infeasible QPs beside a feasible one (tests/_infeas_cases.py, rho = its RHO)
+    "probe_di_position_box": dict(make=_di("di_position_box"), opt=dict(rho=1.0), ext=True),
+    "probe_di_pinned": dict(make=_di("di_pinned"), opt=dict(rho=1.0), ext=True),
+    # the probe's bound table after admm_set_soft: the corridor rows go from open to hard and back, the flags with them
+    "soft_probe_corridor": dict(make=_soft_di, opt=dict(rho=1.0), ext=True, soft=True, unfused=True, hard_or_soft=True,
+                                seeds=(5, 7, 8), stationary_rows=0.25),
+})
+NEW_KINDS = tuple(k for k in KINDS if k not in OLD_KINDS)
 SEEDS = (1, 2, 3)
+
+# sha256 of repr(sequence(kind, seed)) of the kinds that predate ext=True, taken before the flag existed: their sequences stay as they were
+DIGESTS = {
+    ("one_lane_alt", 1): "b7d292afd9bee50bb1a5e80a466960925ff812515f321ab4a308ab4d612fb04f",
+    ("one_lane_alt", 2): "9dfceecdb88200105ac1a9d491da4381e27212f9d78e5fad031ffb0917522ce1",
+    ("one_lane_alt", 3): "1981d8718250503de2263e14000c355a0774790a9daeb173ce5443fcc2cf4569",
+    ("one_lane_alt_relaxed", 1): "ce3158f646e7acfdeb30c15716f1a7f0923d403dd4a9de7d26777412515b8647",
+    ("one_lane_alt_relaxed", 2): "cc90c47a2360ba776e6b4c20e77738436afc4cffc3fe4cadaccc8d71a192138f",
+    ("one_lane_alt_relaxed", 3): "3ed4f704a35f287bfc3fe8385dfd52f4386c585fb7a9a2e1b1eb8791deb0969b",
+    ("with_q_two_blocks", 1): "6b777f0c2387304012e8d62eef9bd3164f644a19c0f8400855303700193712b1",
+    ("with_q_two_blocks", 2): "94f187659063040c5ed3d8fb9d3bc39024cf35b420c4db94a247fda04dde6280",
+    ("with_q_two_blocks", 3): "1c991e9925ec3480ea9edffd5b5472d37c51feb577fd5dbc136168eb3d7cde7b",
+    ("lean_xfree", 1): "d844bbf7c47f7f3a68314704af92face44f64a114cb872760b119598ca7a43d4",
+    ("lean_xfree", 2): "9e954c91e4105fa065a025567b7a2c8f02ff69195da808b96b3256ca51d61a22",
+    ("lean_xfree", 3): "99445ec516f104fe534c13550ab74bfcd2846e66597d430cc98d2d9e798ec577",
+    ("plain_fused", 1): "182ca7eef3a0ff4c13a00da512fb234fd1442ecb24195f82d22159122a4a4d00",
+    ("plain_fused", 2): "875ad1286e36e25f2f9b12d3bf3d05f57a9c6689ec05de4c8b16f3df1315d0e5",
+    ("plain_fused", 3): "18402256e2df58ad210da1b2c7067821b4fcb85e598a9dc5ed365e78b0d4eb4d",
+    ("plain_fused_chain", 1): "c1547ade80256d3b97ec3e7257926490213a3854354df85c50e5ab7451baa2bd",
+    ("plain_fused_chain", 2): "00380f76e1c8d850f2708482aa48b995def2ea3a759f6b440806810aeaf73d9e",
+    ("plain_fused_chain", 3): "da07d86a83cd819dde627343416f26d259d61045ef47e0ab5287ea15ba0c4e8a",
+    ("unfused", 1): "cba584be7ccf8a443ada5921312a26ed0c0aeffc3cffe681a9b45b92ec7c839a",
+    ("unfused", 2): "ec5830c30cba5b6235c7d92f73a3272a8f85c5479777d53d5958cedc58a4c953",
+    ("unfused", 3): "821ea96050213ba80f9ffbb6d774be24036ebea26e3b68b6df1abee9def99508",
+    ("graph_replay", 1): "16e0df7119369fffa703c0ec5e5f88a2a6eea484d2c485db4d9ad178f2359801",
+    ("graph_replay", 2): "b6ffd9197d94d41aa08e1e00fa69aa1a11f6cbb6dda02bc488ba3ace0a1a65fb",
+    ("graph_replay", 3): "d01ced0d1d6f42bb70f1789b5f35a92387d1fd11b864f25e35184c49a0698415",
+    ("thrust_bound", 1): "482e3a2055ab032d6db0275ccfe31179c63b669e056b6f00c48178c7175db581",
+    ("thrust_bound", 2): "461a69dc04e0b9829d98d23861e68dfc132801783d884ff7971a039b4e39ab0a",
+    ("thrust_bound", 3): "0f5e2692b8e9715ff693961e12e55ad7e7e0d207dea615495aeb3d57d0f7b3e9",
+    ("fuel_thrust_bound", 1): "210c33cb54395c1fdf544a7555f300a64278ba4fc179b54ad2b34b171e229a5f",
+    ("fuel_thrust_bound", 2): "22592783fb857afa8d58d82508be7ab16e18b887c33169599855b2e2dc1ab637",
+    ("fuel_thrust_bound", 3): "e5bcd190a5307f8576726c0ec6cbb162508925278d7eb79594ad44dfe0e19718",
+    ("mfma_fp64_formation", 1): "d99a8a888467e27ff67672f6dbcd28a8090c944777235b32eaa0c7b65a189e98",
+    ("mfma_fp64_formation", 2): "dae367351034dfc21e0bd0e3b2d62e61af812d2e1c08146a693e0057ac9c0401",
+    ("mfma_fp64_formation", 3): "da5e84bd5c08e0e89b34c8a4124581819318935eb2a9b5aafa2dd92adf6d21ef",
+    ("mfma_fp64_ltv", 1): "2af6f95d45f90306a216925e564c5534e39635afe6b37385988601105529a235",
+    ("mfma_fp64_ltv", 2): "6152f861d787fbd9c401723be46243bb9bf3f748e50f4bf60d4b0c8e6e3af6b3",
+    ("mfma_fp64_ltv", 3): "2d7b7342665890ae61a7e2cf703d296744aca6371e25c22369058fd319d3b299",
+    ("mfma_default_formation", 1): "feb61ed4a8784e8447e1df26ad54ef90381ebafd87fb5216dd8b6bbc4bec0e4d",
+    ("mfma_default_formation", 2): "1f56c1bbb20a0617671552a9e8fbae7fc110e3746368ff2b36bbf5f843284a81",
+    ("mfma_default_formation", 7): "417d6823c9ecdad299516f8e86c477ca0d20f3e854e0d6db76f48a63a4d69da4",
+    ("mixed", 1): "2cb39949c4a2ed8c05e37fa057c48c2f9d7f7345b5d64f5f340a235a103f183e",
+    ("mixed", 2): "cc1ba6becc6f9e7bd29b13e967fb079ca94da19c685a6c29bf74d451c31997b5",
+    ("mixed", 3): "73cd11b292fe0ba3e45e429ec606be7584f22ff9356a7d659a19c1d527d38a0b",
+    ("wide_one_lane", 1): "7164f98ed3128560f7d847337685bf63691656f95c8eabeb9d28a42a6e2cbacb",
+    ("wide_one_lane", 2): "b72e656eb9bf613503664da3d3b4f7d2c204a101fc5f9ba7a3a03fdab523fbed",
+    ("wide_one_lane", 3): "cd8292921c3f8240f7e64fe90aa6cb2207e3d9a535bc1e32b392192af4c2a2b4",
+    ("pinst_lane_per_qp", 1): "a6764bc413bd15aafa4bf7c998e5225dcf3383c9557a62e6bf7f1da05a48e727",
+    ("pinst_lane_per_qp", 2): "b49d4876cd20e48b42cda34f8bf3a3d330f35b2f8c6f33947dd6e5ecabc370ab",
+    ("pinst_lane_per_qp", 3): "936db52fdf2a5f0caa79053825f81e258fca660835b2c1521f49cb2287531dc7",
+    ("pinst_rows_over_lanes", 1): "5239b62bec35a64032272e62e74858eeb5bb8d70d503a3f92b83022e3507d21e",
+    ("pinst_rows_over_lanes", 2): "9eb8c1de7febcab5b14042ef15ecbe5677908c9d48e337072cc19f1b7d249161",
+    ("pinst_rows_over_lanes", 3): "868165e93c8b269b068bbf2fe6450284c31ed5a72dee033a677de83ad776ae75",
+    ("pinst_wide_one_segment", 1): "29e87dc7e2b7133cef601834cb00bd571d3c7580e4b4c66ee805b2d9ba5053ba",
+    ("pinst_wide_one_segment", 2): "7cdd3a51f374849019e3a907ac5c114032e4d9ad1550867a90876257642a1c97",
+    ("pinst_wide_one_segment", 3): "40a4c4a10d0cbd708cde5c132ce27f48a3ea444d57d99dff575742a3e6646c04",
+    ("pinst_wide_four_segments", 1): "88db4cf859c9503ae4474d5edb4c0de441f275fda2208e7d9685a1fbdbbb675b",
+    ("pinst_wide_four_segments", 2): "ff428057dff6896bcb610f43312a550f71faced116baa9c8a69d18ea55d5dd3d",
+    ("pinst_wide_four_segments", 3): "c3f591889a53915b0000b1f5027e1f0bc16f3020d503665881880335ad13244a",
+}
 
 
 def seeds(kind):
@@ -98,7 +264,9 @@ def options(kind):
 
 
 def classes_of(kind):
-    return tuple(c for c in CLASSES if c != "solve" or KINDS[kind].get("solve", True))
+    cfg = KINDS[kind]
+    probe = cfg.get("ext", False) and not cfg.get("consensus")                  # (a consensus handle refuses the probe)
+    return tuple(c for c in CLASSES if (c != "solve" or cfg.get("solve", True)) and (c != "probe" or probe))
 
 
 def legal_ops(kind):
@@ -114,7 +282,24 @@ def legal_ops(kind):
         "refused": ["refuse_set_state_nan", "refuse_update_N", "refuse_update_lohi"] + (["refuse_set_fuel_neg"] if cfg.get("fuel") else []),
         "readout": ["get", "residuals", "rho_per_qp"] + ([] if pinst else ["certificate"]) + (["get_device"] if dev else []),
         "solve": ["solve", "solve_pieces"],
+        "probe": [],
     }
+    if cfg.get("ext"):
+        soft, cons = cfg.get("soft", False), cfg.get("consensus", False)
+        if cons:
+            ops["refused"] += ["refuse_mpc", "refuse_probe"]
+        else:
+            ops["change"] += ["mpc_advance"] + (["mpc_advance_device"] if dev else [])
+            ops["probe"] = ["infeasibility"] + (["infeasibility_device"] if dev else [])
+            ops["refused"] += ["refuse_mpc_xmeas_and_dx", "refuse_mpc_nan_du"] + ([] if problem_has_q(kind) else ["refuse_mpc_qtail_without_q"])
+        if soft:
+            ops["change"] += ["set_soft"]
+            ops["readout"] += ["soft_report", "soft_report_device"]
+            ops["refused"] += ["refuse_set_soft_neg"] + (["refuse_set_fuel_on_soft_rows"] if cfg.get("fuel") else [])
+        if cons:
+            ops["readout"] += ["consensus", "consensus_device"]
+        if soft or cons:
+            ops["refused"] += ["refuse_profile_fused"]
     return {c: ops[c] for c in classes_of(kind)}
 
 
@@ -137,12 +322,18 @@ def sequence(kind, seed):
     walk = _circuit(rng, classes_of(kind))
     ops_of = legal_ops(kind)
     profile_modes = [0] if cfg.get("unfused") else [1, 2, 3] if cfg.get("alt") else [1]
-    cost = {"odd": 1, "even": 2, "resid": 1, "solve": SOLVE["max_iter"]}        # the least an op of the class applies
+    cost = {"odd": 1, "even": 2, "resid": 1, "solve": SOLVE["max_iter"], "probe": 1}        # the least an op of the class applies
     used, seq = 0, []
+    deck = {c: [] for c in ops_of}
     for i, cls in enumerate(walk):
         reserve = sum(cost.get(c, 0) for c in walk[i + 1:])
         room = MAX_ITERATIONS - used - reserve
-        name = ops_of[cls][int(rng.integers(len(ops_of[cls])))]
+        if cfg.get("ext"):                                                      # dealt from a shuffled deck of the class's ops
+            if not deck[cls]:
+                deck[cls] = [ops_of[cls][j] for j in rng.permutation(len(ops_of[cls]))]
+            name = deck[cls].pop()
+        else:
+            name = ops_of[cls][int(rng.integers(len(ops_of[cls])))]
         k = int(rng.integers(1, 10))                                            # lengths 1 .. 9: both parities
         if cls == "odd":
             k = k if k % 2 else k - 1 if k > 1 else 1
@@ -195,6 +386,20 @@ def sequence(kind, seed):
             args = (int(rng.integers(1, 8)),)
         elif name == "refuse_set_state_nan":
             args = (int(rng.integers(3)),)
+        elif name in ("mpc_advance", "mpc_advance_device"):
+            # (tail: 0 copy / 1 zero; x_meas in place of the plant; seeds of du, dx, the plant and q_tail, 0: absent)
+            sd = [int(rng.integers(1, 1 << 30)) if rng.integers(2) else 0 for _ in range(4)]
+            if name == "mpc_advance_device" and not sd[0]:
+                sd[0] = 1 + int(rng.integers(1 << 30))                          # (the device form of the wrapper needs one tensor)
+            if not problem_has_q(kind):
+                sd[3] = 0
+            args = (int(rng.integers(2)), int(rng.integers(3) == 0)) + tuple(sd)
+        elif name in ("infeasibility", "infeasibility_device"):
+            k = int(rng.integers(1, 7))
+            k = k if k <= room else 1
+            args = (k, bool(rng.integers(2)))
+        elif name == "set_soft":
+            args = (float(np.round(4.0 ** rng.uniform(-1.0, 1.0), 3)), int(rng.integers(1, 1 << 30)))
         if cls in cost:
             used += k
         seq.append((name, args))
@@ -210,7 +415,10 @@ def op_class(name, args):
         return "solve"
     if name.startswith("refuse_"):
         return "refused"
-    if name in ("get", "get_device", "residuals", "rho_per_qp", "certificate"):
+    if name in ("infeasibility", "infeasibility_device"):
+        return "probe"
+    if name in ("get", "get_device", "residuals", "rho_per_qp", "certificate", "soft_report", "soft_report_device", "consensus",
+                "consensus_device"):
         return "readout"
     if name == "step_z":
         return "resid" if args[0] else "odd"
@@ -239,7 +447,10 @@ def materialise(kind, name, args, model, snap):
     p = model.p
     if name in ("set_state", "set_state_device"):
         mask, scales = args[0], args[1:]
-        return {k: (snap[i] * scales[i] if mask >> i & 1 else None) for i, k in enumerate(("w", "z", "y"))}
+        out = {k: (snap[i] * scales[i] if mask >> i & 1 else None) for i, k in enumerate(("w", "z", "y"))}
+        if p.consensus is not None and out["z"] is not None:                    # control rows that differ within a group
+            out["z"] = out["z"] + 0.01 * np.random.default_rng(int(1000 * scales[1])).standard_normal(out["z"].shape)
+        return out
     if name == "refuse_set_state_nan":
         arrs = {k: None for k in ("w", "z", "y")}
         a = snap[args[0]].copy()
@@ -253,12 +464,12 @@ def materialise(kind, name, args, model, snap):
         q = p.q * (1.0 + 0.2 * rng.standard_normal(p.q.shape)) + 0.02 * rng.standard_normal(p.q.shape) if which & 2 else None
         return dict(x0=x0, q=q)
     if name == "update_problem":
-        return dict(problem=dataclasses.replace(problem(kind, args[0]), fuel=None))     # (the handle's weights stay in force)
+        return dict(problem=dataclasses.replace(problem(kind, args[0]), fuel=None, soft=None))     # (the handle's weights stay in force)
     if name == "refuse_update_N":
-        return dict(problem=dataclasses.replace(problem(kind, 2, dN=1), fuel=None))
+        return dict(problem=dataclasses.replace(problem(kind, 2, dN=1), fuel=None, soft=None))
     if name == "refuse_update_lohi":
-        new = dataclasses.replace(problem(kind, 2), fuel=None)
-        lo = np.array(new.lo, np.float64)
+        new = dataclasses.replace(problem(kind, 2), fuel=None, soft=None)
+        lo = np.array(new.lo, np.float64, order="C")                            # (reshape(-1) below must be a view)
         finite = np.flatnonzero(np.isfinite(np.asarray(new.hi).reshape(-1)))
         k = int(finite[len(finite) // 2])                                       # one bounded row in the middle of the box
         lo.reshape(-1)[k] = np.asarray(new.hi).reshape(-1)[k] + 1.0
@@ -271,6 +482,51 @@ def materialise(kind, name, args, model, snap):
         return dict(fuel=f)
     if name == "set_rho":
         return dict(rho=KINDS[kind]["opt"]["rho"] * args[0])
+    if name in ("mpc_advance", "mpc_advance_device"):
+        tail, meas, s_du, s_dx, s_plant, s_q = args
+        B, n, m = p.batch, p.n, p.m
+        gen = lambda s, shape, scale: scale * np.random.default_rng(s).standard_normal(shape) if s else None
+        out = dict(tail=("copy", "zero")[tail], du=gen(s_du, (B, m), 0.05), q_tail=gen(s_q, (B, p.nb), 0.1), plant=None, dx=None,
+                   x_meas=None)
+        if meas:
+            out["x_meas"] = p.x0 * (1.0 + gen(s_dx or 7, (B, n), 0.1)) + gen(s_plant or 11, (B, n), 0.02)
+        else:
+            out["dx"] = gen(s_dx, (B, n), 0.02)
+            if s_plant:
+                from admm_library_amd import mpc
+                A0, B0 = mpc.model_plant(p)
+                out["plant"] = (A0 * (1.0 + gen(s_plant, A0.shape, 0.05)), B0 * (1.0 + gen(s_plant + 1, B0.shape, 0.05)))
+        return out
+    if name in ("refuse_mpc_xmeas_and_dx", "refuse_mpc_nan_du", "refuse_mpc_qtail_without_q", "refuse_mpc"):
+        out = dict(tail="copy", du=None, q_tail=None, plant=None, dx=None, x_meas=None)
+        if name == "refuse_mpc_xmeas_and_dx":
+            out.update(x_meas=np.array(p.x0, np.float64), dx=np.zeros((p.batch, p.n)))
+        elif name == "refuse_mpc_nan_du":
+            du = np.zeros((p.batch, p.m))
+            du[p.batch - 1, p.m - 1] = np.nan
+            out.update(du=du)
+        elif name == "refuse_mpc_qtail_without_q":
+            out.update(q_tail=np.zeros((p.batch, p.nb)))
+        return out
+    if name in ("set_soft", "refuse_set_soft_neg"):
+        base = np.array(problem(kind).soft, np.float64)
+        if name == "refuse_set_soft_neg":
+            sw = np.array(p.soft, np.float64, order="C")
+            fin = np.flatnonzero(np.isfinite(sw).reshape(-1))
+            sw.reshape(-1)[fin[len(fin) // 2] if len(fin) else sw.size // 2] = -0.1
+            return dict(soft=sw)
+        if KINDS[kind].get("hard_or_soft"):                                     # every row hard, or the weights of set-up scaled
+            return dict(soft=base * args[0] if args[1] % 2 else np.full_like(base, np.inf))
+        rng = np.random.default_rng(args[1])
+        pick = rng.uniform(size=base.shape)
+        sw = base * args[0]                                                     # (+inf stays +inf)
+        sw[pick < 0.1] = np.inf                                                 # some rows turned hard,
+        sw[(pick > 0.9) & np.isfinite(base)] = 0.0                              # some ignored
+        return dict(soft=sw)
+    if name == "refuse_set_fuel_on_soft_rows":
+        f = np.array(p.fuel, np.float64)
+        f[SOFT_FUEL_STAGE] = 0.1
+        return dict(fuel=f)
     return {}
 
 
@@ -298,8 +554,22 @@ def apply_model(model, name, args, concrete):
         return model.update_instances(**concrete)
     if name in ("update_problem", "refuse_update_N", "refuse_update_lohi"):
         return model.update_problem(concrete["problem"])
-    if name in ("set_fuel", "refuse_set_fuel_neg"):
+    if name in ("set_fuel", "refuse_set_fuel_neg", "refuse_set_fuel_on_soft_rows"):
         return model.set_fuel(concrete["fuel"])
+    if name in ("set_soft", "refuse_set_soft_neg"):
+        return model.set_soft(concrete["soft"])
+    if name in ("mpc_advance", "mpc_advance_device") or name.startswith("refuse_mpc"):
+        return dict(mpc=model.mpc_advance(**concrete))
+    if name in ("infeasibility", "infeasibility_device"):
+        return dict(probe=model.infeasibility(args[0], PROBE_EPS, args[1]))
+    if name == "refuse_probe":
+        return dict(probe=model.infeasibility(3, PROBE_EPS, False))
+    if name == "refuse_profile_fused":
+        return model.profile(1, False, 1)
+    if name in ("soft_report", "soft_report_device"):
+        return dict(soft_report=model.soft_report())
+    if name in ("consensus", "consensus_device"):
+        return dict(consensus=model.consensus())
     if name == "certificate":
         return dict(cert=model.certificate())
     if name in ("get", "get_device"):

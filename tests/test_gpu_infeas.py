@@ -32,23 +32,7 @@ NAMES = ("sep", "drift", "defect", "infeasible", "nu")
 def _compare(p, y0, y1, span, eps, r):
     """All five outputs of probe `r` against the reference on (y0, y1); +inf must match as +inf."""
     ref = ir.probe(p, y0, y1, span, eps)
-    s_nu = np.maximum(1.0, np.abs(ref["nu"]).reshape(p.batch, -1).max(axis=1))
-    assert np.array_equal(np.isinf(r.sep), np.isinf(ref["sep"])) and np.all(r.sep[np.isinf(r.sep)] > 0)
-    assert np.array_equal(np.isinf(r.defect), np.isinf(ref["defect"]))
-    fs, fd = np.isfinite(ref["sep"]), np.isfinite(ref["defect"])
-    ratio_mu = np.where(ref["mu_max"] > 0, s_nu / np.where(ref["mu_max"] > 0, ref["mu_max"], 1.0), 1.0)
-    ratios = {"nu": (np.abs(r.nu - ref["nu"]).reshape(p.batch, -1).max(axis=1) / (TOL * s_nu)).max(),
-              "sep": (np.abs(r.sep - ref["sep"])[fs] / (TOL * np.maximum(1.0, ref["sep_abs"])[fs])).max(initial=0.0),
-              "drift": (np.abs(r.drift - ref["drift"]) / (TOL * np.maximum(1.0, ref["drift"]))).max(),
-              "defect": (np.abs(r.defect - ref["defect"])[fd] /
-                         (TOL * np.maximum(np.maximum(1.0, ref["defect"]), ratio_mu))[fd]).max(initial=0.0)}
-    print("error / tolerance:", {k: float(f"{v:.3g}") for k, v in ratios.items()}, "finite sep:", int(fs.sum()), "of", p.batch,
-          "flags:", int(ref["infeasible"].sum()))
-    for name, v in ratios.items():
-        assert v <= 1.0, (name, v)
-    # a flag may differ from the reference's only where sep sits within the comparison's tolerance of -eps
-    near = fs & (np.abs(ref["sep"] + eps) <= TOL * np.maximum(1.0, ref["sep_abs"]))
-    assert r.infeasible.dtype == np.int32 and np.array_equal(r.infeasible[~near], ref["infeasible"][~near])
+    ir.check(ref, r, eps, TOL)               # (the scales and the flag rule: shared with tests/test_gpu_sequences.py)
     return ref
 
 

@@ -10,21 +10,33 @@ kind, the file header of test_gpu_mfma.py); the certificate as in test_gpu_cert.
 host tests keep every stopping-rule and adaptive-rule comparison of these sequences a relative 1e-6 away from its threshold, so
 rounding on the GPU cannot flip one.  A set_rho / update_problem refused with ADMM_ERR_NUMERIC (conditioning bound) and a
 fall-back to the plain kernels with a warning are legal outcomes; the iterates must match either way.
+
+The kinds with ext=True add the receding-horizon step (its outputs u and x_next are compared like a read-out, and the model goes on
+from its own x+), the infeasibility probe (the scales and the flag rule of tests/test_gpu_infeas.py, _infeas_ref.check; flags equal and
+sep finite on the same QPs: the host tests keep every sep away from -eps and every open row away from eps |mu|_inf; defect is left out
+on the QPs where the model finds mu or lambda to be a rounding error of a stationary y -- none in the committed sequences but for the
+rows of the soft kinds that stay violated, y = s / rho there: stationary_rows in tests/_op_sequences.py), the consensus read-out and the soft report.  The bounds of the soft report follow from the iterate tolerance tau = 1e-10 max(1, |z|_inf) of the
+model's z: max_violation is a difference of z and a bound (tau), the penalty a sum of weight times violation (tau x the sum of the
+finite weights), and n_violated is exact -- the host tests keep every finite-weight row of every committed report clearly outside its
+box, clearly inside, or exactly on a bound with |y| away from s / rho.
 """
 import ctypes as C
 
 import numpy as np
 import pytest
+import torch  # noqa: F401  (before the library is loaded: one HIP runtime in the process, also when this file runs alone)
 
 import admm_library_amd as pkg
 from admm_library_amd import _abi
 from admm_library_amd.solver import AdmmError
 
+import _infeas_ref as ir
 import _op_sequences as ops
 from _handle_model import NUMERIC, Refused
 
 pytestmark = pytest.mark.gpu
 _LEAN = {}          # seed -> lean_iterations() of the lean kind's sequence
+_WORST = {}         # compared quantity -> worst error / bound over the tests run so far (printed by every test)
 
 
 def _tensor(a):
@@ -32,9 +44,78 @@ def _tensor(a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
 
 
+def _rc(lib, rc):
+    if rc:
+        raise AdmmError(rc, lib.admm_last_error().decode())
+
+
+def _mpc_args(c, device=False):
+    per_qp = ("du", "dx", "x_meas", "q_tail")
+    return {k: (_tensor(v) if device and k in per_qp else v) for k, v in c.items()}
+
+
+def _probe_device(s, span, eps, costates):
+    """admm_probe_infeasibility_device on a handle set up from host arrays -> an Infeasibility of NumPy arrays."""
+    import torch
+    from admm_library_amd.solver import Infeasibility, _stream, _tptr
+    p, dev = s.problem, "cuda:0"
+    outs = [torch.empty(s.batch, dtype=torch.float64, device=dev) for _ in range(3)]
+    flag = torch.empty(s.batch, dtype=torch.int32, device=dev)
+    nu = torch.empty((s.batch, p.N, p.n), dtype=torch.float64, device=dev) if costates else None
+    _rc(s._lib, s._lib.admm_probe_infeasibility_device(s._h, int(span), float(eps), *[_tptr(o) for o in outs],
+                                                       C.cast(C.c_void_p(flag.data_ptr()), _abi.c_int32_p), _tptr(nu), _stream(dev)))
+    torch.cuda.synchronize()
+    return Infeasibility(*[o.cpu().numpy() for o in outs], flag.cpu().numpy(), None if nu is None else nu.cpu().numpy())
+
+
 def _apply_gpu(s, name, args, c):
     """One op on the Solver; returns what a read-out op reads.  Raises AdmmError (ValueError from the wrapper's own checks)."""
     lib = s._lib
+    if name == "mpc_advance" or name.startswith("refuse_mpc"):
+        u, x = s.mpc_advance(**_mpc_args(c))
+        return dict(mpc=dict(u=u, x_next=x))
+    if name == "mpc_advance_device":
+        import torch
+        u, x = s.mpc_advance(**_mpc_args(c, device=True))
+        assert u.is_cuda and x.is_cuda                        # (the device form ran)
+        torch.cuda.synchronize()
+        return dict(mpc=dict(u=u.cpu().numpy(), x_next=x.cpu().numpy()))
+    if name == "infeasibility":
+        return dict(probe=s.infeasibility(args[0], ops.PROBE_EPS, args[1]))
+    if name == "infeasibility_device":
+        return dict(probe=_probe_device(s, args[0], ops.PROBE_EPS, args[1]))
+    if name == "refuse_probe":
+        return dict(probe=s.infeasibility(3, ops.PROBE_EPS, False))
+    if name == "refuse_profile_fused":
+        return s.profile(1, residuals=False, fused=True) and None
+    if name == "set_soft":
+        return s.set_soft(c["soft"])
+    if name == "refuse_set_soft_neg":         # Problem.validate would stop it in the wrapper: hand the weights to the library itself
+        return _rc(lib, lib.admm_set_soft(s._h, _abi.dptr(np.ascontiguousarray(c["soft"], np.float64))))
+    if name == "refuse_set_fuel_on_soft_rows":          # (likewise)
+        return _rc(lib, lib.admm_set_fuel(s._h, _abi.dptr(np.ascontiguousarray(c["fuel"], np.float64))))
+    if name == "refuse_update_N" and getattr(s.problem, "soft", None) is not None:      # (likewise: the wrapper re-attaches the weights)
+        cp, keep = _abi.marshal_problem(c["problem"], s._row_major)
+        return _rc(lib, lib.admm_update_problem(s._h, C.byref(cp)))
+    if name == "soft_report":
+        r = s.soft_report()
+        return dict(soft_report=dict(penalty=r.penalty, max_violation=r.max_violation, n_violated=r.n_violated))
+    if name == "soft_report_device":
+        import torch
+        r = s.soft_report(device=True)
+        torch.cuda.synchronize()
+        return dict(soft_report=dict(penalty=r.penalty.cpu().numpy(), max_violation=r.max_violation.cpu().numpy(),
+                                     n_violated=r.n_violated.cpu().numpy()))
+    if name == "consensus":
+        return dict(consensus=s.consensus())
+    if name == "consensus_device":
+        import torch
+        from admm_library_amd.solver import _stream, _tptr
+        p = s.problem
+        out = torch.empty((s.batch // int(p.consensus), p.N, p.m), dtype=torch.float64, device="cuda:0")
+        _rc(lib, lib.admm_get_consensus_device(s._h, _tptr(out), _stream("cuda:0")))
+        torch.cuda.synchronize()
+        return dict(consensus=out.cpu().numpy())
     if name == "iterate":
         return s.iterate(args[0])
     if name == "run":
@@ -105,7 +186,13 @@ def _close(what, got, ref, tol):
     err = np.abs(np.asarray(got) - np.asarray(ref)).max()
     bound = tol * max(1.0, np.abs(ref).max())
     print(f"    {what}: |gpu - model| = {err:.3e} (bound {bound:.1e})")
+    _worst(what.split(".")[0] if what.startswith("residuals") else what, err / bound, tol)
     assert err <= bound, (what, err, bound)
+
+
+def _worst(what, ratio, tol):
+    key = what if tol == 1e-10 else f"{what} (tolerance {tol:g})"
+    _WORST[key] = max(_WORST.get(key, 0.0), float(ratio))
 
 
 def _compare(got, ref, model, tol):
@@ -134,7 +221,31 @@ def _compare(got, ref, model, tol):
         if g.nu is not None:
             ratios["nu"] = (np.abs(g.nu - r["nu"]).reshape(b, -1).max(axis=1) / (tol * s_nu)).max()
         print("    certificate, error / tolerance:", {k: float(f"{v:.3g}") for k, v in ratios.items()})
+        for k, v in ratios.items():
+            _worst("certificate." + k, v, tol)
         assert all(v <= 1.0 for v in ratios.values()), ratios
+    if "mpc" in ref:
+        _close("u", got["mpc"]["u"], ref["mpc"]["u"], tol)
+        _close("x_next", got["mpc"]["x_next"], ref["mpc"]["x_next"], tol)
+    if "consensus" in ref:
+        assert got["consensus"].shape == ref["consensus"].shape
+        _close("consensus", got["consensus"], ref["consensus"], tol)
+    if "probe" in ref:
+        g, r = got["probe"], ref["probe"]
+        assert (g.nu is not None) == r["costates"]
+        for k, v in ir.check(r, g, r["eps"], tol, flags_exact=True, defect_on=r["defect_clear"]).items():
+            _worst("probe." + k, v, tol)
+    if "soft_report" in ref:
+        g, r = got["soft_report"], ref["soft_report"]
+        tau = tol * max(1.0, np.abs(model.z).max())
+        e_pen = np.abs(g["penalty"] - r["penalty"]).max()
+        ratios = {"max_violation": np.abs(g["max_violation"] - r["max_violation"]).max() / tau,
+                  "penalty": e_pen / (tau * r["weight_sum"]) if r["weight_sum"] > 0 else (0.0 if e_pen == 0 else np.inf)}
+        print("    soft report, error / bound:", {k: float(f"{v:.3g}") for k, v in ratios.items()}, "violated rows:", int(r["n_violated"].sum()))
+        for k, v in ratios.items():
+            _worst("soft_report." + k, v, tol)
+        assert all(v <= 1.0 for v in ratios.values()), ratios
+        assert g["n_violated"].dtype == np.int32 and np.array_equal(g["n_violated"], r["n_violated"]), (g["n_violated"], r["n_violated"])
 
 
 def _run(kind, seed, monkeypatch, compare=True):
@@ -193,6 +304,7 @@ def _run(kind, seed, monkeypatch, compare=True):
 def test_sequence_matches_the_host_model(gpu, kind, seed, monkeypatch):
     lean, model = _run(kind, seed, monkeypatch)
     print(f"{kind} seed {seed}: {model.iterations} iterations, lean {lean}")
+    print("worst error / bound so far:", {k: float(f"{v:.3g}") for k, v in sorted(_WORST.items())})
     if ops.KINDS[kind].get("lean"):
         _LEAN[seed] = lean
 
