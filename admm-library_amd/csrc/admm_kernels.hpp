@@ -1282,243 +1282,10 @@ static __global__ __launch_bounds__(256) void scale_kernel(double* __restrict__ 
   }
 }
 
-// One row of two adjacent QPs, 16-byte pairs: (z, y) from v by the box, or -- the control rows of a thrust stage -- z = c v
-// without the clip (their box is (-inf, inf): admm_prox.hpp).
-struct ZY2 { double2 z, y; };
-__device__ __forceinline__ ZY2 zy2_box(double2 v, double lo, double hi) {
-  const double2 z = make_double2(clip(v.x, lo, hi), clip(v.y, lo, hi));
-  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
-}
-// ... with the bounds of row r still in memory: each read between the two halves of the clip, as the read-out kernels always did
-template <class P>
-__device__ __forceinline__ ZY2 zy2_box(double2 v, P lo, P hi, int r) {
-  const double2 z = make_double2(clip_hi(clip_lo(v.x, lo[r]), hi[r]), clip_hi(clip_lo(v.y, lo[r]), hi[r]));
-  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
-}
-__device__ __forceinline__ ZY2 zy2_scaled(double2 v, double2 c) {
-  const double2 z = make_double2(v.x * c.x, v.y * c.y);
-  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
-}
-__device__ __forceinline__ void zy2_store(const ZY2& p, double* z, double* y, size_t o = 0) {
-  *reinterpret_cast<double2*>(z + o) = p.z;
-  *reinterpret_cast<double2*>(y + o) = p.y;
-}
-
-// v+ = w^ + y of one row of two adjacent QPs, from the loaded (z, y)
-template <bool RELAX>
-__device__ __forceinline__ double2 v_plus2(double alpha, double2 w, double2 z, double2 y) {
-  return make_double2(relaxed<RELAX>(alpha, w.x, z.x) + y.x, relaxed<RELAX>(alpha, w.y, z.y) + y.y);
-}
-
-// One row of the unfused z-update for two adjacent QPs, in place: (z, y) <- z-update of (w, z, y); acc: the sums of either QP
-template <bool RESID, bool RELAX>
-__device__ __forceinline__ void zdual_row(double2 wv, double2 zv, double2 yv, bool scaled, double2 c, double lo, double hi,
-                                          double alpha, double* z, double* y, ResidSums (&acc)[2]) {
-  const double2 v = v_plus2<RELAX>(alpha, wv, zv, yv);
-  const ZY2 p = scaled ? zy2_scaled(v, c) : zy2_box(v, lo, hi);
-  zy2_store(p, z, y);
-  if (RESID) {
-    acc[0].add(wv.x, p.z.x, zv.x, p.y.x);
-    acc[1].add(wv.y, p.z.y, zv.y, p.y.y);
-  }
-}
-
-__device__ __forceinline__ void store_sums2(double* part, size_t P, const ResidSums (&acc)[2]) {
-  *reinterpret_cast<double2*>(part + 0 * P) = make_double2(acc[0].r, acc[1].r);
-  *reinterpret_cast<double2*>(part + 1 * P) = make_double2(acc[0].s, acc[1].s);
-  *reinterpret_cast<double2*>(part + 2 * P) = make_double2(acc[0].w, acc[1].w);
-  *reinterpret_cast<double2*>(part + 3 * P) = make_double2(acc[0].z, acc[1].z);
-  *reinterpret_cast<double2*>(part + 4 * P) = make_double2(acc[0].y, acc[1].y);
-}
-
-// v -> (z, y): z = clip(v), y = v - z.  Read-out / mode switches only.  One lane =
-// two adjacent QPs, blockIdx.y = row chunk (same geometry as zdual_kernel).
-static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_kernel(
-    const double* __restrict__ v, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_, int L, int zrows, int pitch) {
-  const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
-  if (col >= pitch) return;
-  const int r_begin = blockIdx.y * zrows;
-  const int r_end = (r_begin + zrows < L) ? r_begin + zrows : L;
-  cdouble_p lo = as_const(lo_);
-  cdouble_p hi = as_const(hi_);
-  constexpr int U = 4;                 // rows in flight per lane (a row-at-a-time loop ran at 3.5 TB/s: 250 us at configs[2])
-  int r = r_begin;
-  for (; r + U <= r_end; r += U) {
-    double2 vv[U];
-#pragma unroll
-    for (int i = 0; i < U; ++i) vv[i] = *reinterpret_cast<const double2*>(v + (size_t)(r + i) * pitch + col);
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const size_t o = (size_t)(r + i) * pitch + col;
-      zy2_store(zy2_box(vv[i], lo, hi, r + i), z, y, o);
-    }
-  }
-  for (; r < r_end; ++r) {
-    const size_t o = (size_t)r * pitch + col;
-    const double2 vv = *reinterpret_cast<const double2*>(v + o);
-    zy2_store(zy2_box(vv, lo, hi, r), z, y, o);
-  }
-}
+#include "admm_zdual.hpp"   // the standalone z-update and read-out kernels: zdual_*, v_to_zy_*
 
 #undef ADMM_MV
 #undef ADMM_LD
-
-// ---------------------------------------------------------------------------
-// Fused z-update + dual ascent + residual partial sums -- the HBM-bound kernel
-// the project is graded on.  One lane = two adjacent QPs (16-B accesses), a
-// workgroup = 512 columns x `zrows` rows (blockIdx.y = row chunk).
-//     wh = alpha w + (1 - alpha) z        (RELAX only)
-//     v  = wh + y;  z+ = min(max(v, lo), hi);  y+ = v - z+       (in place)
-//     RESID: per-QP partial sums over the chunk's rows of
-//            (w - z+)^2, (z+ - z)^2, w^2, z+^2, y+^2  -> part[chunk][5][pitch]
-// The row index is wave-uniform, so lo/hi are scalar loads and the per-QP sums
-// need no cross-lane step at all: each lane owns its QPs' accumulators.
-// Algorithmic HBM bytes per stacked element: RESID/RELAX: 3 reads + 2 writes =
-// 40 B; plain: 2 reads + 2 writes = 32 B.
-// ---------------------------------------------------------------------------
-template <bool RESID, bool RELAX>
-__global__ __launch_bounds__(Z_THREADS) void zdual_kernel(
-    const double* __restrict__ w, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_,
-    double* __restrict__ part, double alpha, int L, int zrows, int pitch) {
-  const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
-  if (col >= pitch) return;
-  const int chunk = blockIdx.y;
-  const int r_begin = chunk * zrows;
-  const int r_end = (r_begin + zrows < L) ? r_begin + zrows : L;
-  const size_t P = (size_t)pitch;
-  cdouble_p lo = as_const(lo_);
-  cdouble_p hi = as_const(hi_);
-  ResidSums acc[2];
-#ifndef ADMM_Z_UNROLL
-#define ADMM_Z_UNROLL 4
-#endif
-  constexpr int U = ADMM_Z_UNROLL;
-  int r = r_begin;
-  for (; r + U <= r_end; r += U) {
-    double2 wv[U], yv[U], zv[U];
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const size_t o = (size_t)(r + i) * P + col;
-#ifdef ADMM_Z_NT          // A/B: non-temporal hint on the once-read operand w
-      wv[i] = __builtin_nontemporal_load(reinterpret_cast<const double2*>(w + o));
-#else
-      wv[i] = *reinterpret_cast<const double2*>(w + o);
-#endif
-      yv[i] = *reinterpret_cast<const double2*>(y + o);
-      zv[i] = make_double2(0.0, 0.0);
-      if (RESID || RELAX) zv[i] = *reinterpret_cast<const double2*>(z + o);
-    }
-#pragma unroll
-    for (int i = 0; i < U; ++i) {
-      const size_t o = (size_t)(r + i) * P + col;
-      zdual_row<RESID, RELAX>(wv[i], zv[i], yv[i], false, wv[i], lo[r + i], hi[r + i], alpha, z + o, y + o, acc);
-    }
-  }
-  for (; r < r_end; ++r) {
-    const size_t o = (size_t)r * P + col;
-    const double2 wv = *reinterpret_cast<const double2*>(w + o);
-    const double2 yv = *reinterpret_cast<const double2*>(y + o);
-    double2 zv = {0, 0};
-    if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-    zdual_row<RESID, RELAX>(wv, zv, yv, false, wv, lo[r], hi[r], alpha, z + o, y + o, acc);
-  }
-  if (RESID) store_sums2(part + (size_t)chunk * 5 * P + col, P, acc);
-}
-
-// ---------------------------------------------------------------------------
-// Block-structured forms of zdual_kernel / v_to_zy_kernel for problems with a thrust-magnitude
-// bound: the projection of a stage's control rows needs their joint norm, so a
-// chunk is a whole number of blocks (zrows % nb == 0) and each block is visited twice -- once
-// over its m control rows for ||v_u|| (the re-read hits L1/L2), once to apply.  Unfused path and
-// read-out only; the fused xfz / xb kernels do the same work on register-resident blocks.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double2 soc_scale2(double2 ss, double ub, double kap) {
-  return make_double2(soc_factor(sqrt(ss.x), ub, kap), soc_factor(sqrt(ss.y), ub, kap));
-}
-
-template <bool RESID, bool RELAX>
-__global__ __launch_bounds__(Z_THREADS) void zdual_soc_kernel(
-    const double* __restrict__ w, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_, const double* __restrict__ kap_,
-    double* __restrict__ part, double alpha, int L, int zrows, int pitch, int nb, int m) {
-  const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
-  if (col >= pitch) return;
-  const int chunk = blockIdx.y;
-  const int r_begin = chunk * zrows;
-  const int r_end = (r_begin + zrows < L) ? r_begin + zrows : L;
-  const size_t P = (size_t)pitch;
-  cdouble_p lo = as_const(lo_);
-  cdouble_p hi = as_const(hi_);
-  cdouble_p ubv = as_const(ub_);
-  cdouble_p kapv = as_const(kap_);
-  ResidSums acc[2];
-  for (int rb = r_begin; rb < r_end; rb += nb) {
-    const double ub = ubv[rb / nb], kap = kapv[rb / nb];
-    const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their box)
-    double2 cs = {1.0, 1.0};
-    if (soc) {
-      double2 ss = {0.0, 0.0};
-      for (int j = 0; j < m; ++j) {
-        const size_t o = (size_t)(rb + j) * P + col;
-        const double2 wv = *reinterpret_cast<const double2*>(w + o);
-        const double2 yv = *reinterpret_cast<const double2*>(y + o);
-        double2 zv = {0, 0};
-        if (RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-        const double2 vn = v_plus2<RELAX>(alpha, wv, zv, yv);
-        ss.x = fma(vn.x, vn.x, ss.x);
-        ss.y = fma(vn.y, vn.y, ss.y);
-      }
-      cs = soc_scale2(ss, ub, kap);
-    }
-    for (int r = 0; r < nb; ++r) {
-      const int row = rb + r;
-      const size_t o = (size_t)row * P + col;
-      const double2 wv = *reinterpret_cast<const double2*>(w + o);
-      const double2 yv = *reinterpret_cast<const double2*>(y + o);
-      double2 zv = {0, 0};
-      if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-      zdual_row<RESID, RELAX>(wv, zv, yv, soc && r < m, cs, lo[row], hi[row], alpha, z + o, y + o, acc);
-    }
-  }
-  if (RESID) store_sums2(part + (size_t)chunk * 5 * P + col, P, acc);
-}
-
-static __global__ __launch_bounds__(Z_THREADS) void v_to_zy_soc_kernel(
-    const double* __restrict__ v, double* __restrict__ z, double* __restrict__ y,
-    const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ ub_, const double* __restrict__ kap_,
-    int L, int zrows, int pitch, int nb, int m) {
-  const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
-  if (col >= pitch) return;
-  const int r_begin = blockIdx.y * zrows;
-  const int r_end = (r_begin + zrows < L) ? r_begin + zrows : L;
-  cdouble_p lo = as_const(lo_);
-  cdouble_p hi = as_const(hi_);
-  cdouble_p ubv = as_const(ub_);
-  cdouble_p kapv = as_const(kap_);
-  for (int rb = r_begin; rb < r_end; rb += nb) {
-    const double ub = ubv[rb / nb], kap = kapv[rb / nb];
-    const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their box)
-    double2 cs = {1.0, 1.0};
-    if (soc) {
-      double2 ss = {0.0, 0.0};
-      for (int j = 0; j < m; ++j) {
-        const double2 vv = *reinterpret_cast<const double2*>(v + (size_t)(rb + j) * pitch + col);
-        ss.x = fma(vv.x, vv.x, ss.x);
-        ss.y = fma(vv.y, vv.y, ss.y);
-      }
-      cs = soc_scale2(ss, ub, kap);
-    }
-    for (int r = 0; r < nb; ++r) {
-      const int row = rb + r;
-      const size_t o = (size_t)row * pitch + col;
-      const double2 vv = *reinterpret_cast<const double2*>(v + o);
-      if (soc && r < m) zy2_store(zy2_scaled(vv, cs), z, y, o);
-      else zy2_store(zy2_box(vv, lo, hi, row), z, y, o);
-    }
-  }
-}
 
 // Standalone residual finalise (see finalize_body above).
 static __global__ __launch_bounds__(FIN_COLS * FIN_GROUPS) void resid_finalize_kernel(FinArgs fa, int pitch) {

@@ -21,8 +21,9 @@
 // setup), so  z_u = clip(c v_u, lo, hi)  is the ball projection in the one case and the box projection in the other, bit
 // for bit.  (The first version branched on the wave-uniform `ub < inf`: every row of the block then stayed live across the
 // branch and the two sqrt / division sequences inside it, and the fused kernels went to scratch at most shapes.)
-// A kernel that reaches the same bits by another sequence keeps it: zdual_soc_kernel / v_to_zy_soc_kernel branch on the
-// wave-uniform `soc && r < m` and take z_u = c v_u without the clip -- clip(x, -inf, inf) = x for every non-NaN x.
+// A kernel that reaches the same bits by another sequence keeps it: the block walk of the standalone kernels (z_walk_blocks,
+// admm_zdual.hpp: zdual_soc_kernel, v_to_zy_soc_kernel, zdual_soft_kernel<.., true>) branches on the wave-uniform
+// `soc && r < m` and takes z_u = c v_u without the clip -- clip(x, -inf, inf) = x for every non-NaN x.
 #pragma once
 #include <cmath>
 

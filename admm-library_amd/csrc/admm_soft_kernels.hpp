@@ -2,17 +2,15 @@
 // Row i of the stacked vector carries a weight s_i >= 0 (+inf: the hard box) and the cost gains  s_i dist(w_i, [lo_i, hi_i]);
 // with kap_i = s_i / rho the z-update of the row is soft_clip of admm_prox.hpp:
 //     c = clip(v, lo, hi),  e = v - c,  z = |e| <= kap ? c : (e > 0 ? v - kap : v + kap),  y = v - z
-// and everything else -- the relaxation, v+ = w^ + y, the five residual sums and their order -- is that of zdual_kernel /
-// zdual_soc_kernel (admm_kernels.hpp), whose helpers are used as they are.  With every kap = +inf the select always takes c: the
-// bits of those kernels, residual partials included, given the same rows per chunk.
+// That prox (SoftBoxProx) is all this file adds to the z-update: the walk over the rows, the relaxation, v+ = w^ + y, the five
+// residual sums and their order are those of zdual_kernel / zdual_soc_kernel (admm_zdual.hpp), the same functions.  With every
+// kap = +inf the select always takes c: the bits of those kernels, residual partials included, given the same rows per chunk.
 //
 // zdual_soft_kernel<RESID, RELAX, SOC>
-//   SOC = false: zdual_kernel's geometry.  One lane = two adjacent QPs (16-byte accesses), four rows in flight, blockIdx.y = row
-//       chunk; lo, hi and kap of a row are wave-uniform and read through the constant address space (scalar loads).  In place:
-//       40 B per stacked element with RESID or RELAX, 32 B without; the kap array is L doubles for the whole batch.
-//   SOC = true: zdual_soc_kernel's, a chunk being a whole number of blocks.  The control rows of a stage with a finite thrust
-//       bound or a fuel weight take soc_factor (their weights are +inf: checked at set-up); every other row takes soft_clip.
-// Pad columns (batch .. pitch - 1) are computed like any other, as in those kernels: their state is zero and stays finite.
+//   SOC = false: z_walk_rows, as zdual_kernel.  In place: 40 B per stacked element with RESID or RELAX, 32 B without; the kap
+//       array is L doubles for the whole batch.
+//   SOC = true: z_walk_blocks, as zdual_soc_kernel.  The control rows of a stage with a finite thrust bound or a fuel weight
+//       take soc_factor (their weights are +inf: checked at set-up); every other row takes soft_clip.
 //
 // soft_report_kernel: one lane = one QP walks its column of z (a wave reads 64 adjacent columns: coalesced), four rows in flight.
 // Over the rows with a finite weight, in row order:  penalty = fma(s_i, d_i, penalty),  d_i = max(lo_i - z_i, 0, z_i - hi_i);
@@ -24,24 +22,15 @@
 
 namespace admm {
 
-// One row of two adjacent QPs by the soft box
-__device__ __forceinline__ ZY2 zy2_soft(double2 v, double lo, double hi, double kap) {
-  const double2 z = make_double2(soft_clip(v.x, lo, hi, kap), soft_clip(v.y, lo, hi, kap));
-  return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
-}
-
-// zdual_row with the soft box in place of the clip
-template <bool RESID, bool RELAX>
-__device__ __forceinline__ void zdual_soft_row(double2 wv, double2 zv, double2 yv, bool scaled, double2 c, double lo, double hi,
-                                               double kap, double alpha, double* z, double* y, ResidSums (&acc)[2]) {
-  const double2 v = v_plus2<RELAX>(alpha, wv, zv, yv);
-  const ZY2 p = scaled ? zy2_scaled(v, c) : zy2_soft(v, lo, hi, kap);
-  zy2_store(p, z, y);
-  if (RESID) {
-    acc[0].add(wv.x, p.z.x, zv.x, p.y.x);
-    acc[1].add(wv.y, p.z.y, zv.y, p.y.y);
+// The soft box as a prox of the z walks: lo, hi and kap of a row are wave-uniform (scalar loads)
+struct SoftBoxProx {
+  cdouble_p lo, hi, kap;
+  __device__ __forceinline__ ZY2 operator()(double2 v, int r) const {
+    const double l = lo[r], h = hi[r], k = kap[r];
+    const double2 z = make_double2(soft_clip(v.x, l, h, k), soft_clip(v.y, l, h, k));
+    return ZY2{z, make_double2(v.x - z.x, v.y - z.y)};
   }
-}
+};
 
 template <bool RESID, bool RELAX, bool SOC>
 __global__ __launch_bounds__(Z_THREADS) void zdual_soft_kernel(
@@ -49,76 +38,10 @@ __global__ __launch_bounds__(Z_THREADS) void zdual_soft_kernel(
     const double* __restrict__ lo_, const double* __restrict__ hi_, const double* __restrict__ skap_,
     const double* __restrict__ ub_, const double* __restrict__ kap_,
     double* __restrict__ part, double alpha, int L, int zrows, int pitch, int nb, int m) {
-  const int col = (blockIdx.x * Z_THREADS + threadIdx.x) * 2;
-  if (col >= pitch) return;
-  const int chunk = blockIdx.y;
-  const int r_begin = chunk * zrows;
-  const int r_end = (r_begin + zrows < L) ? r_begin + zrows : L;
-  const size_t P = (size_t)pitch;
-  cdouble_p lo = as_const(lo_);
-  cdouble_p hi = as_const(hi_);
-  cdouble_p sk = as_const(skap_);
-  ResidSums acc[2];
-  if constexpr (!SOC) {
-    constexpr int U = 4;
-    int r = r_begin;
-    for (; r + U <= r_end; r += U) {
-      double2 wv[U], yv[U], zv[U];
-#pragma unroll
-      for (int i = 0; i < U; ++i) {
-        const size_t o = (size_t)(r + i) * P + col;
-        wv[i] = *reinterpret_cast<const double2*>(w + o);
-        yv[i] = *reinterpret_cast<const double2*>(y + o);
-        zv[i] = make_double2(0.0, 0.0);
-        if (RESID || RELAX) zv[i] = *reinterpret_cast<const double2*>(z + o);
-      }
-#pragma unroll
-      for (int i = 0; i < U; ++i) {
-        const size_t o = (size_t)(r + i) * P + col;
-        zdual_soft_row<RESID, RELAX>(wv[i], zv[i], yv[i], false, wv[i], lo[r + i], hi[r + i], sk[r + i], alpha, z + o, y + o, acc);
-      }
-    }
-    for (; r < r_end; ++r) {
-      const size_t o = (size_t)r * P + col;
-      const double2 wv = *reinterpret_cast<const double2*>(w + o);
-      const double2 yv = *reinterpret_cast<const double2*>(y + o);
-      double2 zv = {0, 0};
-      if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-      zdual_soft_row<RESID, RELAX>(wv, zv, yv, false, wv, lo[r], hi[r], sk[r], alpha, z + o, y + o, acc);
-    }
-  } else {
-    cdouble_p ubv = as_const(ub_);
-    cdouble_p kapv = as_const(kap_);
-    for (int rb = r_begin; rb < r_end; rb += nb) {
-      const double ub = ubv[rb / nb], kap = kapv[rb / nb];
-      const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their soft box)
-      double2 cs = {1.0, 1.0};
-      if (soc) {
-        double2 ss = {0.0, 0.0};
-        for (int j = 0; j < m; ++j) {
-          const size_t o = (size_t)(rb + j) * P + col;
-          const double2 wv = *reinterpret_cast<const double2*>(w + o);
-          const double2 yv = *reinterpret_cast<const double2*>(y + o);
-          double2 zv = {0, 0};
-          if (RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-          const double2 vn = v_plus2<RELAX>(alpha, wv, zv, yv);
-          ss.x = fma(vn.x, vn.x, ss.x);
-          ss.y = fma(vn.y, vn.y, ss.y);
-        }
-        cs = soc_scale2(ss, ub, kap);
-      }
-      for (int r = 0; r < nb; ++r) {
-        const int row = rb + r;
-        const size_t o = (size_t)row * P + col;
-        const double2 wv = *reinterpret_cast<const double2*>(w + o);
-        const double2 yv = *reinterpret_cast<const double2*>(y + o);
-        double2 zv = {0, 0};
-        if (RESID || RELAX) zv = *reinterpret_cast<const double2*>(z + o);
-        zdual_soft_row<RESID, RELAX>(wv, zv, yv, soc && r < m, cs, lo[row], hi[row], sk[row], alpha, z + o, y + o, acc);
-      }
-    }
-  }
-  if (RESID) store_sums2(part + (size_t)chunk * 5 * P + col, P, acc);
+  const StateSource<RESID, RELAX> src{w, z, y, alpha};
+  const SoftBoxProx prox{as_const(lo_), as_const(hi_), as_const(skap_)};
+  if constexpr (SOC) z_walk_blocks(src, prox, z, y, ub_, kap_, part, L, zrows, pitch, nb, m);
+  else z_walk_rows(src, prox, z, y, part, L, zrows, pitch);
 }
 
 constexpr int SOFT_REPORT_THREADS = 64;
