@@ -12,12 +12,13 @@ import threading
 
 import numpy as np
 import pytest
-import torch
+import torch  # noqa: F401  (before libadmm_hip.so is loaded: the exchange runs torch and the library on ONE HIP runtime, torch's)
 
 import admm_library_amd as pkg
 import oracle_c as oc
 from admm_library_amd import _abi
 from admm_library_amd.solver import Solver
+from _timeshard import ThreadExchange as _ThreadExchange
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
@@ -37,43 +38,6 @@ def test_one_rank_time_shard_is_the_ordinary_handle(gpu):
         s0.run(25, residual_every=5)
         for a, b in zip(s.get() + s.residuals(), s0.get() + s0.residuals()):
             np.testing.assert_array_equal(a, b)
-
-
-class _ThreadExchange:
-    """Two 'ranks' in one process: each handle's exchange publishes its buffer, waits for the peer, copies the peer's slice."""
-
-    def __init__(self, world):
-        self.world = world
-        self.barrier = threading.Barrier(world)
-        self.slots = [None] * world
-        self.calls = 0
-
-    def make(self, rank):
-        def fn(ctx, stream, op, buf, count):
-            try:
-                ext = torch.cuda.ExternalStream(stream, device="cuda:0")
-                ext.synchronize()                                     # my slice is complete
-                self.slots[rank] = (buf, count)
-                self.barrier.wait(timeout=60)
-                full = pkg.device_tensor(buf, count * self.world, "cuda:0")
-                with torch.cuda.stream(ext):
-                    for r in range(self.world):
-                        if r != rank:
-                            pb, pc = self.slots[r]
-                            assert pc == count
-                            peer = pkg.device_tensor(pb, count * self.world, "cuda:0")
-                            full[r * count:(r + 1) * count].copy_(peer[r * count:(r + 1) * count])
-                ext.synchronize()
-                self.barrier.wait(timeout=60)                         # nobody overwrites a buffer a peer is still reading
-                if rank == 0:
-                    self.calls += 1
-                return 0
-            except Exception:
-                import traceback
-                traceback.print_exc()
-                self.barrier.abort()
-                return 1
-        return _abi.EXCHANGE_FN(fn)
 
 
 CASES = {

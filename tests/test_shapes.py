@@ -11,6 +11,9 @@ import admm_library_amd as pkg
 from admm_library_amd.solver import host_factor, host_scan_packed
 from _shapes import (ALT_TABLE, CERT_CHUNK_CAP, CERT_LDS_DOUBLES, CHUNK_EDGE_CASES, CSRC, MFMA, PER_INSTANCE, PLAIN_ONLY, SCAN_EMPTY_SLICE, SCAN_GEOMETRIES, SCAN_REFACTOR_RHO,
                      SCAN_REFACTOR_SEED, SCAN_SLICEABLE, SHARED, SWEEP_N, SWEEP_SEGMENTS, WIDE, cert_chunk, chunk_edge, gid, scan_shape)
+from _timeshard import ADAPT as TS_ADAPT, ADAPT_DOUBLINGS as TS_ADAPT_DOUBLINGS
+from _timeshard import CASES as TS_CASES, RHO_FACTOR as TS_RHO_FACTOR, UPDATE_CASES as TS_UPDATE_CASES
+from _timeshard import host_scan_timeshard as ts_host_scan, host_segments as ts_host_segments, second_problem as ts_second_problem
 
 
 def test_compiled_shape_lists_are_pinned():
@@ -83,6 +86,27 @@ def test_scan_geometries_pass_the_probe_and_the_growth_bound(lib, geom):
     widest = int((rng[:, 1] - rng[:, 0]).max()) // 8          # batches of SCAN_U = 8 k-steps
     assert (geom in SCAN_SLICEABLE) == (widest >= 8), (geom, widest)
     assert (geom in SCAN_EMPTY_SLICE) == (S <= 4 and widest < 4), (geom, widest)
+
+
+@pytest.mark.parametrize("case", TS_CASES)
+def test_timeshard_cases_pass_the_growth_bound(lib, case):
+    """Every case of tests/test_gpu_timeshard_ranks.py -- with the rho values and the second problem its state changes move a
+    handle to -- keeps both scan matrices, in the rank-by-rank layout the handles run, inside the conditioning bound: the 1e-10
+    the GPU tests ask for rests on inputs the reference handles as well.  The path the table records (the forward-elimination
+    probe passes or not) and the window shape it records (ranks of unequal length, an interior rank) are checked here too."""
+    c = TS_CASES[case]
+    p, S, rho = c.make(), ts_host_segments(c), c.opts["rho"]
+    assert S % c.world == 0
+    adaptive = [(p, TS_ADAPT[case]["rho"] * 2.0 ** k) for k in range(TS_ADAPT_DOUBLINGS + 1)] if case in TS_ADAPT else []
+    for prob, r in [(p, rho), (p, TS_RHO_FACTOR * rho)] + ([(ts_second_problem(p), rho)] if case in TS_UPDATE_CASES else []) + adaptive:
+        W, WB, ok = ts_host_scan(prob, r, S, c.world)
+        growth = np.abs(W).max(), np.abs(WB).max() if ok else 0.0
+        assert max(growth) <= SCAN_GROWTH_MAX, (case, r, growth)
+        assert ok == (c.alternating or bool(c.opts.get("flags", 0))), (case, r)       # (B: the probe passes, the flag declines)
+    seg = host_factor(p, rho, S)["seg_start"]
+    sl = S // c.world
+    lens = [int(seg[(r + 1) * sl] - seg[r * sl]) for r in range(c.world)]
+    assert sum(lens) == p.N and (len(set(lens)) > 1) == c.uneven, (case, lens)
 
 
 def test_scan_refactor_problems_pass_the_probe_and_the_growth_bound(lib):
