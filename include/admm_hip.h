@@ -155,7 +155,18 @@ typedef struct admm_options {
 #define ADMM_FLAG_NO_ALTERNATE 8 /* always eliminate backward / substitute forward (xb + xfz kernels); by
                                   default (unless the forward form fails its host check for the problem),
                                   consecutive iterations alternate the elimination direction so that each
-                                  substitution sweep is fused with the next elimination sweep */
+                                  substitution sweep is fused with the next elimination sweep.
+                                  ACCURACY: with this flag the iterates stay within 1e-10 of the sequential Riccati
+                                  loop's on every stage at any iteration count (measured <= 7e-13 through 400
+                                  iterations at N = 1000).  The default path holds 1e-10 on the stages past the
+                                  early-gain zone of the forward form (stage 64 on: measured <= 2e-11) at any
+                                  count, and on every stage through the first 16 iterations of a fresh handle;
+                                  the controls of the first few stages then drift -- at N = 1000, n = 6, rho = 0.8 ... 2
+                                  they leave 1e-10 between iterations 80 and 200 and reach 3e-10 by 400 (2e-9 at
+                                  rho = 16); 1.3e-11 at rho = 0.05, 4e-12 at N = 200 (measured; DESIGN.md §4.8, §5;
+                                  tests/test_gpu_alt_drift.py holds them to a NumPy emulation of the form).  A caller
+                                  that needs 1e-10 on u_0 at any count sets this flag (29.33 instead of 21.33 B per
+                                  stacked element and iteration at n = 6, m = 3). */
 
 typedef struct admm_info {
   int32_t iters_run;      /* batch iterations executed by the last admm_solve */
@@ -632,7 +643,9 @@ int admm_get_geometry(admm_handle* h, int32_t* pitch, int32_t* segs, int32_t* zr
  * (and every refactor: admm_set_rho, the adaptive rule, admm_update_problem) verifies it on the host -- one x-update with a
  * random linear term through both forms -- and falls back to the plain fused path (29.33 instead of 21.33 B per stacked
  * element and iteration at n = 6, m = 3) when the relative mismatch alt_check exceeds alt_gate.  That fallback is reported
- * here and through admm_last_warning(), never silently. */
+ * here and through admm_last_warning(), never silently.  The gate bounds ONE x-update; what it implies for the iterates is
+ * stated at ADMM_FLAG_NO_ALTERNATE: 1e-10 past the first stages at any iteration count and everywhere through 16 iterations,
+ * not 1e-10 on the controls of the first stages of a long run at rho >= 0.2 on a long horizon. */
 typedef struct admm_path_info {
   int32_t alternating;     /* 1: the alternating-direction fused kernels run; 0: the plain fused (or unfused) path */
   int32_t alt_requested;   /* 1: options / compiled kernels allow alternation for this problem class (0: ADMM_FLAG_NO_ALTERNATE,
@@ -646,7 +659,7 @@ typedef struct admm_path_info {
   int32_t per_instance;    /* 1: time_varying = 2 (device factor, operands per QP from HBM) */
   double  alt_check;       /* relative mismatch of the forward-elimination form on the host verification vector; -1: not run
                               (alternation not requested, or the form could not be built: a singular A_k or covariance) */
-  double  alt_gate;        /* the bound alt_check must meet (5e-12) */
+  double  alt_gate;        /* the bound alt_check must meet (5e-12, on one x-update: see above for the iterates) */
   double  scan_growth;     /* largest |entry| of the segment-scan matrices (conditioning bound: <= 100 with automatic segments) */
 } admm_path_info;
 int admm_get_path(admm_handle* h, admm_path_info* info);

@@ -193,3 +193,61 @@ def x_update_alt(rec, n, m, g, x0):
             w[:, k, m:] = x
             x = x @ a["AI"][k].T + u @ a["AIB"][k].T
     return w.reshape(batch, N * nb)
+
+
+# ---------------------------------------------------------------------------
+# The whole alternating iteration: which iterations of a call run the
+# forward-elimination form (next_form / after_form of csrc/admm_launch.hip),
+# and the ADMM loop around the two x-updates above.
+# ---------------------------------------------------------------------------
+def form_schedule(count, v_valid=False, alt_state="none"):
+    """The forms of the `count` iterations of one admm_iterate call, as next_form picks them: a list of "plain", "fwd_start", "fwd"
+    (all three: the Riccati form) and "bwd" (the forward-elimination form).  v_valid / alt_state: the handle's state on entry
+    (a fresh handle: False / "none"; afterwards True / what the previous call returned -- admm_get changes neither).
+    Returns (forms, alt_state on return)."""
+    forms = []
+    for remaining in range(count, 0, -1):
+        if not v_valid:
+            f = "plain"
+        elif alt_state == "bwd":
+            f = "fwd"
+        elif alt_state == "fwd" and remaining % 2 == 0:
+            f = "bwd"
+        else:
+            f = "fwd_start" if remaining >= 2 else "plain"
+        forms.append(f)
+        v_valid = True
+        alt_state = {"plain": "none", "bwd": "bwd"}.get(f, "fwd")
+    assert not forms or forms[-1] != "bwd"          # (a call never returns after a backward iteration)
+    return forms, alt_state
+
+
+def alternating_loop(rec, p, rho, iters, alpha=1.0, checkpoints=None, plain=False):
+    """`iters` ADMM iterations from (z, y) = 0, as one admm_iterate call on a fresh handle, with the x-updates emulated from the host
+    records `rec` (host_factor(p, rho, S)): x_update_alt where form_schedule runs the forward-elimination form,
+    x_update_segmented(scan="gemm") elsewhere; plain=True: the latter on every iteration (ADMM_FLAG_NO_ALTERNATE).
+    g = q - rho (z - y); z, y by admm_ref.z_update.  Returns {checkpoint: (w, z, y)} (checkpoints=None: iters alone) and the
+    forms that ran."""
+    import admm_ref as ar
+    n, m, N = p.n, p.m, p.N
+    cps = sorted(set(checkpoints)) if checkpoints is not None else [iters]
+    assert cps and cps[-1] <= iters and cps[0] >= 1
+    lo, hi = ar.expand_bounds(p.lo, p.hi, N, p.nb)
+    un = None if p.unorm is None else ar.expand_unorm(p.unorm, N)
+    q = None if p.q is None else np.asarray(p.q, np.float64).reshape(p.batch, p.L)
+    forms, _ = form_schedule(iters)
+    z = np.zeros((p.batch, p.L))
+    y = np.zeros((p.batch, p.L))
+    out = {}
+    for it in range(1, iters + 1):
+        g = -rho * (z - y)
+        if q is not None:
+            g = g + q
+        if forms[it - 1] == "bwd" and not plain:
+            w = x_update_alt(rec, n, m, g, p.x0)
+        else:
+            w = x_update_segmented(rec, n, m, g, p.x0, scan="gemm")
+        z, y = ar.z_update(w, z, y, lo, hi, alpha, un, m)
+        if it in cps:
+            out[it] = (w, z.copy(), y.copy())
+    return out, forms
