@@ -14,8 +14,9 @@ int upload_h2d(admm_handle* h, void* dst, const void* src, size_t bytes) {
     HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
     return ADMM_OK;
   }
+  int rc;
   for (int i = 0; i < 2; ++i) {
-    if (!h->pin[i]) HIP_TRY(hipHostMalloc((void**)&h->pin[i], PIN_BYTES, hipHostMallocDefault));
+    if (!h->pin[i] && (rc = halloc(h, &h->pin[i], PIN_BYTES))) return rc;
     if (!h->pin_ev[i]) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming));
   }
   int slot = 0;
@@ -39,8 +40,9 @@ int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ADMM_OK;
   }
+  int slot = 0, rc;
   for (int i = 0; i < 2; ++i) {
-    if (!h->pin[i]) HIP_TRY(hipHostMalloc((void**)&h->pin[i], PIN_BYTES, hipHostMallocDefault));
+    if (!h->pin[i] && (rc = halloc(h, &h->pin[i], PIN_BYTES))) return rc;
     if (!h->pin_ev[i]) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev[i], hipEventDisableTiming));
   }
   HIP_TRY(hipEventSynchronize(h->pin_ev[0]));                 // (an upload may have been the buffers' last user)
@@ -52,7 +54,6 @@ int download_d2h(admm_handle* h, void* dst, const void* src, size_t bytes) {
     host_parallel(len, 1, [pb, db](size_t b, size_t e) { std::memcpy(db + b, pb + b, e - b); });
     return ADMM_OK;
   };
-  int slot = 0, rc;
   size_t prev_off = 0, prev_len = 0;
   for (size_t off = 0; off < bytes; off += PIN_BYTES, slot ^= 1) {
     const size_t len = std::min(PIN_BYTES, bytes - off);
@@ -344,7 +345,7 @@ int prepare_device_problem(int device, hipStream_t s, const admm_problem* p, con
 }
 
 int check_scratch(admm_handle* h) {
-  return h->chk_d ? ADMM_OK : dalloc(&h->chk_d, CHK_SLOTS);
+  return h->chk_d ? ADMM_OK : dalloc(h, &h->chk_d, CHK_SLOTS);
 }
 
 // ---- CallerIO: the caller-array contract of the host and *_device forms of a handle call (admm_runtime.hpp) ----
@@ -436,64 +437,47 @@ void destroy_graph(admm_handle* h) {
   }
 }
 
+// ---- memory of a handle (admm_runtime.hpp): one function allocates and records, release() frees what is recorded ----
+
+static std::atomic<int64_t> g_owned_count{0}, g_owned_bytes{0};     // device allocations only (admm_debug_handle_memory)
+
+int handle_alloc(admm_handle* h, void** p, size_t bytes, bool zeroed, bool pinned) {
+  void* a = nullptr;
+  const hipError_t e = pinned ? hipHostMalloc(&a, bytes, hipHostMallocDefault) : hipMalloc(&a, bytes);
+  if (e != hipSuccess)
+    return pinned ? fail(ADMM_ERR_HIP, std::string("hipHostMalloc failed: ") + hipGetErrorString(e))
+                  : fail(ADMM_ERR_ALLOC, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+  h->owned.push_back({a, bytes, pinned});
+  if (!pinned) { g_owned_count += 1; g_owned_bytes += (int64_t)bytes; }
+  *p = a;
+  if (zeroed) HIP_TRY(h->stream ? hipMemsetAsync(a, 0, bytes, h->stream) : hipMemset(a, 0, bytes));
+  return ADMM_OK;
+}
+
+static void free_owned(const admm_handle::Owned& o) {
+  if (o.pinned) { (void)hipHostFree(o.ptr); return; }
+  (void)hipFree(o.ptr);
+  g_owned_count -= 1;
+  g_owned_bytes -= (int64_t)o.bytes;
+}
+
+void handle_free(admm_handle* h, void* p) {
+  auto it = std::find_if(h->owned.begin(), h->owned.end(), [p](const admm_handle::Owned& o) { return o.ptr == p; });
+  if (it == h->owned.end()) return;
+  free_owned(*it);
+  h->owned.erase(it);
+}
+
 void release(admm_handle* h) {
   if (!h) return;
   h->spec.clear();               // joins the background factorisations (they read the handle's problem copy)
   h->spec_stale.clear();
   (void)hipSetDevice(h->device);
   destroy_graph(h);
-  // the big per-stage arrays are held as pointers biased by the stage window (admm_runtime.hpp): undo that before freeing
-  for (double** b : {&h->w, &h->z, &h->y, &h->v, &h->q})
-    if (*b) *b += win_bias(h);
-  for (double** b : {&h->dbuf, &h->mvec, &h->wu})
-    if (*b) *b += win_bias_m(h);
-  double** bufs[] = {&h->w, &h->z, &h->y, &h->v, &h->q, &h->dbuf, &h->scan_in, &h->scan_out, &h->scanWp,
-                     &h->part, &h->resid, &h->lo, &h->hi, &h->ub, &h->kap, &h->recB, &h->recF, &h->recS, &h->stage,
-                     &h->recFE, &h->recBE, &h->mvec, &h->scanWpB, &h->wu, &h->xbnd, &h->soft_d, &h->skap_d, &h->soft_out};
-  for (auto b : bufs)
-    if (*b) { (void)hipFree(*b); *b = nullptr; }
-  {
-    double** pb[] = {&h->Ad, &h->Bd, &h->Kd, &h->Sd, &h->lod, &h->hid, &h->lodT, &h->hidT, &h->Qd, &h->Rd, &h->QNd,
-                     &h->Ad2, &h->Bd2, &h->Kd2, &h->Sd2, &h->Qd2, &h->Rd2, &h->QNd2, &h->rho2_d};
-    if (h->qflag_d) { (void)hipFree(h->qflag_d); h->qflag_d = nullptr; }
-    if (h->nveto_d) { (void)hipFree(h->nveto_d); h->nveto_d = nullptr; }
-    for (auto b : pb)
-      if (*b) { (void)hipFree(*b); *b = nullptr; }
-    if (h->pfail) { (void)hipFree(h->pfail); h->pfail = nullptr; }
-    if (h->rho_d) { (void)hipFree(h->rho_d); h->rho_d = nullptr; }
-    double** sb[] = {&h->Omd, &h->Psd, &h->Segd};
-    for (auto b : sb)
-      if (*b) { (void)hipFree(*b); *b = nullptr; }
-    if (h->pgrow) { (void)hipFree(h->pgrow); h->pgrow = nullptr; }
-    if (h->cscale_d) { (void)hipFree(h->cscale_d); h->cscale_d = nullptr; }
-    int** ib[] = {&h->nupd_d, &h->todo_d, &h->nchanged_d};
-    for (auto b : ib)
-      if (*b) { (void)hipFree(*b); *b = nullptr; }
-  }
-  if (h->scanWd) { (void)hipFree(h->scanWd); h->scanWd = nullptr; }
-  if (h->scanWBd) { (void)hipFree(h->scanWBd); h->scanWBd = nullptr; }
-  if (h->scan_rows) { (void)hipFree(h->scan_rows); h->scan_rows = nullptr; }
-  if (h->scan_rowsB) { (void)hipFree(h->scan_rowsB); h->scan_rowsB = nullptr; }
-  if (h->recMF) { (void)hipFree(h->recMF); h->recMF = nullptr; }
-  if (h->recMB) { (void)hipFree(h->recMB); h->recMB = nullptr; }
-  if (h->recMF64) { (void)hipFree(h->recMF64); h->recMF64 = nullptr; }
-  if (h->recMB64) { (void)hipFree(h->recMB64); h->recMB64 = nullptr; }
-  int** ibufs[] = {&h->seg_start, &h->status, &h->iters, &h->nconv, &h->scan_range, &h->scan_rangeB, &h->status1, &h->iters1};
-  for (auto b : ibufs)
-    if (*b) { (void)hipFree(*b); *b = nullptr; }
-  if (h->h_nconv) { (void)hipHostFree(h->h_nconv); h->h_nconv = nullptr; }
-  for (int i = 0; i < 2; ++i) {
-    if (h->pin[i]) { (void)hipHostFree(h->pin[i]); h->pin[i] = nullptr; }
-    if (h->pin_ev[i]) { (void)hipEventDestroy(h->pin_ev[i]); h->pin_ev[i] = nullptr; }
-  }
-  if (h->ext_ev) { (void)hipEventDestroy(h->ext_ev); h->ext_ev = nullptr; }
-  if (h->chk_d) { (void)hipFree(h->chk_d); h->chk_d = nullptr; }
-  for (double** b : {&h->certAB, &h->certQR, &h->certPhi, &h->cert_fuel, &h->cert_cseg, &h->cert_cin, &h->cert_part, &h->cert_out,
-                     &h->cert_nu, &h->infeas_y0, &h->infeas_bnd, &h->infeas_part, &h->infeas_out, &h->mpc_edge, &h->mpc_xn, &h->mpc_io})
-    if (*b) { (void)hipFree(*b); *b = nullptr; }
-  if (h->infeas_flag) { (void)hipFree(h->infeas_flag); h->infeas_flag = nullptr; }
-  if (h->soft_cnt) { (void)hipFree(h->soft_cnt); h->soft_cnt = nullptr; }
-  if (h->stream) { (void)hipStreamDestroy(h->stream); h->stream = nullptr; }
+  for (const admm_handle::Owned& o : h->owned) free_owned(o);
+  for (hipEvent_t ev : {h->pin_ev[0], h->pin_ev[1], h->ext_ev})
+    if (ev) (void)hipEventDestroy(ev);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
@@ -515,7 +499,7 @@ int upload_scan_dense(const std::vector<double>& W, int M, int K, double* Wd, in
   return ADMM_OK;
 }
 
-int upload_factor(admm_handle* h) {
+int upload_factor(admm_handle* h, const char* when) {
   HIP_TRY(hipMemcpy(h->recB, h->fac.recB.data(), sizeof(double) * h->fac.recB.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->recF, h->fac.recF.data(), sizeof(double) * h->fac.recF.size(), hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(h->recS, h->fac.recS.data(), sizeof(double) * h->fac.recS.size(), hipMemcpyHostToDevice));
@@ -526,7 +510,7 @@ int upload_factor(admm_handle* h) {
   drop_side_data(h);
   h->alt_state = admm_handle::ALT_NONE;
   if (!h->fac.alt_ok) {                                             // the forward-elimination form did not survive the refactor
-    if (h->alt_allowed) warn_alt_gate(h->fac, h->fac.rho, "refactor");
+    if (h->alt_allowed) warn_alt_gate(h->fac, h->fac.rho, when);
     h->alt = false; h->alt_allowed = false;
   }
   if (h->mfma_mode) {
@@ -540,8 +524,9 @@ int upload_factor(admm_handle* h) {
   if ((h->has_fuel || h->has_soft) && (rc = upload_kappa(h))) return rc;   // kappa = weight / rho follows every refactor
   if (h->alt_allowed) {
     // (the refactored records go into the allocation of admm_setup: its slack stays zero, and still covers them)
-    if ((rc = check_record_alloc("refactor, recFE", h->recFE_bytes, h->fac.recFE.size() / h->fac.RFE, sizeof(double) * h->fac.RFE))) return rc;
-    if ((rc = check_record_alloc("refactor, recBE", h->recBE_bytes, h->fac.recBE.size() / h->fac.RBE, sizeof(double) * h->fac.RBE))) return rc;
+    const std::string who(when);
+    if ((rc = check_record_alloc((who + ", recFE").c_str(), h->recFE_bytes, h->fac.recFE.size() / h->fac.RFE, sizeof(double) * h->fac.RFE))) return rc;
+    if ((rc = check_record_alloc((who + ", recBE").c_str(), h->recBE_bytes, h->fac.recBE.size() / h->fac.RBE, sizeof(double) * h->fac.RBE))) return rc;
     HIP_TRY(hipMemcpy(h->recFE, h->fac.recFE.data(), sizeof(double) * h->fac.recFE.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(h->recBE, h->fac.recBE.data(), sizeof(double) * h->fac.recBE.size(), hipMemcpyHostToDevice));
     if (!h->scan_gemv) HIP_TRY(hipMemcpy(h->scanWpB, h->fac.scanWpB.data(), sizeof(double) * h->fac.scanWpB.size(), hipMemcpyHostToDevice));
@@ -659,3 +644,8 @@ bool problem_has_soc(const admm_problem* p) {
 
 }  // namespace rt
 }  // namespace admm
+
+extern "C" void admm_debug_handle_memory(int64_t* count, int64_t* bytes) {
+  if (count) *count = admm::rt::g_owned_count.load();
+  if (bytes) *bytes = admm::rt::g_owned_bytes.load();
+}

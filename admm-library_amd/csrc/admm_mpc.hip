@@ -58,11 +58,12 @@ int advance(admm_handle* h, const admm_mpc_step* s, double* u, double* x) {
   const int chunks = chunk_count(h, arr.count);
   const size_t P = h->pitch, edge_count = (size_t)arr.count * (chunks - 1) * h->nb * P;
   if (edge_count > h->mpc_edge_count) {          // (first call, or a larger chunk count asked for since)
-    if (h->mpc_edge) { HIP_TRY(hipFree(h->mpc_edge)); h->mpc_edge = nullptr; h->mpc_edge_count = 0; }
-    if ((rc = dalloc(&h->mpc_edge, edge_count))) return rc;
+    dfree(h, &h->mpc_edge);                      // (hipFree waits for the kernels that still read it)
+    h->mpc_edge_count = 0;
+    if ((rc = dalloc(h, &h->mpc_edge, edge_count))) return rc;
     h->mpc_edge_count = edge_count;
   }
-  if (!h->mpc_xn && (rc = dalloc(&h->mpc_xn, (size_t)h->n * P))) return rc;
+  if (!h->mpc_xn && (rc = dalloc(h, &h->mpc_xn, (size_t)h->n * P))) return rc;
   // the state as (w, z, y) in memory, as admm_get brings it there (w of the last x-update belongs to the old x0)
   if ((rc = ensure_w(h)) || (rc = ensure_zy(h))) return rc;
   double* const arrays[4] = {h->w, h->z, h->y, h->q};
@@ -110,7 +111,7 @@ int advance_common(admm_handle* h, const admm_mpc_step* s, double* u_applied, do
   double *u = u_applied, *x = x_next;
   if (!io.dev()) {
     // the small per-QP arrays cross through one device buffer: du | dx or x_meas | q_tail | u_applied | x_next
-    if (!h->mpc_io && (rc = dalloc(&h->mpc_io, 2 * nu + 2 * nx + nq))) return rc;
+    if (!h->mpc_io && (rc = dalloc(h, &h->mpc_io, 2 * nu + 2 * nx + nq))) return rc;
     double *du_d = h->mpc_io, *dx_d = du_d + nu, *qt_d = dx_d + nx, *u_d = qt_d + nq, *x_d = u_d + nu;
     const double* xin = s->x_meas ? s->x_meas : s->dx;
     if ((s->du && (rc = upload_h2d(h, du_d, s->du, sizeof(double) * nu))) || (xin && (rc = upload_h2d(h, dx_d, xin, sizeof(double) * nx))) ||

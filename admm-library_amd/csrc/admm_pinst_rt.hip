@@ -97,17 +97,17 @@ int pinst_alloc_trial(admm_handle* h, bool dynamics) {
   const size_t P = h->pitch;
   const int n = h->n, m = h->m, N = h->N;
   int rc;
-  if (!h->Kd2 && (rc = dalloc(&h->Kd2, (size_t)N * m * n * P))) return rc;
-  if (!h->Sd2 && (rc = dalloc(&h->Sd2, (size_t)N * m * m * P))) return rc;
-  if (!h->rho2_d && (rc = dalloc(&h->rho2_d, P))) return rc;
-  if (!h->qflag_d && (rc = dalloc(&h->qflag_d, P))) return rc;
-  if (!h->nveto_d && (rc = dalloc(&h->nveto_d, (size_t)1))) return rc;
+  if (!h->Kd2 && (rc = dalloc(h, &h->Kd2, (size_t)N * m * n * P))) return rc;
+  if (!h->Sd2 && (rc = dalloc(h, &h->Sd2, (size_t)N * m * m * P))) return rc;
+  if (!h->rho2_d && (rc = dalloc(h, &h->rho2_d, P))) return rc;
+  if (!h->qflag_d && (rc = dalloc(h, &h->qflag_d, P))) return rc;
+  if (!h->nveto_d && (rc = dalloc(h, &h->nveto_d, (size_t)1))) return rc;
   if (dynamics) {
-    if (!h->Ad2 && (rc = dalloc(&h->Ad2, (size_t)N * n * n * P))) return rc;
-    if (!h->Bd2 && (rc = dalloc(&h->Bd2, (size_t)N * n * m * P))) return rc;
-    if (!h->Qd2 && (rc = dalloc(&h->Qd2, (size_t)n * n))) return rc;
-    if (!h->Rd2 && (rc = dalloc(&h->Rd2, (size_t)m * m))) return rc;
-    if (!h->QNd2 && (rc = dalloc(&h->QNd2, (size_t)n * n))) return rc;
+    if (!h->Ad2 && (rc = dalloc(h, &h->Ad2, (size_t)N * n * n * P))) return rc;
+    if (!h->Bd2 && (rc = dalloc(h, &h->Bd2, (size_t)N * n * m * P))) return rc;
+    if (!h->Qd2 && (rc = dalloc(h, &h->Qd2, (size_t)n * n))) return rc;
+    if (!h->Rd2 && (rc = dalloc(h, &h->Rd2, (size_t)m * m))) return rc;
+    if (!h->QNd2 && (rc = dalloc(h, &h->QNd2, (size_t)n * n))) return rc;
   }
   return ADMM_OK;
 }
@@ -221,64 +221,49 @@ int setup_pinst(admm_handle* h, const admm_problem* p, Mem mem) {
   h->alt = h->alt_allowed = false;
   h->time_varying = 2;
   h->stage_bounds = p->stage_bounds;
-  {  // z-kernel chunking of the shared-bounds read-out kernel (as in admm_setup)
-    const int col_groups = (h->pitch / 2 + Z_THREADS - 1) / Z_THREADS;
-    int chunks = std::max(1, (h->num_cus + col_groups - 1) / col_groups);
-    int zr = ((h->L + chunks - 1) / chunks + 3) / 4 * 4;
-    if (zr < 4) zr = 4;
-    if (h->has_soc) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk
-    h->zrows = zr;
-    h->zchunks = (h->L + zr - 1) / zr;
-  }
+  choose_zchunks(h, 0);          // of the shared-bounds read-out kernel (options.zrows is not read here)
   const size_t P = h->pitch, L = h->L;
   const int n = h->n, m = h->m, N = h->N;
   HIP_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
   int rc;
-#define PD(ptr, cnt) do { if ((rc = dalloc(&(ptr), (size_t)(cnt)))) return rc; HIP_TRY(hipMemsetAsync((ptr), 0, sizeof(*(ptr)) * (size_t)(cnt), h->stream)); } while (0)
-  PD(h->w, L * P); PD(h->z, L * P); PD(h->y, L * P); PD(h->v, L * P);
-  if (h->has_q) PD(h->q, L * P);
-  PD(h->dbuf, (size_t)N * m * P);
-  {  // scan_in = x0 | tseg | eseg,  scan_out = t_in | x_in   ([S][n][pitch] each; only x0 with one segment)
-    const size_t Sn = (size_t)h->S * n;
-    PD(h->scan_in, (size_t)(n + 2 * Sn) * P);
-    PD(h->scan_out, 2 * Sn * P);
-    h->x0 = h->scan_in;
-    h->tseg = h->scan_in + (size_t)n * P;
-    h->eseg = h->tseg + Sn * P;
-    h->tin = h->scan_out;
-    h->xin = h->scan_out + Sn * P;
-    std::vector<int32_t> ss(h->S + 1);
-    for (int sgm = 0; sgm <= h->S; ++sgm) ss[sgm] = (int32_t)(((int64_t)sgm * N) / h->S);
-    PD(h->seg_start, (size_t)h->S + 1);
-    HIP_TRY(hipMemcpyAsync(h->seg_start, ss.data(), sizeof(int32_t) * ss.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    PD(h->pgrow, 1);
-    if (h->S > 1) {
-      PD(h->Omd, (size_t)N * n * m * P);
-      PD(h->Psd, (size_t)N * m * n * P);
-      PD(h->Segd, (size_t)h->S * 3 * n * n * P);
-    }
-  }
-  PD(h->part, (size_t)std::max(h->zchunks, h->S) * 5 * P);
-  PD(h->resid, 5 * P);
-  PD(h->lo, L); PD(h->hi, L); PD(h->ub, (size_t)N); PD(h->kap, (size_t)N);
-  PD(h->Ad, (size_t)N * n * n * P); PD(h->Bd, (size_t)N * n * m * P);
-  PD(h->Kd, (size_t)N * m * n * P); PD(h->Sd, (size_t)N * m * m * P);
-  if (h->pbounds) { PD(h->lod, L * P); PD(h->hid, L * P); }
-  if (h->pbounds && h->pi_tiled) { PD(h->lodT, L * P); PD(h->hidT, L * P); }
-  PD(h->Qd, (size_t)n * n); PD(h->Rd, (size_t)m * m); PD(h->QNd, (size_t)n * n);
-  PD(h->pfail, 1); PD(h->status, P); PD(h->iters, P); PD(h->nconv, 1);
-  PD(h->rho_d, P); PD(h->cscale_d, P); PD(h->nupd_d, P); PD(h->todo_d, P); PD(h->nchanged_d, 1);
+  const size_t Sn = (size_t)h->S * n;
   h->stage_rows = std::max(L, (size_t)N * n * n);
-  if ((rc = dalloc(&h->stage, h->stage_rows * (size_t)h->batch))) return rc;
-#undef PD
+  auto za = [h](auto** field, size_t count) { return dalloc(h, field, count, /*zeroed=*/true); };
+  // state and work arrays; scan_in = x0 | tseg | eseg,  scan_out = t_in | x_in   ([S][n][pitch] each; only x0 with one segment)
+  if ((rc = za(&h->w, L * P)) || (rc = za(&h->z, L * P)) || (rc = za(&h->y, L * P)) || (rc = za(&h->v, L * P)) ||
+      (h->has_q && (rc = za(&h->q, L * P))) || (rc = za(&h->dbuf, (size_t)N * m * P)) ||
+      (rc = za(&h->scan_in, (size_t)(n + 2 * Sn) * P)) || (rc = za(&h->scan_out, 2 * Sn * P)) ||
+      (rc = za(&h->seg_start, (size_t)h->S + 1)) || (rc = za(&h->pgrow, 1)) ||
+      (rc = za(&h->part, (size_t)std::max(h->zchunks, h->S) * 5 * P)) || (rc = za(&h->resid, 5 * P)) ||
+      (rc = za(&h->pfail, 1)) || (rc = za(&h->status, P)) || (rc = za(&h->iters, P)) || (rc = za(&h->nconv, 1)) ||
+      (rc = dalloc(h, &h->stage, h->stage_rows * (size_t)h->batch)))
+    return rc;
+  // per-QP operands and factor, transfer matrices of the segments, the box (shared, per instance, tiled), weights, per-QP rho
+  if ((rc = za(&h->Ad, (size_t)N * n * n * P)) || (rc = za(&h->Bd, (size_t)N * n * m * P)) ||
+      (rc = za(&h->Kd, (size_t)N * m * n * P)) || (rc = za(&h->Sd, (size_t)N * m * m * P)) ||
+      (h->S > 1 && ((rc = za(&h->Omd, (size_t)N * n * m * P)) || (rc = za(&h->Psd, (size_t)N * m * n * P)) ||
+                    (rc = za(&h->Segd, (size_t)h->S * 3 * n * n * P)))) ||
+      (rc = za(&h->lo, L)) || (rc = za(&h->hi, L)) || (rc = za(&h->ub, (size_t)N)) || (rc = za(&h->kap, (size_t)N)) ||
+      (h->pbounds && ((rc = za(&h->lod, L * P)) || (rc = za(&h->hid, L * P)))) ||
+      (h->pbounds && h->pi_tiled && ((rc = za(&h->lodT, L * P)) || (rc = za(&h->hidT, L * P)))) ||
+      (rc = za(&h->Qd, (size_t)n * n)) || (rc = za(&h->Rd, (size_t)m * m)) || (rc = za(&h->QNd, (size_t)n * n)) ||
+      (rc = za(&h->rho_d, P)) || (rc = za(&h->cscale_d, P)) || (rc = za(&h->nupd_d, P)) || (rc = za(&h->todo_d, P)) ||
+      (rc = za(&h->nchanged_d, 1)))
+    return rc;
+  h->x0 = h->scan_in;
+  h->tseg = h->scan_in + (size_t)n * P;
+  h->eseg = h->tseg + Sn * P;
+  h->tin = h->scan_out;
+  h->xin = h->scan_out + Sn * P;
+  std::vector<int32_t> ss(h->S + 1);
+  for (int sgm = 0; sgm <= h->S; ++sgm) ss[sgm] = (int32_t)(((int64_t)sgm * N) / h->S);
+  HIP_TRY(hipMemcpyAsync(h->seg_start, ss.data(), sizeof(int32_t) * ss.size(), hipMemcpyHostToDevice, h->stream));
   // The zero-fills above are asynchronous on the handle's NON-BLOCKING stream, and the small uploads below (weights, shared box, thrust
   // bounds) are synchronous copies on the null stream, which does not wait for it: with GBs of fills queued (a wide shape's operand
   // arrays) a copy could land first and be zeroed afterwards -- Q = R = 0, a factor of nonsense, every QP wrong from the first iteration
   // (found by the full-horizon optimality certificate of round 3; the second large handle of a process, whose allocations are fast).
   HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipHostMalloc((void**)&h->h_nconv, sizeof(int), hipHostMallocDefault));
-  if ((rc = pinst_upload(h, p, mem))) return rc;
+  if ((rc = halloc(h, &h->h_nconv, 1)) || (rc = pinst_upload(h, p, mem))) return rc;
   if ((rc = upload_transposed(h, mem, p->x0, h->x0, n))) return rc;
   if (h->has_q && (rc = upload_transposed(h, mem, p->q, h->q, (int)L))) return rc;
   if ((rc = pinst_fill_rho(h, o.rho))) return rc;

@@ -191,8 +191,14 @@ struct admm_handle {
   //   finalises the previous iteration's residuals
   hipGraph_t graph[16] = {};
   hipGraphExec_t graph_exec[16] = {};
+  // Every device and pinned-host allocation made for this handle, as handle_alloc() returned it (the fields above may hold it
+  // biased by the stage window, or swapped with another field): release() frees these and nothing else
+  struct Owned { void* ptr; size_t bytes; bool pinned; };
+  std::vector<Owned> owned;
 };
 
+// live handle-owned device allocations of the process and their bytes (tests/test_gpu_handle_memory.py; not part of the ABI)
+extern "C" void admm_debug_handle_memory(int64_t* count, int64_t* bytes);
 
 namespace admm {
 namespace rt {
@@ -248,6 +254,7 @@ void host_parallel(size_t count, size_t bytes_per_item, F&& fn) {
   for (auto& x : th) x.join();
 }
 
+// device memory that belongs to no handle (the scratch slots of admm_setup_device, the SCvx counter): freed by whoever allocates it
 template <typename T>
 int dalloc(T** p, size_t count) {
   hipError_t e = hipMalloc((void**)p, sizeof(T) * (count ? count : 1));
@@ -255,6 +262,24 @@ int dalloc(T** p, size_t count) {
   return ADMM_OK;
 }
 
+// ---- memory of a handle (admm_hostio.hip): every allocation is recorded in h->owned and freed by release().
+// zeroed: filled with zeros on the handle's stream (before the stream exists: at once).  The fill is asynchronous, and the handle's
+// stream is non-blocking: synchronise it before a null-stream copy into the same array.
+int handle_alloc(admm_handle* h, void** p, size_t bytes, bool zeroed, bool pinned);
+void handle_free(admm_handle* h, void* p);       // a recorded allocation, before release() (nullptr: nothing)
+template <typename T>
+int dalloc(admm_handle* h, T** field, size_t count, bool zeroed = false) {
+  return handle_alloc(h, (void**)field, sizeof(T) * (count ? count : 1), zeroed, false);
+}
+template <typename T>
+int halloc(admm_handle* h, T** field, size_t count) {      // pinned host memory
+  return handle_alloc(h, (void**)field, sizeof(T) * count, false, true);
+}
+template <typename T>
+void dfree(admm_handle* h, T** field) {          // (a field that holds the allocation's own address)
+  handle_free(h, *field);
+  *field = nullptr;
+}
 
 // Device arrays of stage records that a kernel stages by LDS-DMA (glds_chunk, admm_kernels.hpp: recFE / recBE, recMF / recMB):
 // a chunk is copied in whole KiB pieces, so its last piece reads up to 1008 bytes past the chunk -- past the ARRAY for the
@@ -267,6 +292,12 @@ inline int check_record_alloc(const char* what, size_t alloc_bytes, size_t stage
   return fail(ADMM_ERR_INVALID, std::string(what) + ": " + std::to_string(alloc_bytes) + " bytes allocated for " + std::to_string(stages) +
               " stage records of " + std::to_string(stage_bytes) + " bytes; the KiB-wise LDS-DMA copy reads up to " +
               std::to_string(rec_alloc_needed(stages, stage_bytes)));
+}
+// such an array for `payload` bytes of records: allocated with the slack, zeroed; *alloc_bytes = what check_record_alloc is given
+template <typename T>
+int dalloc_records(admm_handle* h, T** field, size_t payload, size_t* alloc_bytes = nullptr) {
+  if (alloc_bytes) *alloc_bytes = payload + REC_SLACK_BYTES;
+  return handle_alloc(h, (void**)field, payload + REC_SLACK_BYTES, true, false);
 }
 
 // ---- launches, exchange and iteration forms (admm_launch.hip)
@@ -373,8 +404,13 @@ void warn_alt_gate(const admm::Factor& f, double rho, const char* when);
 double scan_growth(const admm::Factor& f);
 void destroy_graph(admm_handle* h);
 void release(admm_handle* h);
+// a handle under construction: released when set-up returns early, with the message of the failure kept
+struct HandleReleaser {
+  void operator()(admm_handle* h) const { std::string keep = g_err; release(h); g_err = keep; }
+};
+using HandleGuard = std::unique_ptr<admm_handle, HandleReleaser>;
 int upload_scan_dense(const std::vector<double>& W, int M, int K, double* Wd, int* rows_d);
-int upload_factor(admm_handle* h);
+int upload_factor(admm_handle* h, const char* when = "refactor");   // when: the call, as the messages and the warning name it
 int upload_bounds(admm_handle* h, const admm_problem* p);
 void keep_shared(admm_handle* h, const admm_problem* p);
 bool problem_has_soc(const admm_problem* p);
@@ -398,6 +434,7 @@ int pinst_try(admm_handle* h, const double* Ad, const double* Bd, const double* 
               const double* rhov, const int* todo, int* n_not_pd, int* n_grown);
 int pinst_segments(admm_handle* h);
 int setup_pinst(admm_handle* h, const admm_problem* p, Mem mem);
+void choose_zchunks(admm_handle* h, int zrows);   // admm_api.hip; zrows = 0: one workgroup per CU
 
 // ---- refactors: background candidates of the adaptive rule, rho changes (admm_rho_update.hip)
 admm_problem shared_problem(const admm_handle* h);
