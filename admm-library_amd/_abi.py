@@ -187,6 +187,16 @@ def marshal_soft(p: Problem):
     return np.ascontiguousarray(np.broadcast_to(np.asarray(p.soft, np.float64), p.lo.shape), np.float64)
 
 
+def marshal_halfspace(p: Problem):
+    """(a, b, nh, per_qp) of p.hs_a / p.hs_b as admm_setup_halfspace / admm_set_halfspace read them: contiguous fp64, C order
+    (a[b][k][i], b[b][k]); nh and the form inferred from the shapes."""
+    from .problems import halfspace_form
+    a = np.ascontiguousarray(p.hs_a, np.float64)
+    b = np.ascontiguousarray(p.hs_b, np.float64)
+    nh, per_qp = halfspace_form(a, b, p.N, p.n, p.batch)
+    return a, b, nh, per_qp
+
+
 def marshal_device_problem(p, row_major: bool = False):
     """marshal_problem of a DeviceProblem (validated here): the CProblem holds device pointers.  The layout work marshal_problem does
     on the host -- column-major matrices, the broadcast of unorm -- is done by torch on the tensors' GPU (copies on the current

@@ -6,6 +6,7 @@
 #include "admm_consensus.hpp"
 #include "admm_infeas.hpp"
 #include "admm_soft.hpp"
+#include "admm_halfspace.hpp"
 
 
 using namespace admm::rt;
@@ -27,6 +28,12 @@ struct SetupRequest {
   const double* fuel;            // admm_setup_fuel: the weights of the minimum-fuel term, in unorm's shape; NULL = none
   int group;                     // admm_setup_consensus: QPs per scenario group, 0 = a handle without groups
   const double* soft;            // admm_setup_soft: the weights of the soft box, in lo's shape; NULL = none
+  // admm_setup_halfspace: a[b][k][i], b[b][k] of one half-space per stage on the first hs_nh state rows (one "QP" unless hs_perqp);
+  // hs_nh = 0: none.  hs_any: the stages with a plane for some QP, filled by check_setup_request
+  const double *hs_a = nullptr, *hs_b = nullptr;
+  int hs_nh = 0;
+  bool hs_perqp = false;
+  std::vector<char> hs_any;
 };
 
 // options and problem data, then what a fuel term, scenario groups, soft weights and time shards each exclude (the standalone z
@@ -68,6 +75,19 @@ static int check_setup_request(SetupRequest& r) {
     if ((rc = validate_soft(p, r.soft, false, r.fuel ? fk.data() : nullptr))) return rc;
     // (no time-sharded or consensus form: neither admm_setup_timeshard nor admm_setup_consensus takes weights)
     o.flags |= ADMM_FLAG_UNFUSED;      // the (z, y) pair, never the v-form: the v -> (z, y) read-out kernels know only the hard prox
+  }
+  if (r.hs_nh) {
+    // the projection exists as the standalone z kernel of the one-lane fp64 path of batch-shared dynamics only
+    if (p->time_varying == 2) return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_halfspace: half-spaces need batch-shared dynamics (time_varying = 0 or 1)");
+    if (o.precision_mode != ADMM_PRECISION_FP64)
+      return fail(ADMM_ERR_UNSUPPORTED, "admm_setup_halfspace: precision_mode " + std::to_string(o.precision_mode) + ": half-spaces are not supported by the MFMA forms (use ADMM_PRECISION_FP64)");
+    if (r.hs_nh < 1 || r.hs_nh > p->n)
+      return fail(ADMM_ERR_INVALID, "admm_setup_halfspace: nh = " + std::to_string(r.hs_nh) + " must lie in 1 .. n = " + std::to_string(p->n));
+    if ((rc = halfspace_stages("admm_setup_halfspace", r.hs_a, r.hs_b, r.hs_perqp ? p->batch : 1, p->N, r.hs_nh, r.hs_any)) ||
+        (rc = halfspace_box_open("admm_setup_halfspace", p, r.hs_any, r.hs_nh)))
+      return rc;
+    // (no time-sharded, consensus or soft form: none of those set-up calls takes planes)
+    o.flags |= ADMM_FLAG_UNFUSED;      // the (z, y) pair, never the v-form: the v -> (z, y) read-out kernels know only the per-row prox
   }
   if (r.ts_n) {
     if (r.ts_n < 1 || r.ts_rank < 0 || r.ts_rank >= r.ts_n) return fail(ADMM_ERR_INVALID, "admm_setup_timeshard: need 0 <= rank < nranks");
@@ -111,6 +131,9 @@ static void init_handle(admm_handle* h, const SetupRequest& r, int dev) {
   h->has_q = p->q != nullptr;
   h->has_soc = problem_has_soc(p) || r.fuel != nullptr;    // a fuel handle runs the SOC forms with or without a thrust bound
   h->cons_G = r.group;
+  h->hs_nh = r.hs_nh;
+  h->hs_perqp = r.hs_perqp;
+  h->hs_any = r.hs_any;
   if (r.soft) {
     h->has_soft = true;
     h->soft.resize(h->L);
@@ -177,7 +200,7 @@ void choose_zchunks(admm_handle* h, int zrows) {
     zr = ((zr + 3) / 4) * 4;
     if (zr < 4) zr = 4;
   }
-  if (h->has_soc || h->cons_G) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk (also with soft weights)
+  if (h->has_soc || h->cons_G || h->hs_nh) zr = ((zr + h->nb - 1) / h->nb) * h->nb;   // block-structured kernels: whole blocks per chunk (also with soft weights)
   h->zrows = zr;
   h->zchunks = (h->L + zr - 1) / zr;
 }
@@ -332,6 +355,8 @@ static int alloc_shared(admm_handle* h) {
   if ((rc = dalloc(h, &h->part, part_chunks * 5 * P, true)) || (rc = dalloc(h, &h->resid, 5 * P, true)) ||
       (rc = dalloc(h, &h->lo, L)) || (rc = dalloc(h, &h->hi, L)) || (rc = dalloc(h, &h->ub, (size_t)h->N)) || (rc = dalloc(h, &h->kap, (size_t)h->N)) ||
       (h->has_soft && ((rc = dalloc(h, &h->soft_d, L)) || (rc = dalloc(h, &h->skap_d, L)))) ||
+      (h->hs_nh && ((rc = dalloc(h, &h->hs_a, (size_t)h->N * h->hs_nh * (h->hs_perqp ? P : 1), true)) ||
+                    (rc = dalloc(h, &h->hs_b, (size_t)h->N * (h->hs_perqp ? P : 1), true)))) ||
       (rc = dalloc(h, &h->recB, f.recB.size())) || (rc = dalloc(h, &h->recF, f.recF.size())) || (rc = dalloc(h, &h->recS, f.recS.size())) ||
       (rc = dalloc(h, &h->seg_start, f.seg_start.size())) || (rc = dalloc(h, &h->status, P, true)) || (rc = dalloc(h, &h->iters, P, true)) ||
       (rc = dalloc(h, &h->nconv, 1)) || (rc = dalloc(h, &h->stage, Lw * (size_t)h->batch)))
@@ -503,13 +528,32 @@ int admm_host_factor_mfma(const admm_problem* p, double rho, int32_t segments, i
   return ADMM_OK;
 }
 
+// the planes of a half-space handle into h->hs_a / h->hs_b (their addresses never change): the shared form as it is, the per-QP
+// form through the transposing upload.  Returns with the copies complete.
+static int upload_halfspace(admm_handle* h, Mem mem, const double* a, const double* b) {
+  int rc;
+  if (h->hs_perqp) {
+    if ((rc = upload_transposed(h, mem, a, h->hs_a, h->N * h->hs_nh)) || (rc = upload_transposed(h, mem, b, h->hs_b, h->N))) return rc;
+    return ADMM_OK;
+  }
+  const hipMemcpyKind kind = mem == Mem::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIP_TRY(hipMemcpyAsync(h->hs_a, a, sizeof(double) * (size_t)h->N * h->hs_nh, kind, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->hs_b, b, sizeof(double) * (size_t)h->N, kind, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return ADMM_OK;
+}
+
+// the planes of admm_setup_halfspace
+struct HalfspaceArgs { const double *a, *b; int nh; bool perqp; };
+
 static int setup_common(admm_handle** out, const admm_problem* p, const admm_options* o_in, int ts_rank, int ts_n,
                         admm_exchange_fn ts_fn, void* ts_ctx, Mem src = Mem::Host, const DeviceScan* scan = nullptr,
-                        const double* fuel = nullptr, int group = 0, const double* soft = nullptr) {
+                        const double* fuel = nullptr, int group = 0, const double* soft = nullptr, const HalfspaceArgs* hs = nullptr) {
   if (!out || !p) return fail(ADMM_ERR_INVALID, "NULL argument");
   *out = nullptr;
   g_warn.clear();
   SetupRequest r{p, {}, ts_rank, ts_n, ts_fn, ts_ctx, src, scan, fuel, group, soft};
+  if (hs) { r.hs_a = hs->a; r.hs_b = hs->b; r.hs_nh = hs->nh; r.hs_perqp = hs->perqp; }
   if (o_in) r.o = *o_in; else admm_default_options(&r.o);
   int rc, dev;
   if ((rc = check_setup_request(r)) || (rc = pick_device(r.o.device, &dev))) return rc;
@@ -533,6 +577,7 @@ static int setup_common(admm_handle** out, const admm_problem* p, const admm_opt
   HIP_TRY(hipMemcpy(h->seg_start, h->fac.seg_start.data(), sizeof(int32_t) * h->fac.seg_start.size(), hipMemcpyHostToDevice));
   if ((rc = upload_transposed(h, src, p->x0, h->x0, h->n))) return rc;
   if (h->has_q && (rc = upload_transposed(h, src, p->q, h->q, h->L))) return rc;
+  if (h->hs_nh && (rc = upload_halfspace(h, Mem::Host, r.hs_a, r.hs_b))) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   *out = guard.release();
   return ADMM_OK;
@@ -613,6 +658,121 @@ int admm_get_soft_report(admm_handle* h, double* penalty, double* max_violation,
 }
 int admm_get_soft_report_device(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated, void* hip_stream) {
   return soft_report_common(h, penalty, max_violation, n_violated, Mem::Device, hip_stream);
+}
+
+// One half-space per stage: admm_setup_fuel with a' xi <= b on the first nh state rows of every block; the
+// z-update is zdual_halfspace_kernel.
+int admm_setup_halfspace(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, const double* a,
+                         const double* b, int32_t nh, int32_t per_instance) {
+  if (out) *out = nullptr;
+  if (!a || !b) return fail(ADMM_ERR_INVALID, "admm_setup_halfspace: a and b must not be NULL (admm_setup / admm_setup_fuel set up a handle without half-spaces)");
+  if (nh < 1) return fail(ADMM_ERR_INVALID, "admm_setup_halfspace: nh = " + std::to_string(nh) + " must lie in 1 .. n");
+  const HalfspaceArgs hs{a, b, nh, per_instance != 0};
+  return setup_common(out, p, o, 0, 0, nullptr, nullptr, Mem::Host, nullptr, fuel, 0, nullptr, &hs);
+}
+
+// New planes on a half-space handle, same form and nh: nothing of the handle is written before every check has passed.  The
+// state is the (z, y) pair already (such a handle never enters the v-form) and the factor does not depend on the planes.
+static int set_halfspace_common(admm_handle* h, const double* a, const double* b, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_set_halfspace_device" : "admm_set_halfspace";
+  if (!h || !a || !b) return fail(ADMM_ERR_INVALID, "NULL argument");
+  g_warn.clear();
+  if (!h->hs_nh) return fail(ADMM_ERR_INVALID, std::string(fn) + ": half-spaces cannot be added to a handle (set it up with admm_setup_halfspace)");
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  const int cnt = h->hs_perqp ? h->batch : 1, N = h->N, nh = h->hs_nh;
+  const size_t na = (size_t)cnt * N * nh, nbv = (size_t)cnt * N;
+  int rc;
+  if ((rc = io.check_ptr(a, na * sizeof(double), "a")) || (rc = io.check_ptr(b, nbv * sizeof(double), "b"))) return rc;
+  std::vector<char> any;
+  if (!io.dev()) {
+    if ((rc = halfspace_stages(fn, a, b, cnt, N, nh, any))) return rc;
+  } else {
+    int bad;
+    if ((rc = io.begin()) || (rc = io.check_finite({{a, na, "a"}, {b, nbv, "b"}}, &bad))) return rc;
+    if (bad >= 0) return fail(ADMM_ERR_INVALID, std::string(fn) + ": non-finite entry in a or b");
+    if (h->hs_perqp) {              // the device-side findings: which stages have a plane for some QP, and whether an a'a is unusable
+      if (!h->hs_flags && (rc = dalloc(h, &h->hs_flags, (size_t)2 * N))) return rc;
+      std::vector<int> fl((size_t)2 * N);
+      HIP_TRY(hipMemsetAsync(h->hs_flags, 0, sizeof(int) * fl.size(), h->stream));
+      admm::launch_halfspace_scan(h->stream, a, h->batch, N, nh, h->hs_flags, h->hs_flags + N);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(fl.data(), h->hs_flags, sizeof(int) * fl.size(), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      any.assign(N, 0);
+      for (int k = 0; k < N; ++k) {
+        if (fl[N + k]) return fail(ADMM_ERR_INVALID, std::string(fn) + ": a'a of stage " + std::to_string(k) + " is not a normal number (scale the row)");
+        any[k] = fl[k] != 0;
+      }
+    } else {                        // the shared form is N (nh + 1) doubles: checked on the host, as a DeviceProblem's small arrays are
+      std::vector<double> ah(na), bh(nbv);
+      HIP_TRY(hipMemcpyAsync(ah.data(), a, sizeof(double) * na, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(bh.data(), b, sizeof(double) * nbv, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      if ((rc = halfspace_stages(fn, ah.data(), bh.data(), 1, N, nh, any))) return rc;
+    }
+  }
+  const admm_problem p = shared_problem(h);
+  if ((rc = halfspace_box_open(fn, &p, any, nh))) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));   // kernels of the old planes are done before they change
+  if ((rc = upload_halfspace(h, mem, a, b))) return rc;
+  h->hs_any = any;
+  return io.finish();
+}
+
+int admm_set_halfspace(admm_handle* h, const double* a, const double* b) { return set_halfspace_common(h, a, b, Mem::Host, nullptr); }
+int admm_set_halfspace_device(admm_handle* h, const double* a, const double* b, void* hip_stream) {
+  return set_halfspace_common(h, a, b, Mem::Device, hip_stream);
+}
+
+// the planes in force, in the caller's order (a[b][k][i], b[b][k]; one "QP" in the shared form)
+int admm_get_halfspace(admm_handle* h, double* a, double* b) {
+  if (!h || !a || !b) return fail(ADMM_ERR_INVALID, "NULL argument");
+  if (!h->hs_nh) return fail(ADMM_ERR_INVALID, "admm_get_halfspace: the handle has no half-spaces (set it up with admm_setup_halfspace)");
+  HIP_TRY(hipSetDevice(h->device));
+  int rc;
+  if (h->hs_perqp) {
+    if ((rc = download_transposed(h, Mem::Host, h->hs_a, a, h->N * h->hs_nh))) return rc;
+    return download_transposed(h, Mem::Host, h->hs_b, b, h->N);
+  }
+  HIP_TRY(hipMemcpyAsync(a, h->hs_a, sizeof(double) * (size_t)h->N * h->hs_nh, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(b, h->hs_b, sizeof(double) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return ADMM_OK;
+}
+
+// largest violation of a plane by w, the stages with a positive multiplier, and the multipliers (halfspace_report_kernel)
+static int halfspace_report_common(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_get_halfspace_report_device" : "admm_get_halfspace_report";
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (!max_violation && !n_active && !lam) return fail(ADMM_ERR_INVALID, std::string(fn) + ": at least one output must be given");
+  if (!h->hs_nh) return fail(ADMM_ERR_INVALID, std::string(fn) + ": the handle has no half-spaces (set it up with admm_setup_halfspace)");
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  int rc;
+  const size_t bsz = sizeof(double) * (size_t)h->batch, csz = sizeof(int32_t) * (size_t)h->batch;
+  if ((rc = io.check_ptr(max_violation, bsz, "max_violation")) ||
+      (rc = io.check_ptr(n_active, csz, "n_active", sizeof(int32_t), "int32 entries")) || (rc = io.check_ptr(lam, bsz * h->N, "lam")))
+    return rc;
+  if (!h->hs_out && (rc = dalloc(h, &h->hs_out, (size_t)h->pitch))) return rc;
+  if (!h->hs_cnt && (rc = dalloc(h, &h->hs_cnt, (size_t)h->pitch))) return rc;
+  if (lam && !h->hs_lam && (rc = dalloc(h, &h->hs_lam, (size_t)h->N * h->pitch, true))) return rc;
+  if ((rc = ensure_w(h)) || (rc = ensure_zy(h))) return rc;      // w of the last x-update; the state as the (z, y) pair
+  if ((rc = io.begin())) return rc;
+  admm::launch_halfspace_report(h->stream, h->w, h->y, h->hs_a, h->hs_b, h->hs_out, h->hs_cnt, lam ? h->hs_lam : nullptr, h->fac.rho,
+                                h->N, h->nb, h->m, h->hs_nh, h->pitch, h->batch, h->hs_perqp);
+  HIP_TRY(hipGetLastError());
+  if (max_violation && (rc = io.copy_out(max_violation, h->hs_out, bsz))) return rc;
+  if (n_active && (rc = io.copy_out(n_active, h->hs_cnt, csz))) return rc;
+  if (lam && (rc = download_transposed(h, mem, h->hs_lam, lam, h->N))) return rc;
+  return io.finish();
+}
+
+int admm_get_halfspace_report(admm_handle* h, double* max_violation, int32_t* n_active, double* lam) {
+  return halfspace_report_common(h, max_violation, n_active, lam, Mem::Host, nullptr);
+}
+int admm_get_halfspace_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream) {
+  return halfspace_report_common(h, max_violation, n_active, lam, Mem::Device, hip_stream);
 }
 
 // the control rows of each group's z, (ngroups, N, m): column g * G of the rows j < m of every block (consensus_gather_kernel)
@@ -1279,6 +1439,8 @@ static int infeasibility_common(admm_handle* h, int32_t span, double eps, double
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle");
   if (h->cons_G)
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a scenario-consensus handle (a per-QP Farkas certificate is not the coupled problem's)");
+  if (h->hs_nh)
+    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a handle with half-spaces (the Farkas certificate is written for boxes and the thrust ball)");
   if (h->opt.precision_mode == ADMM_PRECISION_MIXED)
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with precision_mode MIXED (the fp32 phase would put rounding "
                 "noise into the dual's difference)");

@@ -1,5 +1,6 @@
 // admm_hostio.hip -- solver runtime: host <-> device transfers, validation, uploads of a factor, handle lifetime (admm_runtime.hpp)
 #include "admm_runtime.hpp"
+#include "admm_halfspace.hpp"
 
 namespace admm {
 namespace rt {
@@ -629,6 +630,39 @@ int validate_soft(const admm_problem* p, const double* soft, bool expanded, cons
     for (int j = 0; j < p->m; ++j)
       if (soft[o + j] != INFINITY)
         return fail(ADMM_ERR_INVALID, "soft entries of the control rows must be +inf where unorm is finite or fuel is positive");
+  }
+  return ADMM_OK;
+}
+
+int halfspace_stages(const char* fn, const double* a, const double* b, int count, int N, int nh, std::vector<char>& any) {
+  if (!finite_all(a, (size_t)count * N * nh) || !finite_all(b, (size_t)count * N))
+    return fail(ADMM_ERR_INVALID, std::string(fn) + ": non-finite entry in a or b");
+  any.assign(N, 0);
+  for (size_t s = 0; s < (size_t)count * N; ++s) {
+    const double* as = a + s * nh;
+    double nn = 0.0;
+    bool nz = false;
+    for (int i = 0; i < nh; ++i) {
+      nn = std::fma(as[i], as[i], nn);
+      nz = nz || as[i] != 0.0;
+    }
+    if (!nz) continue;
+    if (!admm::halfspace_norm_ok(nn))
+      return fail(ADMM_ERR_INVALID, std::string(fn) + ": a'a of stage " + std::to_string(s % N) + " is not a normal number (scale the row)");
+    any[s % N] = 1;
+  }
+  return ADMM_OK;
+}
+
+int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh) {
+  const int nb = p->n + p->m;
+  for (int k = 0; k < p->N; ++k) {
+    if (!any[k]) continue;
+    const size_t o = (p->stage_bounds ? (size_t)k * nb : 0) + p->m;
+    for (int i = 0; i < nh; ++i)
+      if (p->lo[o + i] != -INFINITY || p->hi[o + i] != INFINITY)
+        return fail(ADMM_ERR_INVALID, std::string(fn) + ": state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with a half-space (stage " +
+                                          std::to_string(k) + ")");
   }
   return ADMM_OK;
 }

@@ -5,6 +5,7 @@
 #include "admm_infeas.hpp"
 #include "admm_select.hpp"
 #include "admm_soft.hpp"
+#include "admm_halfspace.hpp"
 
 namespace admm {
 
@@ -253,6 +254,12 @@ int launch_z(admm_handle* h, bool resid) {
   if (h->has_soft) {                             // soft box: the prox of weight dist(., [lo, hi]) per row (admm_soft_kernels.hpp)
     admm::launch_soft(admm::SoftLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->skap_d, h->ub, h->kap, h->part, h->opt.alpha, h->L,
                                        h->zrows, h->zchunks, h->pitch, h->nb, h->m, resid, h->has_soc});
+    return ADMM_OK;
+  }
+  if (h->hs_nh) {                                // one half-space per stage on the first state rows (admm_halfspace_kernels.hpp)
+    admm::launch_halfspace(admm::HalfspaceLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->hs_a, h->hs_b, h->part,
+                                                 h->opt.alpha, h->L, h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->hs_nh, resid,
+                                                 h->has_soc, h->hs_perqp});
     return ADMM_OK;
   }
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, h->zchunks), block(Z_THREADS);

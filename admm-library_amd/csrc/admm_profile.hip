@@ -16,6 +16,8 @@ int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused
     return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a scenario-consensus handle runs the unfused path only (fused_path = 0)");
   if (h->has_soft && fused_path != 0)
     return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a handle with soft weights runs the unfused path only (fused_path = 0)");
+  if (h->hs_nh && fused_path != 0)
+    return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a handle with half-spaces runs the unfused path only (fused_path = 0)");
   h->xfree_mode = 1;
   drop_side_data(h);                          // modes 0 .. 3 time the full-read / full-write forms; none leaves side data
   HIP_TRY(hipSetDevice(h->device));

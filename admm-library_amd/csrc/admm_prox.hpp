@@ -72,6 +72,30 @@ ADMM_PROX_FN double soft_clip(double v, double lo, double hi, double kap) {
   return fabs(e) <= kap ? c : (e > 0.0 ? v - kap : v + kap);
 }
 
+// Half-space of a stage: the Euclidean projection of the nh rows v onto  a'z <= b.
+//     nn = a'a and d = a'v - b as fma chains in row order (d starts at -b),  t = d > 0 ? d / nn : 0,  z_i = fma(-t, a_i, v_i)
+// nn == 0 (a = 0) is a stage without a half-space: its rows take their box, and nothing below is evaluated for it.  The chains
+// are written where the rows are loaded (halfspace_acc per row); the step and the row are these two functions.  Independent
+// of rho: the prox of an indicator.
+ADMM_PROX_FN void halfspace_acc(double a, double v, double& nn, double& d) {
+  nn = fma(a, a, nn);
+  d = fma(a, v, d);
+}
+ADMM_PROX_FN double halfspace_step(double d, double nn) { return d > 0.0 ? d / nn : 0.0; }
+ADMM_PROX_FN double halfspace_row(double t, double a, double v) { return fma(-t, a, v); }
+// one stage on the host (tests) and wherever the rows sit in an array: z, y of the nh rows; false = the stage is inactive
+ADMM_PROX_FN bool halfspace_project(const double* a, double b, int nh, const double* v, double* z, double* y) {
+  double nn = 0.0, d = -b;
+  for (int i = 0; i < nh; ++i) halfspace_acc(a[i], v[i], nn, d);
+  if (nn == 0.0) return false;
+  const double t = halfspace_step(d, nn);
+  for (int i = 0; i < nh; ++i) {
+    z[i] = halfspace_row(t, a[i], v[i]);
+    y[i] = v[i] - z[i];
+  }
+  return true;
+}
+
 // the relaxed x-update output w^ from w and the old z
 template <bool RELAX>
 ADMM_PROX_FN double relaxed(double alpha, double w, double zo) {

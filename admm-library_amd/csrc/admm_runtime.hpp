@@ -68,6 +68,16 @@ struct admm_handle {
   std::vector<double> soft;      // [L]
   double *soft_d = nullptr, *skap_d = nullptr, *soft_out = nullptr;      // [L], [L], [2][pitch] penalty | max violation
   int* soft_cnt = nullptr;       // [pitch] violated rows
+  // one half-space per stage (admm_setup_halfspace): a' xi <= b on the first hs_nh state rows of a block.  The planes
+  // live on the device only -- shared [N][nh] | [N], or per QP batch-minor [N][nh][pitch] | [N][pitch] --, at addresses that never
+  // change (captured graphs hold them); the host keeps which stages have a plane for some QP (the open-box rule).  The report's
+  // results and the scan's flags are allocated on first use.
+  int hs_nh = 0;                 // 0 = a handle without half-spaces
+  bool hs_perqp = false;
+  double *hs_a = nullptr, *hs_b = nullptr;
+  std::vector<char> hs_any;      // [N] some QP has a plane at the stage
+  double *hs_out = nullptr, *hs_lam = nullptr;     // [pitch] max violation; [N][pitch] multipliers
+  int *hs_cnt = nullptr, *hs_flags = nullptr;      // [pitch] active stages; [2][N] findings of halfspace_scan_kernel
   admm_options opt{};
   admm::Factor fac;
   // host copy of the shared problem data (the caller's pointers are never kept): admm_set_rho refactors from it
@@ -421,6 +431,11 @@ int upload_kappa(admm_handle* h);
 // true: L entries (a handle's own copy).  fuel: N per-stage weights or NULL.
 int validate_soft(const admm_problem* p, const double* soft, bool expanded, const double* fuel);
 inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fuel.data() : nullptr; }
+// half-spaces against a validated problem.  halfspace_stages: a, b as the caller gives them (a[b][k][i], b[b][k]; one "QP" in the
+// shared form) must be finite and every a_k'a_k of a stage with a plane a normal number; any[k] = some QP has a plane at stage k.
+// halfspace_box_open: the state rows 0 .. nh - 1 of every stage in `any` have the box (-inf, inf) in p (a batch-shared box).
+int halfspace_stages(const char* fn, const double* a, const double* b, int count, int N, int nh, std::vector<char>& any);
+int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh);
 
 // ---- per-instance dynamics (admm_pinst_rt.hip)
 int pinst_factor(admm_handle* h, bool only_marked = false);

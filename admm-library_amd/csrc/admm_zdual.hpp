@@ -1,5 +1,6 @@
 // admm_zdual.hpp -- the standalone z-update and read-out kernels: zdual_kernel, zdual_soc_kernel,
-// v_to_zy_kernel, v_to_zy_soc_kernel, and the walk that zdual_soft_kernel (admm_soft_kernels.hpp) shares with them.  Part of
+// v_to_zy_kernel, v_to_zy_soc_kernel, and the walks that zdual_soft_kernel (admm_soft_kernels.hpp) and zdual_halfspace_kernel
+// (admm_halfspace_kernels.hpp) share with them.  Part of
 // admm_kernels.hpp, which includes it inside namespace admm after the declarations it uses (Z_THREADS, cdouble_p, as_const).
 //
 // A kernel here is a WALK over the rows of a chunk, a SOURCE that says what a row is loaded from, and a PROX that says which
@@ -14,6 +15,8 @@
 //                            (zdual_kernel itself reads the same but keeps a walk of its own: see there)
 //            VSource         v itself (read-out and mode switches of the v-form, §4.4); no sums
 //   proxes   BoxProx         clip to [lo[r], hi[r]]; SoftBoxProx (admm_soft_kernels.hpp) is the other one
+//   planes   NoPlane         z_walk_blocks only: a constraint that couples state rows of a stage; HalfspacePlane
+//                            (admm_halfspace_kernels.hpp) is the one there is
 //
 // The row index is wave-uniform, so the bounds of a row are scalar loads through the constant address space and the per-QP sums
 // need no cross-lane step at all: each lane owns its QPs' accumulators.  Pad columns (batch .. pitch - 1) are computed like any
@@ -132,33 +135,71 @@ __device__ __forceinline__ void z_walk_rows(const Source& src, const Prox& prox,
   if (Source::Row::resid) store_sums2(part + (size_t)blockIdx.y * 5 * c.P + c.col, c.P, acc);
 }
 
-template <class Source, class Prox>
+// A constraint on the state rows of a stage, carried by z_walk_blocks beside the thrust ball of its control rows.  NoPlane: none
+// (the walk of zdual_soc_kernel, v_to_zy_soc_kernel, zdual_soft_kernel as it was); the other one is HalfspacePlane
+// (admm_halfspace_kernels.hpp).  A plane says, per block,
+//     Step step(src, k, rb, c)      what it needs from the block's rows before they are applied (a second read, as the norm's)
+//     bool covers(step, r)          wave-uniform: row r of the block may be the plane's
+//     ZY2 row(step, v, r, box, P)   (z, y) of such a row; box = the row's own prox, for the QPs whose stage has no plane
+// and `soc` whether the walk reads ub / kap at all.
+struct NoPlane {
+  static constexpr bool enabled = false, soc = true;
+};
+
+template <class Source, class Prox, class Plane = NoPlane>
 __device__ __forceinline__ void z_walk_blocks(const Source& src, const Prox& prox, double* z, double* y, const double* ub_,
-                                              const double* kap_, double* part, int L, int zrows, int pitch, int nb, int m) {
+                                              const double* kap_, double* part, int L, int zrows, int pitch, int nb, int m,
+                                              const Plane& plane = Plane{}) {
   const ZChunk c(L, zrows, pitch);
   if (c.col >= pitch) return;
   cdouble_p ubv = as_const(ub_);
   cdouble_p kapv = as_const(kap_);
   ResidSums acc[2];
   for (int rb = c.r_begin; rb < c.r_end; rb += nb) {
-    const double ub = ubv[rb / nb], kap = kapv[rb / nb];
-    const bool soc = ub < INFINITY || kap > 0.0;      // a finite thrust bound or a fuel weight (else the control rows use their prox)
+    bool soc = false;
     double2 cs = {1.0, 1.0};
-    if (soc) {
-      double2 ss = {0.0, 0.0};
-      for (int j = 0; j < m; ++j) {
-        const double2 vn = src.v(src.load((size_t)(rb + j) * c.P + c.col));
-        ss.x = fma(vn.x, vn.x, ss.x);
-        ss.y = fma(vn.y, vn.y, ss.y);
+    if constexpr (Plane::soc) {
+      const double ub = ubv[rb / nb], kap = kapv[rb / nb];
+      soc = ub < INFINITY || kap > 0.0;               // a finite thrust bound or a fuel weight (else the control rows use their prox)
+      if (soc) {
+        double2 ss = {0.0, 0.0};
+        for (int j = 0; j < m; ++j) {
+          const double2 vn = src.v(src.load((size_t)(rb + j) * c.P + c.col));
+          ss.x = fma(vn.x, vn.x, ss.x);
+          ss.y = fma(vn.y, vn.y, ss.y);
+        }
+        cs = soc_scale2(ss, ub, kap);
       }
-      cs = soc_scale2(ss, ub, kap);
     }
-    for (int r = 0; r < nb; ++r) {
-      const int row_i = rb + r;
-      const size_t o = (size_t)row_i * c.P + c.col;
-      const typename Source::Row row = src.load(o);
-      const double2 v = src.v(row);
-      z_row_store(row, soc && r < m ? zy2_scaled(v, cs) : prox(v, row_i), z + o, y + o, acc);
+    if constexpr (Plane::enabled) {
+      // (ADMM_Z_UNROLL rows of the block in flight, as z_walk_rows: a workgroup per CU is one wave per SIMD, and a row at a time
+      //  leaves it waiting on every load)
+      const auto step = plane.step(src, rb / nb, rb, c);
+      auto apply = [&](const typename Source::Row& row, int r) {
+        const int row_i = rb + r;
+        const size_t o = (size_t)row_i * c.P + c.col;
+        const double2 v = src.v(row);
+        z_row_store(row, soc && r < m ? zy2_scaled(v, cs) : plane.covers(step, r) ? plane.row(step, v, r, prox(v, row_i), c.P) : prox(v, row_i),
+                    z + o, y + o, acc);
+      };
+      constexpr int U = ADMM_Z_UNROLL;
+      int r = 0;
+      for (; r + U <= nb; r += U) {
+        typename Source::Row row[U];
+#pragma unroll
+        for (int i = 0; i < U; ++i) row[i] = src.load((size_t)(rb + r + i) * c.P + c.col);
+#pragma unroll
+        for (int i = 0; i < U; ++i) apply(row[i], r + i);
+      }
+      for (; r < nb; ++r) apply(src.load((size_t)(rb + r) * c.P + c.col), r);
+    } else {
+      for (int r = 0; r < nb; ++r) {
+        const int row_i = rb + r;
+        const size_t o = (size_t)row_i * c.P + c.col;
+        const typename Source::Row row = src.load(o);
+        const double2 v = src.v(row);
+        z_row_store(row, soc && r < m ? zy2_scaled(v, cs) : prox(v, row_i), z + o, y + o, acc);
+      }
     }
   }
   if (Source::Row::resid) store_sums2(part + (size_t)blockIdx.y * 5 * c.P + c.col, c.P, acc);

@@ -51,6 +51,12 @@ class Problem:
     # sum_rows s_i max(lo_i - w_i, 0, w_i - hi_i) and the row's box is no longer enforced absolutely.  +inf = a hard row, 0 = its box is
     # ignored.  None = every row hard.  +inf on the control rows where unorm is finite or fuel positive.  Batch-shared dynamics only.
     soft: Optional[np.ndarray] = None
+    # one half-space per stage:  hs_a[k] . xi_k <= hs_b[k]  on xi_k, the first nh state rows of block k.  hs_a is
+    # (N, nh) with hs_b (N,) -- shared by the batch -- or (batch, N, nh) with (batch, N) -- one set per QP; nh = hs_a.shape[-1],
+    # 1 <= nh <= n.  hs_a[k] = 0 exactly: no half-space at that stage.  Where a stage has one for any QP, state rows 0 .. nh - 1 of the
+    # stage must have the box (-inf, inf).  Both or neither; finite.  Batch-shared dynamics only; not with soft or consensus.
+    hs_a: Optional[np.ndarray] = None
+    hs_b: Optional[np.ndarray] = None
     # minimum-fuel cost  + sum_k fuel_k ||u_k||_2  (fuel >= 0: scalar, or (N,) when the box is per stage); None = off.
     # Where positive, the box of the control rows must be (-inf, inf).  Batch-shared dynamics only.
     fuel: Optional[np.ndarray] = None
@@ -97,6 +103,8 @@ class Problem:
             rep.update(A=np.ascontiguousarray(self.A[start:stop]), B=np.ascontiguousarray(self.B[start:stop]))
         if self.per_instance_bounds:
             rep.update(lo=np.ascontiguousarray(self.lo[start:stop]), hi=np.ascontiguousarray(self.hi[start:stop]))
+        if self.hs_a is not None and np.ndim(self.hs_a) == 3:
+            rep.update(hs_a=np.ascontiguousarray(self.hs_a[start:stop]), hs_b=np.ascontiguousarray(self.hs_b[start:stop]))
         return dataclasses.replace(self, **rep)
 
     def validate(self) -> None:
@@ -170,6 +178,11 @@ class Problem:
                 hard |= np.broadcast_to(np.asarray(self.fuel, np.float64), hard.shape) > 0
             if np.any(su[hard] != np.inf):
                 raise ValueError("soft must be inf on the control rows where unorm is finite or fuel is positive")
+        if (self.hs_a is None) != (self.hs_b is None):
+            raise ValueError("hs_a and hs_b must be given together")
+        if self.hs_a is not None and not hasattr(self.hs_a, "is_cuda"):
+            # (CUDA tensors: what Solver.set_halfspace left here after the device form; the library has checked them on the device)
+            check_halfspaces(self, self.hs_a, self.hs_b)
         if self.consensus is not None:
             G = int(self.consensus)
             if G != self.consensus or G < 1 or self.batch % G != 0:
@@ -182,6 +195,46 @@ class Problem:
             if a.nbytes <= (256 << 20) and not np.all(np.isfinite(a)):
                 raise ValueError("non-finite problem data")
 
+
+
+def halfspace_form(a, b, N: int, n: int, batch: int):
+    """(nh, per_qp) of half-space arrays by their shapes: (N, nh) with (N,), or (batch, N, nh) with (batch, N).  ValueError otherwise.
+    (With batch = 1 a 3-d array is the per-QP form.)"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.ndim == 2 and a.shape[0] == N and b.shape == (N,):
+        per_qp = False
+    elif a.ndim == 3 and a.shape[:2] == (batch, N) and b.shape == (batch, N):
+        per_qp = True
+    else:
+        raise ValueError(f"hs_a / hs_b must be (N, nh) with (N,), or (batch, N, nh) with (batch, N); got {a.shape} with {b.shape}")
+    nh = int(a.shape[-1])
+    if not 1 <= nh <= n:
+        raise ValueError(f"hs_a: nh = {nh} must lie in 1 .. n = {n}")
+    return nh, per_qp
+
+
+def check_halfspaces(p, a, b) -> None:
+    """The rules of Problem.hs_a / hs_b against the rest of p (ValueError): shapes, finite entries, a normal a.a where a != 0,
+    an open box on state rows 0 .. nh - 1 of every stage that has a half-space for some QP."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    nh, _ = halfspace_form(a, b, p.N, p.n, p.batch)
+    if p.per_instance or p.lo.ndim == 3:
+        raise ValueError("half-spaces need batch-shared dynamics and a batch-shared box (A, B LTI or LTV)")
+    if p.soft is not None or p.consensus is not None:
+        raise ValueError("half-spaces cannot be combined with soft or consensus")
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(b))):
+        raise ValueError("hs_a and hs_b must be finite")
+    a3 = a.reshape(-1, p.N, nh)
+    nz = np.any(a3 != 0, axis=2)
+    with np.errstate(over="ignore", under="ignore"):
+        nn = np.sum(a3 * a3, axis=2)
+    if np.any(nz & ~((nn >= np.finfo(np.float64).tiny) & np.isfinite(nn))):
+        raise ValueError("hs_a: a.a of a stage with a half-space must be a normal number (scale the row)")
+    active = np.any(nz, axis=0)                                            # (N,)
+    lo_x = np.broadcast_to(np.atleast_2d(p.lo), (p.N, p.nb))[:, p.m:p.m + nh]
+    hi_x = np.broadcast_to(np.atleast_2d(p.hi), (p.N, p.nb))[:, p.m:p.m + nh]
+    if np.any(lo_x[active] != -np.inf) or np.any(hi_x[active] != np.inf):
+        raise ValueError("state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with a half-space")
 
 
 @dataclasses.dataclass
@@ -204,7 +257,9 @@ class DeviceProblem:
     name: str = ""
     consensus: Optional[int] = None             # Problem's field; scenario consensus has no device-memory setup (Solver refuses it)
     soft: Optional["torch.Tensor"] = None       # Problem's field; soft constraints have no device-memory setup (Solver refuses it)
-    fuel: Optional["torch.Tensor"] = None       # Problem's field; the device entry points have no fuel term (Solver refuses it)
+    hs_a: Optional["torch.Tensor"] = None       # Problem's fields; half-spaces have no device-memory setup (Solver refuses it): the
+    hs_b: Optional["torch.Tensor"] = None       # device-memory route is Solver.set_halfspace with CUDA tensors
+    fuel: Optional["torch.Tensor"] = None      # Problem's field; the device entry points have no fuel term (Solver refuses it)
 
     n = Problem.n
     m = Problem.m
@@ -229,7 +284,7 @@ class DeviceProblem:
         return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
                    unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name,
                    fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)), consensus=p.consensus,
-                   soft=None if p.soft is None else t(np.asarray(p.soft, np.float64)))
+                   soft=None if p.soft is None else t(np.asarray(p.soft, np.float64)), hs_a=t(p.hs_a), hs_b=t(p.hs_b))
 
     def validate(self) -> None:
         """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
@@ -241,7 +296,10 @@ class DeviceProblem:
             raise ValueError("consensus: scenario consensus has no device-memory setup: give a Problem with NumPy arrays")
         if self.soft is not None:
             raise ValueError("soft: soft constraints have no device-memory setup: give a Problem with NumPy arrays")
-        dev = self.x0.device if torch.is_tensor(self.x0) else None
+        if self.hs_a is not None or self.hs_b is not None:
+            raise ValueError("hs_a / hs_b: half-spaces have no device-memory setup: give a Problem with NumPy arrays "
+                             "(Solver.set_halfspace takes CUDA tensors)")
+        dev =self.x0.device if torch.is_tensor(self.x0) else None
         for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
             a = getattr(self, name)
             if a is None and name in ("q", "unorm"):
@@ -382,6 +440,61 @@ def cw_rendezvous_fuel(N: int = 1000, batch: int = 1, seed0: int = SEED0, u_max:
     p = cw_rendezvous(N=N, batch=batch, seed0=seed0, u_max=u_max, thrust_norm=True)
     f = 2.0 * np.pi / N if fuel is None else float(fuel)
     return dataclasses.replace(p, fuel=np.float64(f), name=f"cw_rendezvous_fuel_N{N}_b{batch}")
+
+
+def keepout_halfspaces(X, radius, centre=0.0):
+    """Tangent half-spaces of the keep-out sphere |r - c| >= R about positions X of shape (batch, N, 3) (or (N, 3)): with
+    n_k = (X_k - c) / |X_k - c| the convexification  n_k . (r_{k+1} - c) >= R  reads  a_k . r <= b_k  with
+    a = -n,  b = -(R + n . c)  (DESIGN.md §2.14).  Returns (a, b), shapes X.shape and X.shape[:-1]; a stage whose X_k sits on the
+    centre has no direction and gets a = 0, b = 0: no half-space.  radius: a scalar, or one per QP."""
+    X = np.asarray(X, np.float64)
+    c = np.broadcast_to(np.asarray(centre, np.float64), X.shape)
+    d = X - c
+    nrm = np.sqrt(np.sum(d * d, axis=-1))
+    ok = nrm > 0
+    nhat = np.where(ok[..., None], d / np.where(ok, nrm, 1.0)[..., None], 0.0)
+    R = np.asarray(radius, np.float64)
+    if R.ndim == 1:
+        R = R[:, None]
+    b = np.where(ok, -(R + np.sum(nhat * c, axis=-1)), 0.0)
+    return -nhat, b
+
+
+def lqr_rollout(p: Problem) -> np.ndarray:
+    """(batch, N, n): the states x_1 .. x_N of p's QPs without box, planes or q -- the finite-horizon LQR trajectory of
+    (A, B, Q, R, QN) from x0, by the Riccati recursion (batch-shared LTI or LTV dynamics)."""
+    N, n = p.N, p.n
+    Ak = lambda k: p.A[k] if p.A.ndim == 3 else p.A
+    Bk = lambda k: p.B[k] if p.B.ndim == 3 else p.B
+    P = p.QN.copy()
+    K = [None] * N
+    for k in range(N - 1, -1, -1):
+        A, B = Ak(k), Bk(k)
+        K[k] = np.linalg.solve(p.R + B.T @ P @ B, B.T @ P @ A)
+        Acl = A - B @ K[k]
+        P = (p.Q if k > 0 else np.zeros((n, n))) + Acl.T @ P @ Acl + K[k].T @ p.R @ K[k]
+    X = np.empty((p.batch, N, n))
+    x = np.asarray(p.x0, np.float64)
+    for k in range(N):
+        x = x @ (Ak(k) - Bk(k) @ K[k]).T
+        X[:, k] = x
+    return X
+
+
+def cw_keepout(N: int = 40, batch: int = 6, radius: Optional[float] = None, free_tail: int = 5, thrust_norm: bool = False,
+               fuel: Optional[float] = None, seed0: int = SEED0) -> Problem:
+    """cw_rendezvous with a keep-out sphere of `radius` about the target, convexified as one tangent half-space per stage and QP
+    (DESIGN.md §2.14): the planes of keepout_halfspaces about the QPs' unconstrained trajectory (lqr_rollout), which runs straight
+    through the target.  The last `free_tail` stages carry no plane (the final approach).  radius = None: half the smallest initial
+    range of the batch.  thrust_norm / fuel: the thrust ball instead of the input box, and the minimum-fuel term on top of it."""
+    p = cw_rendezvous(N=N, batch=batch, seed0=seed0, thrust_norm=thrust_norm or fuel is not None)
+    R = 0.5 * float(np.sqrt(np.sum(p.x0[:, :3] ** 2, axis=1)).min()) if radius is None else float(radius)
+    a, b = keepout_halfspaces(lqr_rollout(p)[:, :, :3], R)
+    if free_tail > 0:
+        a[:, N - free_tail:] = 0.0
+        b[:, N - free_tail:] = 0.0
+    return dataclasses.replace(p, hs_a=a, hs_b=b, fuel=None if fuel is None else np.float64(fuel),
+                               name=f"cw_keepout_N{N}_b{batch}")
 
 
 def cw_rendezvous_scenarios(N: int = 1000, groups: int = 1, group_size: int = 8, spread: float = 0.05, seed0: int = SEED0,

@@ -96,6 +96,14 @@ _SIGNATURES = {
     "admm_get_soft": (C.c_int, [C.c_void_p, c_double_p]),
     "admm_get_soft_report": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p]),
     "admm_get_soft_report_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p, C.c_void_p]),
+    # one half-space per stage (ADMM_HIP_HAS_HALFSPACE): a linear inequality on the first nh state rows of every block
+    "admm_setup_halfspace": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p, c_double_p, c_double_p,
+                                      C.c_int32, C.c_int32]),
+    "admm_set_halfspace": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "admm_set_halfspace_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_get_halfspace": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
+    "admm_get_halfspace_report": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p]),
+    "admm_get_halfspace_report_device": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p, C.c_void_p]),
     # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
     "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
     "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
@@ -283,6 +291,17 @@ class SoftReport:
     n_violated: object
 
 
+@dataclasses.dataclass
+class HalfspaceReport:
+    """Solver.halfspace_report(): per QP, max_violation = max_k (a_k . w_xi - b_k)+ / |a_k| on w of the last
+    x-update, n_active = stages with a positive multiplier (int32), and with multipliers=True lam (batch, N) = rho (a_k . y_xi) /
+    a_k . a_k, the multiplier of the stage's inequality (0 where the stage has no half-space).  NumPy arrays, or CUDA tensors with
+    device=True."""
+    max_violation: object
+    n_active: object
+    lam: object = None
+
+
 class Solver:
     """One handle = one batch of QPs on one GPU.
 
@@ -319,7 +338,14 @@ class Solver:
             _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
         elif timeshard is None:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
-            if problem.soft is not None:         # (validate() has refused soft together with consensus)
+            if problem.hs_a is not None:         # (validate() has refused half-spaces together with soft or consensus)
+                keep["hs_a"], keep["hs_b"], nh, per_qp = _abi.marshal_halfspace(problem)
+                if problem.fuel is not None:
+                    keep["fuel"] = _abi.marshal_fuel(problem)
+                _check(self._lib, self._lib.admm_setup_halfspace(C.byref(self._h), C.byref(cp), C.byref(co),
+                                                                 dptr(keep["fuel"]) if "fuel" in keep else c_double_p(),
+                                                                 dptr(keep["hs_a"]), dptr(keep["hs_b"]), nh, int(per_qp)))
+            elif problem.soft is not None:       # (validate() has refused soft together with consensus)
                 keep["soft"] = _abi.marshal_soft(problem)
                 if problem.fuel is not None:
                     keep["fuel"] = _abi.marshal_fuel(problem)
@@ -344,6 +370,8 @@ class Solver:
                 raise AdmmError(2, "scenario consensus is not supported on time-sharded handles")
             if problem.soft is not None:
                 raise ValueError("soft constraints are not supported on time-sharded handles")
+            if problem.hs_a is not None:
+                raise ValueError("half-spaces are not supported on time-sharded handles")
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -428,6 +456,8 @@ class Solver:
                 problem = self._keep_fuel(problem)
             if problem.soft is not None or getattr(self.problem, "soft", None) is not None:
                 problem = self._keep_soft(problem)
+            if problem.hs_a is not None or getattr(self.problem, "hs_a", None) is not None:
+                problem = self._keep_halfspace(problem)
             cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
             t0 = time.perf_counter()
             _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
@@ -511,6 +541,75 @@ class Solver:
         pen, mx, cnt = np.empty(self.batch), np.empty(self.batch), np.empty(self.batch, np.int32)
         _check(self._lib, self._lib.admm_get_soft_report(self._h, dptr(pen), dptr(mx), iptr(cnt)))
         return SoftReport(pen, mx, cnt)
+
+    def _keep_halfspace(self, problem):
+        """update_problem on a handle with half-spaces: the handle's planes stay in force (admm_update_problem); the problem that
+        becomes self.problem carries them, and the new box is validated against them."""
+        if getattr(self.problem, "hs_a", None) is None:
+            raise ValueError("half-spaces cannot be added to a handle: set up a new Solver")
+        a, b = self.halfspace()
+        if problem.hs_a is not None and not (np.array_equal(np.asarray(problem.hs_a, np.float64), a) and
+                                             np.array_equal(np.asarray(problem.hs_b, np.float64), b)):
+            raise ValueError("update_problem keeps the handle's half-spaces: change them with set_halfspace")
+        return dataclasses.replace(problem, hs_a=a, hs_b=b)
+
+    def _hs_form(self):
+        """(nh, per_qp) of the handle's half-spaces; AdmmError on a handle without."""
+        if getattr(self.problem, "hs_a", None) is None:
+            raise AdmmError(1, "the handle has no half-spaces (set Problem.hs_a / hs_b)")
+        return tuple(self.problem.hs_a.shape)[-1], len(self.problem.hs_a.shape) == 3
+
+    def set_halfspace(self, a, b):
+        """New planes a . xi <= b (the form and nh of Problem.hs_a / hs_b) on a handle set up with them -- the re-linearisation
+        step of a keep-out loop; the state is kept as a warm start (admm_set_halfspace).  NumPy arrays, or CUDA tensors on the
+        handle's GPU (admm_set_halfspace_device, ordered on torch's current stream; self.problem then keeps the tensors).  A
+        refused call changes nothing."""
+        nh, per_qp = self._hs_form()
+        N = self.problem.N
+        sa, sb = ((self.batch, N, nh), (self.batch, N)) if per_qp else ((N, nh), (N,))
+        if _on_gpu(a) or _on_gpu(b):
+            dev = f"cuda:{self._device()}"
+            check_device_tensor("a", a, dev, sa)
+            check_device_tensor("b", b, dev, sb)
+            _check(self._lib, self._lib.admm_set_halfspace_device(self._h, _tptr(a), _tptr(b), _stream(dev)))
+            self.problem = dataclasses.replace(self.problem, hs_a=a, hs_b=b)
+            return
+        a, b = np.ascontiguousarray(a, np.float64), np.ascontiguousarray(b, np.float64)
+        if a.shape != sa or b.shape != sb:
+            raise ValueError(f"set_halfspace keeps the handle's form: expected shapes {sa} and {sb}, got {a.shape} and {b.shape}")
+        cand = dataclasses.replace(self.problem, hs_a=a, hs_b=b)
+        cand.validate()
+        _check(self._lib, self._lib.admm_set_halfspace(self._h, dptr(a), dptr(b)))
+        self.problem = cand
+        self._warn()
+
+    def halfspace(self):
+        """(a, b): the planes in force, in the shapes of Problem.hs_a / hs_b (admm_get_halfspace)."""
+        nh, per_qp = self._hs_form()
+        N = self.problem.N
+        a = np.empty((self.batch, N, nh) if per_qp else (N, nh))
+        b = np.empty((self.batch, N) if per_qp else (N,))
+        _check(self._lib, self._lib.admm_get_halfspace(self._h, dptr(a), dptr(b)))
+        return a, b
+
+    def halfspace_report(self, multipliers: bool = False, device: bool = False) -> HalfspaceReport:
+        """admm_get_halfspace_report: per QP the largest violation of a plane by w, the number of stages with a positive
+        multiplier and, with multipliers=True, the multipliers (batch, N), computed on the device.  device=True returns CUDA
+        tensors through admm_get_halfspace_report_device, ordered on torch's current stream."""
+        N = self.problem.N
+        if device:
+            import torch
+            dev = f"cuda:{self._device()}"
+            mx = torch.empty(self.batch, dtype=torch.float64, device=dev)
+            cnt = torch.empty(self.batch, dtype=torch.int32, device=dev)
+            lam = torch.empty((self.batch, N), dtype=torch.float64, device=dev) if multipliers else None
+            _check(self._lib, self._lib.admm_get_halfspace_report_device(self._h, _tptr(mx), C.cast(C.c_void_p(cnt.data_ptr()), c_int32_p),
+                                                                        _tptr(lam), _stream(dev)))
+            return HalfspaceReport(mx, cnt, lam)
+        mx, cnt = np.empty(self.batch), np.empty(self.batch, np.int32)
+        lam = np.empty((self.batch, N)) if multipliers else None
+        _check(self._lib, self._lib.admm_get_halfspace_report(self._h, dptr(mx), iptr(cnt), dptr(lam)))
+        return HalfspaceReport(mx, cnt, lam)
 
     def set_rho(self, rho: float):
         _check(self._lib, self._lib.admm_set_rho(self._h, float(rho)))

@@ -302,6 +302,51 @@ int admm_get_soft(admm_handle* h, double* soft);
 int admm_get_soft_report(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated);
 int admm_get_soft_report_device(admm_handle* h, double* penalty, double* max_violation, int32_t* n_violated, void* hip_stream);
 
+/* One half-space per stage (new symbols, announced by ADMM_HIP_HAS_HALFSPACE -- no struct or signature changed,
+ * ABI version unchanged): stage k constrains xi_k, the first nh state rows of block k = (u_k, x_{k+1}), 1 <= nh <= n, by
+ *
+ *     a_k' xi_k <= b_k
+ *
+ * -- the tangent plane of a keep-out sphere, re-linearised about the last trajectory by the caller.  a, b are C order, a[b][k][i]
+ * and b[b][k]: shared by the batch (per_instance = 0: N nh and N doubles) or one set per QP (per_instance != 0: batch N nh and
+ * batch N).  a_k = 0 exactly: the stage has no half-space and its rows keep their box.  Where a stage has a plane for any QP, state
+ * rows 0 .. nh - 1 of that stage must have the box (-inf, inf) (with stage_bounds = 0: of the one block); a, b must be finite and
+ * a_k'a_k of a stage with a plane a normal number.  Only the z-update changes: with v = w^ + y on those rows,
+ *     nn = a'a, d = a'v - b (fma chains in row order), t = d > 0 ? d / nn : 0, z_i = fma(-t, a_i, v_i), y_i = v_i - z_i,
+ * the Euclidean projection, independent of rho.  The other state rows and the control rows keep what they have (box, ball, fuel).
+ *
+ * admm_setup_halfspace: admm_setup_fuel (fuel may be NULL) with the planes.  ADMM_ERR_INVALID: nh out of range, NULL a or b, a
+ *   non-finite entry, a closed box under a plane.  ADMM_ERR_UNSUPPORTED: time_varying = 2, precision_mode other than
+ *   ADMM_PRECISION_FP64.  (Time-sharded, consensus and soft forms cannot be asked for: none of those set-up calls takes planes.)
+ *   Refused before a device is looked for, nothing allocated.  The handle runs the unfused one-lane fp64 path (ADMM_FLAG_UNFUSED is
+ *   set internally); the state is always the (z, y) pair.  Everything else works as on a soft handle -- admm_solve*, admm_run /
+ *   admm_iterate, admm_step_z, the adaptive rule and admm_set_rho, q, over-relaxation, admm_update_instances*, admm_set_state* /
+ *   admm_get*, admm_set_fuel, admm_get_certificate* (none of its quantities involves the constraint set), ADMM_FLAG_GRAPH (the
+ *   planes keep their device addresses across admm_set_halfspace*), admm_profile with fused_path = 0.  admm_update_problem* keeps
+ *   the planes and re-checks the open-box rule against the new box.  ADMM_ERR_UNSUPPORTED on such a handle: admm_mpc_advance* (a
+ *   per-QP plane is not window-relative), admm_probe_infeasibility* (its certificate is written for boxes and the ball),
+ *   admm_profile with fused_path != 0.
+ * admm_set_halfspace: replace a, b (same form, same nh) between iterations; the state is kept as a warm start.  Every check comes
+ *   first: a refused call changes nothing.  ADMM_ERR_INVALID on a handle set up without half-spaces.
+ * admm_set_halfspace_device: a, b are device memory of the handle's GPU, under the rules of admm_set_state_device; the per-QP
+ *   arrays are checked on the device.
+ * admm_get_halfspace: the planes in force, in the caller's order and form.
+ * admm_get_halfspace_report: per QP (batch entries; any pointer may be NULL, not all):
+ *     max_violation = max_k (a_k' w_xi - b_k)+ / sqrt(a_k'a_k)  on w, the dynamics-feasible iterate of the last x-update
+ *     n_active      = number of stages with lam_k > 0
+ *     lam[b][k]     = rho (a_k' y_xi) / a_k'a_k  (batch N doubles), the multiplier of the stage's inequality: the sensitivity of
+ *                     the cost to b_k -- for a keep-out plane, to the radius.  0 at a stage without a plane.
+ * admm_get_halfspace_report_device: the outputs are device memory of the handle's GPU, under the rules of
+ *   admm_get_certificate_device (n_active: 4-byte alignment). */
+#define ADMM_HIP_HAS_HALFSPACE 1
+int admm_setup_halfspace(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel,
+                         const double* a, const double* b, int32_t nh, int32_t per_instance);
+int admm_set_halfspace(admm_handle* h, const double* a, const double* b);
+int admm_set_halfspace_device(admm_handle* h, const double* a, const double* b, void* hip_stream);
+int admm_get_halfspace(admm_handle* h, double* a, double* b);
+int admm_get_halfspace_report(admm_handle* h, double* max_violation, int32_t* n_active, double* lam);
+int admm_get_halfspace_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream);
+
 /* Warm start / test hook: overwrite device state.  Any pointer may be NULL
  * (left unchanged).  Each is L*batch and must be finite (ADMM_ERR_INVALID otherwise, nothing uploaded). */
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y);
