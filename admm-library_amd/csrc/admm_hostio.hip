@@ -522,7 +522,7 @@ int upload_factor(admm_handle* h, const char* when) {
       HIP_TRY(hipMemcpy(h->recMB64, h->fac.recMB64.data(), h->fac.recMB64.size(), hipMemcpyHostToDevice));
     }
   }
-  if ((h->has_fuel || h->has_soft) && (rc = upload_kappa(h))) return rc;   // kappa = weight / rho follows every refactor
+  if ((h->has_fuel || h->zkind == ZKind::Soft) && (rc = upload_kappa(h))) return rc;   // kappa = weight / rho follows every refactor
   if (h->alt_allowed) {
     // (the refactored records go into the allocation of admm_setup: its slack stays zero, and still covers them)
     const std::string who(when);
@@ -565,7 +565,7 @@ int upload_kappa(admm_handle* h) {
     for (int k = 0; k < h->N; ++k) kap[k] = h->fuel[k] / h->fac.rho;
   HIP_TRY(hipMemcpyAsync(h->kap, kap.data(), sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
   std::vector<double> skap;                   // soft box: weight / rho per stacked row, an IEEE division (inf / rho = inf, 0 / rho = 0)
-  if (h->has_soft) {
+  if (h->zkind == ZKind::Soft) {
     skap.resize(h->L);
     for (int e = 0; e < h->L; ++e) skap[e] = h->soft[e] / h->fac.rho;
     HIP_TRY(hipMemcpyAsync(h->skap_d, skap.data(), sizeof(double) * h->L, hipMemcpyHostToDevice, h->stream));

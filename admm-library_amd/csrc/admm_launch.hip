@@ -246,21 +246,21 @@ int ensure_zy(admm_handle* h) {
 }
 
 int launch_z(admm_handle* h, bool resid) {
-  if (h->cons_G) {                               // scenario consensus: the control rows are projected once per group
-    admm::launch_consensus(admm::ConsLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L,
-                                            h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->cons_G, h->batch, resid});
-    return ADMM_OK;
-  }
-  if (h->has_soft) {                             // soft box: the prox of weight dist(., [lo, hi]) per row (admm_soft_kernels.hpp)
-    admm::launch_soft(admm::SoftLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->skap_d, h->ub, h->kap, h->part, h->opt.alpha, h->L,
-                                       h->zrows, h->zchunks, h->pitch, h->nb, h->m, resid, h->has_soc});
-    return ADMM_OK;
-  }
-  if (h->hs_nh) {                                // one half-space per stage on the first state rows (admm_halfspace_kernels.hpp)
-    admm::launch_halfspace(admm::HalfspaceLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->hs_a, h->hs_b, h->part,
-                                                 h->opt.alpha, h->L, h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->hs_nh, resid,
-                                                 h->has_soc, h->hs_perqp});
-    return ADMM_OK;
+  switch (h->zkind) {
+    case ZKind::Consensus:                       // the control rows are projected once per group (admm_consensus_kernels.hpp)
+      admm::launch_consensus(admm::ConsLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->part, h->opt.alpha, h->L,
+                                              h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->cons_G, h->batch, resid});
+      return ADMM_OK;
+    case ZKind::Soft:                            // the prox of weight dist(., [lo, hi]) per row (admm_soft_kernels.hpp)
+      admm::launch_soft(admm::SoftLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->skap_d, h->ub, h->kap, h->part, h->opt.alpha, h->L,
+                                         h->zrows, h->zchunks, h->pitch, h->nb, h->m, resid, h->has_soc});
+      return ADMM_OK;
+    case ZKind::Halfspace:                       // one half-space per stage on the first state rows (admm_halfspace_kernels.hpp)
+      admm::launch_halfspace(admm::HalfspaceLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->hs_a, h->hs_b, h->part,
+                                                   h->opt.alpha, h->L, h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->hs_nh, resid,
+                                                   h->has_soc, h->hs_perqp});
+      return ADMM_OK;
+    case ZKind::Box: break;                      // the per-QP box / thrust-ball prox below
   }
   dim3 grid((h->pitch / 2 + Z_THREADS - 1) / Z_THREADS, h->zchunks), block(Z_THREADS);
   const bool relax = h->opt.alpha != 1.0;

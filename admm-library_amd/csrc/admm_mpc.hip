@@ -35,10 +35,7 @@ int check_step(const char* fn, const admm_handle* h, const admm_mpc_step* s) {
   if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
   if (!s) return bad(fn, "step is NULL");
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a time-sharded handle (a rank holds a stage window only)");
-  if (h->cons_G)
-    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a scenario-consensus handle (a per-QP plant step is not the coupled problem's)");
-  if (h->hs_nh)
-    return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on a handle with half-spaces (a per-QP plane is not window-relative: it would have to shift with the horizon)");
+  if (int rc = refuse_on_kind(h, fn, &ZKindInfo::no_step)) return rc;
   if (h->pinst || h->time_varying == 2)
     return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available with per-instance dynamics (time_varying = 2): the per-QP operands and factors would have to shift too");
   if (h->n > admm::MPC_MAX_N || h->m > admm::MPC_MAX_M) return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": (n, m) beyond (12, 6)");

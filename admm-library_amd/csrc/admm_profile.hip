@@ -12,12 +12,8 @@ int admm_profile(admm_handle* h, int32_t iters, int32_t residuals, int32_t fused
   if (h->pinst && fused_path != 1) return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: per-instance dynamics run the plain fused path only (fused_path = 1)");
   if (h->ts_n) return fail(ADMM_ERR_UNSUPPORTED, "admm_profile is not available on a time-sharded handle");
   // (the fused kernels carry the per-QP z-update and leave the state in the v-form, whose read-out knows only the per-QP prox)
-  if (h->cons_G && fused_path != 0)
-    return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a scenario-consensus handle runs the unfused path only (fused_path = 0)");
-  if (h->has_soft && fused_path != 0)
-    return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a handle with soft weights runs the unfused path only (fused_path = 0)");
-  if (h->hs_nh && fused_path != 0)
-    return fail(ADMM_ERR_UNSUPPORTED, "admm_profile: a handle with half-spaces runs the unfused path only (fused_path = 0)");
+  if (h->zkind != ZKind::Box && fused_path != 0)
+    return fail(ADMM_ERR_UNSUPPORTED, std::string("admm_profile: ") + zkind_info(h->zkind).handle + " runs the unfused path only (fused_path = 0)");
   h->xfree_mode = 1;
   drop_side_data(h);                          // modes 0 .. 3 time the full-read / full-write forms; none leaves side data
   HIP_TRY(hipSetDevice(h->device));

@@ -266,9 +266,9 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, Mem mem) {
   } else if (problem_has_soc(p) != h->has_soc)
     return fail(ADMM_ERR_INVALID, "admm_update_problem: a thrust-magnitude bound cannot be added to or removed from a handle");
   // soft weights stay in force, per stacked row; the control rows of the new problem's thrust / fuel stages must still be hard
-  if (h->has_soft && (rc = validate_soft(p, h->soft.data(), true, fuel_of(h)))) return rc;
+  if (h->zkind == ZKind::Soft && (rc = validate_soft(p, h->soft.data(), true, fuel_of(h)))) return rc;
   // half-spaces stay in force; the state rows under a plane must still be open in the new box
-  if (h->hs_nh && p->time_varying != 2 && (rc = halfspace_box_open("admm_update_problem", p, h->hs_any, h->hs_nh))) return rc;
+  if (h->zkind == ZKind::Halfspace && p->time_varying != 2 && (rc = halfspace_box_open("admm_update_problem", p, h->hs_any, h->hs_nh))) return rc;
   if ((p->time_varying == 2) != h->pinst || (h->pinst && (p->stage_bounds == 2) != h->pbounds))
     return fail(ADMM_ERR_INVALID, "admm_update_problem: per-instance dynamics / bounds cannot be added to or removed from a handle");
   if (h->pinst) {

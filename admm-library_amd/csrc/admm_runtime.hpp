@@ -1,6 +1,8 @@
 // admm_runtime.hpp -- internals shared by the translation units of the solver runtime (round 3: csrc/admm_api.hip used to hold
 // all of it in 2.4 k lines):
-//   admm_api.hip      the C ABI entry points (setup, state, iteration, solve, read-out)
+//   admm_api.hip      the C ABI of state, iteration, solve and read-out
+//   admm_setup.hip    set-up of a handle, step by step, and every admm_setup* entry point
+//   admm_zext.hip     the entry points of the fuel term and of the z-update extensions (consensus, soft box, half-spaces)
 //   admm_launch.hip   kernel launches, the time-shard exchange, iteration forms and their schedule, graph capture
 //   admm_hostio.hip   host <-> device transfers, validation, uploads of a factor, handle lifetime
 //   admm_rho_update.hip rho changes and problem updates: background candidate factors, admm_set_rho, admm_update_problem
@@ -41,6 +43,33 @@ struct SpecFactor {
   ~SpecFactor() { if (th.joinable()) th.join(); }
 };
 
+// Which standalone z kernel a handle runs: the per-QP box / thrust-ball prox, or ONE extension of it.  A fuel term
+// and a thrust bound (has_fuel, has_soc) compose with every kind and are not one.
+enum class ZKind { Box, Consensus, Soft, Halfspace };
+
+// What the runtime says and decides per kind, once.  Every extension runs the unfused path of the one-lane fp64 kernels of
+// batch-shared dynamics only: its set-up refuses time_varying = 2 and the MFMA precision modes and forces ADMM_FLAG_UNFUSED.
+struct ZKindInfo {
+  const char* setup;         // the set-up entry point, as the messages name it
+  const char *needs, *is_not;   // the subject of set-up's refusals, with its verb: "... needs batch-shared dynamics", "... is not supported by ..."
+  bool whole_blocks;         // a chunk of the z kernel is whole blocks (a block-structured walk)
+  const char* handle;        // such a handle, as the refusals of calls on it name it
+  const char* no_step;       // why the receding-horizon step refuses it; nullptr: it does not
+  const char* no_probe;      // why the infeasibility probe refuses it; nullptr: it does not
+  const char* payload;       // what a handle of another kind lacks: "the handle has no ..."
+};
+constexpr ZKindInfo ZKINDS[] = {
+    {"admm_setup", nullptr, nullptr, false, nullptr, nullptr, nullptr, nullptr},
+    {"admm_setup_consensus", "scenario consensus needs", "scenario consensus is not", true, "a scenario-consensus handle",
+     "a per-QP plant step is not the coupled problem's", "a per-QP Farkas certificate is not the coupled problem's", "scenario groups"},
+    {"admm_setup_soft", "soft constraints need", "soft constraints are not", false, "a handle with soft weights", nullptr, nullptr,
+     "soft weights"},
+    {"admm_setup_halfspace", "half-spaces need", "half-spaces are not", true, "a handle with half-spaces",
+     "a per-QP plane is not window-relative: it would have to shift with the horizon",
+     "the Farkas certificate is written for boxes and the thrust ball", "half-spaces"},
+};
+constexpr const ZKindInfo& zkind_info(ZKind k) { return ZKINDS[static_cast<int>(k)]; }
+
 struct admm_handle {
   int N = 0, n = 0, m = 0, nb = 0, batch = 0, pitch = 0, L = 0;
   int S = 0, zrows = 0, zchunks = 0;
@@ -61,10 +90,10 @@ struct admm_handle {
   bool has_soc = false;          // some stage has a finite thrust-magnitude bound, or the handle has a fuel term
   bool has_fuel = false;         // set up by admm_setup_fuel with weights: cost term sum_k fuel[k] ||u_k||_2
   std::vector<double> fuel;      // its N per-stage weights (the records and h->kap hold fuel[k] / rho)
-  int cons_G = 0;                // scenario consensus (admm_setup_consensus): group size, 0 = a handle without groups
+  ZKind zkind = ZKind::Box;      // the standalone z kernel (launch_z), set once by init_handle; only that kind's fields below are in use
+  int cons_G = 0;                // scenario consensus (admm_setup_consensus): group size
   // soft box constraints (admm_setup_soft): the weights per stacked row (+inf = hard), their device copy, weight / rho
   // beside it (refreshed wherever h->kap is: upload_kappa), and the report's results, allocated on the first admm_get_soft_report* call
-  bool has_soft = false;
   std::vector<double> soft;      // [L]
   double *soft_d = nullptr, *skap_d = nullptr, *soft_out = nullptr;      // [L], [L], [2][pitch] penalty | max violation
   int* soft_cnt = nullptr;       // [pitch] violated rows
@@ -72,7 +101,7 @@ struct admm_handle {
   // live on the device only -- shared [N][nh] | [N], or per QP batch-minor [N][nh][pitch] | [N][pitch] --, at addresses that never
   // change (captured graphs hold them); the host keeps which stages have a plane for some QP (the open-box rule).  The report's
   // results and the scan's flags are allocated on first use.
-  int hs_nh = 0;                 // 0 = a handle without half-spaces
+  int hs_nh = 0;
   bool hs_perqp = false;
   double *hs_a = nullptr, *hs_b = nullptr;
   std::vector<char> hs_any;      // [N] some QP has a plane at the stage
@@ -223,7 +252,22 @@ inline int fail(int code, const std::string& msg) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                          \
+// A call that some kinds cannot serve: ADMM_OK, or the refusal with the reason the table gives in column `why` (no_step / no_probe).
+inline int refuse_on_kind(const admm_handle* h, const char* fn, const char* ZKindInfo::*why) {
+  const ZKindInfo& k = zkind_info(h->zkind);
+  if (!(k.*why)) return ADMM_OK;
+  return fail(ADMM_ERR_UNSUPPORTED, std::string(fn) + ": not available on " + k.handle + " (" + k.*why + ")");
+}
+// A call on one kind's payload: ADMM_OK on a handle of that kind, else that the handle has none (adding: that none can be added).
+inline int require_kind(const admm_handle* h, ZKind want, const char* fn, bool adding = false) {
+  if (h->zkind == want) return ADMM_OK;
+  const ZKindInfo& k = zkind_info(want);
+  return fail(ADMM_ERR_INVALID, std::string(fn) + ": " + (adding ? std::string(k.payload) + " cannot be added to a handle"
+                                                                 : std::string("the handle has no ") + k.payload) +
+                                    " (set it up with " + k.setup + ")");
+}
+
+#define HIP_TRY(expr)                                                                         \
   do {                                                                                         \
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess)                                                                      \
@@ -436,6 +480,8 @@ inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fue
 // halfspace_box_open: the state rows 0 .. nh - 1 of every stage in `any` have the box (-inf, inf) in p (a batch-shared box).
 int halfspace_stages(const char* fn, const double* a, const double* b, int count, int N, int nh, std::vector<char>& any);
 int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh);
+// the planes of a half-space handle into h->hs_a / h->hs_b (admm_zext.hip); returns with the copies complete
+int upload_halfspace(admm_handle* h, Mem mem, const double* a, const double* b);
 
 // ---- per-instance dynamics (admm_pinst_rt.hip)
 int pinst_factor(admm_handle* h, bool only_marked = false);
@@ -449,7 +495,7 @@ int pinst_try(admm_handle* h, const double* Ad, const double* Bd, const double* 
               const double* rhov, const int* todo, int* n_not_pd, int* n_grown);
 int pinst_segments(admm_handle* h);
 int setup_pinst(admm_handle* h, const admm_problem* p, Mem mem);
-void choose_zchunks(admm_handle* h, int zrows);   // admm_api.hip; zrows = 0: one workgroup per CU
+void choose_zchunks(admm_handle* h, int zrows);   // admm_setup.hip; zrows = 0: one workgroup per CU
 
 // ---- refactors: background candidates of the adaptive rule, rho changes (admm_rho_update.hip)
 admm_problem shared_problem(const admm_handle* h);

@@ -95,6 +95,16 @@ class Problem:
         """Every QP has its own per-stage box (admm_problem.stage_bounds = 2)."""
         return self.lo.ndim == 3
 
+    @property
+    def z_kind(self) -> Optional[str]:
+        """The extension of the z-update the problem asks for: "consensus", "soft", "halfspace", or None.
+        validate() admits at most one; a fuel term and a thrust bound compose with each and are not one."""
+        if self.hs_a is not None:
+            return "halfspace"
+        if self.soft is not None:
+            return "soft"
+        return "consensus" if self.consensus is not None else None
+
     def slice(self, start: int, stop: int) -> "Problem":
         """Contiguous sub-batch [start, stop): the sharding unit."""
         rep = dict(x0=np.ascontiguousarray(self.x0[start:stop]),

@@ -338,30 +338,22 @@ class Solver:
             _check(self._lib, self._lib.admm_setup_device(C.byref(self._h), C.byref(cp), C.byref(co), _stream(problem.device)))
         elif timeshard is None:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
-            if problem.hs_a is not None:         # (validate() has refused half-spaces together with soft or consensus)
+            keep["fuel"] = None if problem.fuel is None else _abi.marshal_fuel(problem)
+            head = (C.byref(self._h), C.byref(cp), C.byref(co))
+            kind = problem.z_kind                # (validate() has admitted at most one extension of the z-update)
+            if kind == "halfspace":
                 keep["hs_a"], keep["hs_b"], nh, per_qp = _abi.marshal_halfspace(problem)
-                if problem.fuel is not None:
-                    keep["fuel"] = _abi.marshal_fuel(problem)
-                _check(self._lib, self._lib.admm_setup_halfspace(C.byref(self._h), C.byref(cp), C.byref(co),
-                                                                 dptr(keep["fuel"]) if "fuel" in keep else c_double_p(),
-                                                                 dptr(keep["hs_a"]), dptr(keep["hs_b"]), nh, int(per_qp)))
-            elif problem.soft is not None:       # (validate() has refused soft together with consensus)
+                rc = self._lib.admm_setup_halfspace(*head, dptr(keep["fuel"]), dptr(keep["hs_a"]), dptr(keep["hs_b"]), nh, int(per_qp))
+            elif kind == "soft":
                 keep["soft"] = _abi.marshal_soft(problem)
-                if problem.fuel is not None:
-                    keep["fuel"] = _abi.marshal_fuel(problem)
-                _check(self._lib, self._lib.admm_setup_soft(C.byref(self._h), C.byref(cp), C.byref(co),
-                                                            dptr(keep["fuel"]) if "fuel" in keep else c_double_p(), dptr(keep["soft"])))
-            elif problem.consensus is not None:
-                if problem.fuel is not None:
-                    keep["fuel"] = _abi.marshal_fuel(problem)
-                _check(self._lib, self._lib.admm_setup_consensus(C.byref(self._h), C.byref(cp), C.byref(co),
-                                                                 dptr(keep["fuel"]) if "fuel" in keep else c_double_p(),
-                                                                 int(problem.consensus)))
-            elif problem.fuel is not None:
-                keep["fuel"] = _abi.marshal_fuel(problem)
-                _check(self._lib, self._lib.admm_setup_fuel(C.byref(self._h), C.byref(cp), C.byref(co), dptr(keep["fuel"])))
+                rc = self._lib.admm_setup_soft(*head, dptr(keep["fuel"]), dptr(keep["soft"]))
+            elif kind == "consensus":
+                rc = self._lib.admm_setup_consensus(*head, dptr(keep["fuel"]), int(problem.consensus))
+            elif keep["fuel"] is not None:
+                rc = self._lib.admm_setup_fuel(*head, dptr(keep["fuel"]))
             else:
-                _check(self._lib, self._lib.admm_setup(C.byref(self._h), C.byref(cp), C.byref(co)))
+                rc = self._lib.admm_setup(*head)
+            _check(self._lib, rc)
         else:
             cp, keep = _abi.marshal_problem(problem, self._row_major)
             if problem.fuel is not None:

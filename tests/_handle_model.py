@@ -92,7 +92,7 @@ class HandleModel:
             outs = [oc.solve(self._sub(b), rho=float(self.rho[b]), z0=self.z[b:b + 1], y0=self.y[b:b + 1], nthreads=1, **kw)
                     for b in range(self.p.batch)]
             self.w, self.z, self.y = (np.concatenate([o[k_] for o in outs]) for k_ in ("w", "z", "y"))
-        elif self.p.soft is not None or self.p.consensus is not None:
+        elif self.p.z_kind is not None:
             o = (sr if self.p.soft is not None else cs).solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw)
             self.w, self.z, self.y = o.w, o.z, o.y
         elif self.p.fuel is not None:
@@ -128,7 +128,7 @@ class HandleModel:
             raise Refused(UNSUPPORTED, "the alternating-direction kernels are not enabled")
         if self.per_qp and mode != 1:
             raise Refused(UNSUPPORTED, "per-instance dynamics: mode 1 only")
-        if (self.p.soft is not None or self.p.consensus is not None) and mode != 0:
+        if self.p.z_kind is not None and mode != 0:
             raise Refused(UNSUPPORTED, "soft and scenario-consensus handles run the unfused path only")
         k = {0: iters, 1: iters, 2: 2 * iters + 1, 3: 1}[mode] + (1 if mode in (2, 3) and self.pair_form else 0)
         self._advance(k, k if residuals else 0)

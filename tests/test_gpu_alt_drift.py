@@ -57,7 +57,7 @@ PARAMS = [(c, k) for c in ad.CASES for k in (("default_b3", "plain_b3") if c.wid
 
 def _family(p, flags):
     """The family a handle of p with these flags runs: the fp64 MFMA form by default for a small batch of a compiled shape
-    without q or thrust bound (csrc/admm_api.hip); the one-lane kernels otherwise."""
+    without q or thrust bound (csrc/admm_setup.hip); the one-lane kernels otherwise."""
     small = p.batch <= 64 or (p.n >= 9 and p.batch <= 128)
     mfma = not (flags & (NO_MFMA | NO_ALT)) and (p.n, p.m) in MFMA_DIMS and p.q is None and p.unorm is None and small
     return "mfma_fp64" if mfma else "one_lane_fp64"

@@ -29,7 +29,7 @@ def _solver(p, opts, expect_plain):
         s = pkg.Solver(p, opts)
     path = s.path()
     assert path["alternating"] == (requested and not expect_plain), path
-    # the fp64 MFMA form is the default at its pairs for small batches (admm_api.hip), a linear term at (6, 3) only
+    # the fp64 MFMA form is the default at its pairs for small batches (admm_setup.hip), a linear term at (6, 3) only
     pitch = (p.batch + 63) // 64 * 64
     mfma = ((p.n, p.m) in ((6, 3), (10, 4), (12, 6)) and (p.q is None or ((p.n, p.m) == (6, 3) and pitch <= 128))
             and p.unorm is None and path["alternating"] and not opts.flags & 32 and (pitch <= 64 or (p.n >= 9 and pitch <= 128)))
