@@ -197,6 +197,15 @@ def marshal_halfspace(p: Problem):
     return a, b, nh, per_qp
 
 
+def marshal_cone(p: Problem):
+    """(c, apex, gamma, nh, per_qp) of p.cone_c / cone_p / cone_g as admm_setup_cone / admm_set_cone read them: contiguous fp64, C
+    order (c[b][k][i], apex[b][k][i], gamma[b][k]); nh and the form inferred from the shapes."""
+    from .problems import cone_form
+    c, apex, g = (np.ascontiguousarray(x, np.float64) for x in (p.cone_c, p.cone_p, p.cone_g))
+    nh, per_qp = cone_form(c, apex, g, p.N, p.n, p.batch)
+    return c, apex, g, nh, per_qp
+
+
 def marshal_device_problem(p, row_major: bool = False):
     """marshal_problem of a DeviceProblem (validated here): the CProblem holds device pointers.  The layout work marshal_problem does
     on the host -- column-major matrices, the broadcast of unorm -- is done by torch on the tensors' GPU (copies on the current

@@ -1,6 +1,7 @@
 // admm_hostio.hip -- solver runtime: host <-> device transfers, validation, uploads of a factor, handle lifetime (admm_runtime.hpp)
 #include "admm_runtime.hpp"
 #include "admm_halfspace.hpp"
+#include "admm_cone.hpp"
 
 namespace admm {
 namespace rt {
@@ -654,15 +655,38 @@ int halfspace_stages(const char* fn, const double* a, const double* b, int count
   return ADMM_OK;
 }
 
-int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh) {
+int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh, const char* what) {
   const int nb = p->n + p->m;
   for (int k = 0; k < p->N; ++k) {
     if (!any[k]) continue;
     const size_t o = (p->stage_bounds ? (size_t)k * nb : 0) + p->m;
     for (int i = 0; i < nh; ++i)
       if (p->lo[o + i] != -INFINITY || p->hi[o + i] != INFINITY)
-        return fail(ADMM_ERR_INVALID, std::string(fn) + ": state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with a half-space (stage " +
-                                          std::to_string(k) + ")");
+        return fail(ADMM_ERR_INVALID, std::string(fn) + ": state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with " + what +
+                                          " (stage " + std::to_string(k) + ")");
+  }
+  return ADMM_OK;
+}
+
+int cone_stages(const char* fn, const double* c, const double* apex, const double* gamma, int count, int N, int nh, std::vector<char>& any) {
+  if (!finite_all(c, (size_t)count * N * nh) || !finite_all(apex, (size_t)count * N * nh) || !finite_all(gamma, (size_t)count * N))
+    return fail(ADMM_ERR_INVALID, std::string(fn) + ": non-finite entry in c, apex or gamma");
+  any.assign(N, 0);
+  for (size_t s = 0; s < (size_t)count * N; ++s) {
+    const double* cs = c + s * nh;
+    double nn = 0.0;
+    bool nz = false;
+    for (int i = 0; i < nh; ++i) {
+      nn = std::fma(cs[i], cs[i], nn);
+      nz = nz || cs[i] != 0.0;
+    }
+    if (!nz) continue;
+    if (!admm::halfspace_norm_ok(nn))
+      return fail(ADMM_ERR_INVALID, std::string(fn) + ": c'c of stage " + std::to_string(s % N) + " is not a normal number (scale the axis)");
+    if (!admm::cone_slope_ok(gamma[s]))
+      return fail(ADMM_ERR_INVALID, std::string(fn) + ": gamma of stage " + std::to_string(s % N) +
+                                        " must be a positive normal number with 1 + gamma^2 finite");
+    any[s % N] = 1;
   }
   return ADMM_OK;
 }

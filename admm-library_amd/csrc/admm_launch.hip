@@ -6,6 +6,7 @@
 #include "admm_select.hpp"
 #include "admm_soft.hpp"
 #include "admm_halfspace.hpp"
+#include "admm_cone.hpp"
 
 namespace admm {
 
@@ -259,6 +260,11 @@ int launch_z(admm_handle* h, bool resid) {
       admm::launch_halfspace(admm::HalfspaceLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->hs_a, h->hs_b, h->part,
                                                    h->opt.alpha, h->L, h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->hs_nh, resid,
                                                    h->has_soc, h->hs_perqp});
+      return ADMM_OK;
+    case ZKind::Cone:                            // one approach cone per stage on the first state rows (admm_cone_kernels.hpp)
+      admm::launch_cone(admm::ConeLaunch{h->stream, h->w, h->z, h->y, h->lo, h->hi, h->ub, h->kap, h->cone_c, h->cone_p, h->cone_g, h->part,
+                                         h->opt.alpha, h->L, h->zrows, h->zchunks, h->pitch, h->nb, h->m, h->cone_nh, resid, h->has_soc,
+                                         h->cone_perqp});
       return ADMM_OK;
     case ZKind::Box: break;                      // the per-QP box / thrust-ball prox below
   }

@@ -96,6 +96,68 @@ ADMM_PROX_FN bool halfspace_project(const double* a, double b, int nh, const dou
   return true;
 }
 
+// Approach cone of a stage: the Euclidean projection of the nh rows v onto the second-order cone
+//     { z :  r <= g s },   e = c / |c|,  s = e'(z - p),  r = |(z - p) - s e|      (axis c, apex p, slope g = tan of the half-angle)
+// With dl_i = v_i - p_i and the three sums as fma chains in row order from 0 (cone_norm, cone_acc):
+//     nn = c'c,  d = c'dl,  q = dl'dl,   rn = sqrt(nn),  s = d / rn,  r = sqrt(max(fma(-s, s, q), 0))
+//     r <= g s         inside:   z_i = v_i      (the bits of v: y_i = +0)
+//     else g r <= -s   polar:    z_i = p_i      (the apex)
+//     else             surface:  t = fma(g, r, s) / fma(g, g, 1),  bet = g t / r,  kap = (t - bet s) / rn,
+//                                z_i = fma(kap, c_i, fma(bet, dl_i, p_i))
+// r > 0 in the third branch by the two tests before it.  nn == 0 (c = 0) is a stage without a cone: its rows take their box, and
+// nothing below is evaluated for it.  Every product and difference outside an fma is rounded on its own: the functions switch
+// contraction off, so that host and device give the same bits.  The row is a select between v, p and the surface expression (no
+// divergent branch); the quotients of the surface branch are formed with r replaced by 1 where the branch is not taken, so no
+// lane ever divides by zero.  Independent of rho: the prox of an indicator.
+enum ConeBranch : int { CONE_INSIDE = 0, CONE_APEX = 1, CONE_SURFACE = 2 };
+struct ConeStep {
+  double kap, bet;
+  int branch;
+};
+ADMM_PROX_FN double cone_norm(double c, double nn) { return fma(c, c, nn); }
+ADMM_PROX_FN void cone_acc(double c, double p, double v, double& d, double& q) {
+  const double dl = v - p;
+  d = fma(c, dl, d);
+  q = fma(dl, dl, q);
+}
+ADMM_PROX_FN ConeStep cone_step(double nn, double d, double q, double g) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double rn = sqrt(nn);
+  const double s = d / rn;
+  const double r = sqrt(fmax(fma(-s, s, q), 0.0));
+  const double gr = g * r;
+  const int branch = r <= g * s ? CONE_INSIDE : gr <= -s ? CONE_APEX : CONE_SURFACE;
+  const double r1 = branch == CONE_SURFACE ? r : 1.0;
+  const double t = fma(g, r, s) / fma(g, g, 1.0);
+  const double gt = g * t;
+  const double bet = gt / r1;
+  const double bs = bet * s;
+  const double kap = (t - bs) / rn;
+  return ConeStep{kap, bet, branch};
+}
+ADMM_PROX_FN double cone_row(const ConeStep& st, double c, double p, double v) {
+  const double dl = v - p;
+  const double surf = fma(st.kap, c, fma(st.bet, dl, p));
+  return st.branch == CONE_INSIDE ? v : st.branch == CONE_APEX ? p : surf;
+}
+// one stage on the host (tests) and wherever the rows sit in an array: z, y of the nh rows; returns the branch, -1 = no cone
+ADMM_PROX_FN int cone_project(const double* c, const double* p, double g, int nh, const double* v, double* z, double* y) {
+  double nn = 0.0, d = 0.0, q = 0.0;
+  for (int i = 0; i < nh; ++i) {
+    nn = cone_norm(c[i], nn);
+    cone_acc(c[i], p[i], v[i], d, q);
+  }
+  if (nn == 0.0) return -1;
+  const ConeStep st = cone_step(nn, d, q, g);
+  for (int i = 0; i < nh; ++i) {
+    z[i] = cone_row(st, c[i], p[i], v[i]);
+    y[i] = v[i] - z[i];
+  }
+  return st.branch;
+}
+
 // the relaxed x-update output w^ from w and the old z
 template <bool RELAX>
 ADMM_PROX_FN double relaxed(double alpha, double w, double zo) {

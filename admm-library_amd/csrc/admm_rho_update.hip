@@ -269,6 +269,7 @@ int update_problem_checked(admm_handle* h, const admm_problem* p, Mem mem) {
   if (h->zkind == ZKind::Soft && (rc = validate_soft(p, h->soft.data(), true, fuel_of(h)))) return rc;
   // half-spaces stay in force; the state rows under a plane must still be open in the new box
   if (h->zkind == ZKind::Halfspace && p->time_varying != 2 && (rc = halfspace_box_open("admm_update_problem", p, h->hs_any, h->hs_nh))) return rc;
+  if (h->zkind == ZKind::Cone && p->time_varying != 2 && (rc = halfspace_box_open("admm_update_problem", p, h->cone_any, h->cone_nh, "a cone"))) return rc;
   if ((p->time_varying == 2) != h->pinst || (h->pinst && (p->stage_bounds == 2) != h->pbounds))
     return fail(ADMM_ERR_INVALID, "admm_update_problem: per-instance dynamics / bounds cannot be added to or removed from a handle");
   if (h->pinst) {

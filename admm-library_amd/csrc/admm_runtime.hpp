@@ -2,7 +2,7 @@
 // all of it in 2.4 k lines):
 //   admm_api.hip      the C ABI of state, iteration, solve and read-out
 //   admm_setup.hip    set-up of a handle, step by step, and every admm_setup* entry point
-//   admm_zext.hip     the entry points of the fuel term and of the z-update extensions (consensus, soft box, half-spaces)
+//   admm_zext.hip     the entry points of the fuel term and of the z-update extensions (consensus, soft box, half-spaces, cones)
 //   admm_launch.hip   kernel launches, the time-shard exchange, iteration forms and their schedule, graph capture
 //   admm_hostio.hip   host <-> device transfers, validation, uploads of a factor, handle lifetime
 //   admm_rho_update.hip rho changes and problem updates: background candidate factors, admm_set_rho, admm_update_problem
@@ -45,7 +45,7 @@ struct SpecFactor {
 
 // Which standalone z kernel a handle runs: the per-QP box / thrust-ball prox, or ONE extension of it.  A fuel term
 // and a thrust bound (has_fuel, has_soc) compose with every kind and are not one.
-enum class ZKind { Box, Consensus, Soft, Halfspace };
+enum class ZKind { Box, Consensus, Soft, Halfspace, Cone };
 
 // What the runtime says and decides per kind, once.  Every extension runs the unfused path of the one-lane fp64 kernels of
 // batch-shared dynamics only: its set-up refuses time_varying = 2 and the MFMA precision modes and forces ADMM_FLAG_UNFUSED.
@@ -67,6 +67,9 @@ constexpr ZKindInfo ZKINDS[] = {
     {"admm_setup_halfspace", "half-spaces need", "half-spaces are not", true, "a handle with half-spaces",
      "a per-QP plane is not window-relative: it would have to shift with the horizon",
      "the Farkas certificate is written for boxes and the thrust ball", "half-spaces"},
+    {"admm_setup_cone", "approach cones need", "approach cones are not", true, "a handle with approach cones",
+     "a per-QP cone is not window-relative: it would have to shift with the horizon",
+     "the Farkas certificate is written for boxes and the thrust ball", "approach cones"},
 };
 constexpr const ZKindInfo& zkind_info(ZKind k) { return ZKINDS[static_cast<int>(k)]; }
 
@@ -107,6 +110,15 @@ struct admm_handle {
   std::vector<char> hs_any;      // [N] some QP has a plane at the stage
   double *hs_out = nullptr, *hs_lam = nullptr;     // [pitch] max violation; [N][pitch] multipliers
   int *hs_cnt = nullptr, *hs_flags = nullptr;      // [pitch] active stages; [2][N] findings of halfspace_scan_kernel
+  // one approach cone per stage (admm_setup_cone): axis, apex and slope on the first cone_nh state rows of a block,
+  // kept as the half-spaces are -- on the device only, shared [N][nh] | [N][nh] | [N] or per QP batch-minor [N][nh][pitch] twice |
+  // [N][pitch], at addresses that never change; the host keeps which stages have a cone for some QP (the open-box rule)
+  int cone_nh = 0;
+  bool cone_perqp = false;
+  double *cone_c = nullptr, *cone_p = nullptr, *cone_g = nullptr;
+  std::vector<char> cone_any;    // [N] some QP has a cone at the stage
+  double *cone_out = nullptr, *cone_lam = nullptr; // [pitch] max violation; [N][pitch] rho |y_xi|
+  int *cone_cnt = nullptr, *cone_flags = nullptr;  // [pitch] active stages; [3][N] findings of cone_scan_kernel
   admm_options opt{};
   admm::Factor fac;
   // host copy of the shared problem data (the caller's pointers are never kept): admm_set_rho refactors from it
@@ -479,9 +491,15 @@ inline const double* fuel_of(const admm_handle* h) { return h->has_fuel ? h->fue
 // shared form) must be finite and every a_k'a_k of a stage with a plane a normal number; any[k] = some QP has a plane at stage k.
 // halfspace_box_open: the state rows 0 .. nh - 1 of every stage in `any` have the box (-inf, inf) in p (a batch-shared box).
 int halfspace_stages(const char* fn, const double* a, const double* b, int count, int N, int nh, std::vector<char>& any);
-int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh);
+int halfspace_box_open(const char* fn, const admm_problem* p, const std::vector<char>& any, int nh, const char* what = "a half-space");
 // the planes of a half-space handle into h->hs_a / h->hs_b (admm_zext.hip); returns with the copies complete
 int upload_halfspace(admm_handle* h, Mem mem, const double* a, const double* b);
+// approach cones against a validated problem: c, apex, gamma as the caller gives them (c[b][k][i], apex[b][k][i], gamma[b][k]; one
+// "QP" in the shared form) must be finite, and where c_k != 0 c_k'c_k a normal number and gamma a positive normal number with
+// 1 + gamma^2 finite; any[k] = some QP has a cone at stage k.  The open-box rule is halfspace_box_open's.
+int cone_stages(const char* fn, const double* c, const double* apex, const double* gamma, int count, int N, int nh, std::vector<char>& any);
+// the cones of such a handle into h->cone_c / cone_p / cone_g (admm_zext.hip); returns with the copies complete
+int upload_cone(admm_handle* h, Mem mem, const double* c, const double* apex, const double* gamma);
 
 // ---- per-instance dynamics (admm_pinst_rt.hip)
 int pinst_factor(admm_handle* h, bool only_marked = false);

@@ -31,6 +31,12 @@ struct SetupRequest {
   int hs_nh = 0;
   bool hs_perqp = false;
   std::vector<char> hs_any;
+  // Cone: c[b][k][i], apex[b][k][i], gamma[b][k] of one approach cone per stage on the first cone_nh state rows (one "QP" unless
+  // cone_perqp); cone_any: the stages with a cone for some QP, filled by check_setup_request
+  const double *cone_c = nullptr, *cone_p = nullptr, *cone_g = nullptr;
+  int cone_nh = 0;
+  bool cone_perqp = false;
+  std::vector<char> cone_any;
 };
 
 // options and problem data, then what a fuel term, the z-update kind and time shards each exclude
@@ -66,6 +72,12 @@ int check_setup_request(SetupRequest& r) {
       std::vector<double> fk;
       if (r.fuel) { fk.resize(p->N); for (int k2 = 0; k2 < p->N; ++k2) fk[k2] = r.fuel[p->stage_bounds ? k2 : 0]; }
       if ((rc = validate_soft(p, r.soft, false, r.fuel ? fk.data() : nullptr))) return rc;
+    } else if (r.zkind == ZKind::Cone) {
+      if (r.cone_nh < 1 || r.cone_nh > p->n)
+        return fail(ADMM_ERR_INVALID, fn + "nh = " + std::to_string(r.cone_nh) + " must lie in 1 .. n = " + std::to_string(p->n));
+      if ((rc = cone_stages(k.setup, r.cone_c, r.cone_p, r.cone_g, r.cone_perqp ? p->batch : 1, p->N, r.cone_nh, r.cone_any)) ||
+          (rc = halfspace_box_open(k.setup, p, r.cone_any, r.cone_nh, "a cone")))
+        return rc;
     } else {
       if (r.hs_nh < 1 || r.hs_nh > p->n)
         return fail(ADMM_ERR_INVALID, fn + "nh = " + std::to_string(r.hs_nh) + " must lie in 1 .. n = " + std::to_string(p->n));
@@ -130,6 +142,11 @@ void init_handle(admm_handle* h, const SetupRequest& r, int dev) {
       h->hs_nh = r.hs_nh;
       h->hs_perqp = r.hs_perqp;
       h->hs_any = r.hs_any;
+      break;
+    case ZKind::Cone:
+      h->cone_nh = r.cone_nh;
+      h->cone_perqp = r.cone_perqp;
+      h->cone_any = r.cone_any;
       break;
   }
   if (r.fuel) {
@@ -356,12 +373,16 @@ int alloc_shared(admm_handle* h) {
   }
   const size_t part_chunks = (size_t)(h->zchunks > h->S ? h->zchunks : h->S);
   const size_t hs_cols = h->hs_perqp ? P : 1;        // the planes: shared, or one set per QP (batch-minor)
+  const size_t cone_cols = h->cone_perqp ? P : 1;    // the cones likewise
   h->stage_rows = Lw;
   if ((rc = dalloc(h, &h->part, part_chunks * 5 * P, true)) || (rc = dalloc(h, &h->resid, 5 * P, true)) ||
       (rc = dalloc(h, &h->lo, L)) || (rc = dalloc(h, &h->hi, L)) || (rc = dalloc(h, &h->ub, (size_t)h->N)) || (rc = dalloc(h, &h->kap, (size_t)h->N)) ||
       (h->zkind == ZKind::Soft && ((rc = dalloc(h, &h->soft_d, L)) || (rc = dalloc(h, &h->skap_d, L)))) ||
       (h->zkind == ZKind::Halfspace && ((rc = dalloc(h, &h->hs_a, (size_t)h->N * h->hs_nh * hs_cols, true)) ||
                                         (rc = dalloc(h, &h->hs_b, (size_t)h->N * hs_cols, true)))) ||
+      (h->zkind == ZKind::Cone && ((rc = dalloc(h, &h->cone_c, (size_t)h->N * h->cone_nh * cone_cols, true)) ||
+                                   (rc = dalloc(h, &h->cone_p, (size_t)h->N * h->cone_nh * cone_cols, true)) ||
+                                   (rc = dalloc(h, &h->cone_g, (size_t)h->N * cone_cols, true)))) ||
       (rc = dalloc(h, &h->recB, f.recB.size())) || (rc = dalloc(h, &h->recF, f.recF.size())) || (rc = dalloc(h, &h->recS, f.recS.size())) ||
       (rc = dalloc(h, &h->seg_start, f.seg_start.size())) || (rc = dalloc(h, &h->status, P, true)) || (rc = dalloc(h, &h->iters, P, true)) ||
       (rc = dalloc(h, &h->nconv, 1)) || (rc = dalloc(h, &h->stage, Lw * (size_t)h->batch)))
@@ -400,6 +421,7 @@ int setup_common(admm_handle** out, SetupRequest& r) {
   if ((rc = upload_transposed(h, r.src, p->x0, h->x0, h->n))) return rc;
   if (h->has_q && (rc = upload_transposed(h, r.src, p->q, h->q, h->L))) return rc;
   if (h->zkind == ZKind::Halfspace && (rc = upload_halfspace(h, Mem::Host, r.hs_a, r.hs_b))) return rc;
+  if (h->zkind == ZKind::Cone && (rc = upload_cone(h, Mem::Host, r.cone_c, r.cone_p, r.cone_g))) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   *out = guard.release();
   return ADMM_OK;
@@ -473,6 +495,21 @@ int admm_setup_halfspace(admm_handle** out, const admm_problem* p, const admm_op
   r.fuel = fuel;
   r.zkind = ZKind::Halfspace;
   r.hs_a = a; r.hs_b = b; r.hs_nh = nh; r.hs_perqp = per_instance != 0;
+  return setup_common(out, r);
+}
+
+// One approach cone per stage: admm_setup_fuel with the second-order cone of axis c, apex `apex` and slope gamma on
+// the first nh state rows of every block; the z-update is zdual_cone_kernel.
+int admm_setup_cone(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, const double* c,
+                    const double* apex, const double* gamma, int32_t nh, int32_t per_instance) {
+  if (out) *out = nullptr;
+  if (!c || !apex || !gamma)
+    return fail(ADMM_ERR_INVALID, "admm_setup_cone: c, apex and gamma must not be NULL (admm_setup / admm_setup_fuel set up a handle without approach cones)");
+  if (nh < 1) return fail(ADMM_ERR_INVALID, "admm_setup_cone: nh = " + std::to_string(nh) + " must lie in 1 .. n");
+  SetupRequest r(p, o);
+  r.fuel = fuel;
+  r.zkind = ZKind::Cone;
+  r.cone_c = c; r.cone_p = apex; r.cone_g = gamma; r.cone_nh = nh; r.cone_perqp = per_instance != 0;
   return setup_common(out, r);
 }
 

@@ -1,6 +1,6 @@
 // admm_zdual.hpp -- the standalone z-update and read-out kernels: zdual_kernel, zdual_soc_kernel,
-// v_to_zy_kernel, v_to_zy_soc_kernel, and the walks that zdual_soft_kernel (admm_soft_kernels.hpp) and zdual_halfspace_kernel
-// (admm_halfspace_kernels.hpp) share with them.  Part of
+// v_to_zy_kernel, v_to_zy_soc_kernel, and the walks that zdual_soft_kernel (admm_soft_kernels.hpp), zdual_halfspace_kernel
+// (admm_halfspace_kernels.hpp) and zdual_cone_kernel (admm_cone_kernels.hpp) share with them.  Part of
 // admm_kernels.hpp, which includes it inside namespace admm after the declarations it uses (Z_THREADS, cdouble_p, as_const).
 //
 // A kernel here is a WALK over the rows of a chunk, a SOURCE that says what a row is loaded from, and a PROX that says which
@@ -16,7 +16,7 @@
 //            VSource         v itself (read-out and mode switches of the v-form, §4.4); no sums
 //   proxes   BoxProx         clip to [lo[r], hi[r]]; SoftBoxProx (admm_soft_kernels.hpp) is the other one
 //   planes   NoPlane         z_walk_blocks only: a constraint that couples state rows of a stage; HalfspacePlane
-//                            (admm_halfspace_kernels.hpp) is the one there is
+//                            (admm_halfspace_kernels.hpp) and ConePlane (admm_cone_kernels.hpp) are the ones there are
 //
 // The row index is wave-uniform, so the bounds of a row are scalar loads through the constant address space and the per-QP sums
 // need no cross-lane step at all: each lane owns its QPs' accumulators.  Pad columns (batch .. pitch - 1) are computed like any
@@ -136,8 +136,8 @@ __device__ __forceinline__ void z_walk_rows(const Source& src, const Prox& prox,
 }
 
 // A constraint on the state rows of a stage, carried by z_walk_blocks beside the thrust ball of its control rows.  NoPlane: none
-// (the walk of zdual_soc_kernel, v_to_zy_soc_kernel, zdual_soft_kernel as it was); the other one is HalfspacePlane
-// (admm_halfspace_kernels.hpp).  A plane says, per block,
+// (the walk of zdual_soc_kernel, v_to_zy_soc_kernel, zdual_soft_kernel as it was); the others are HalfspacePlane
+// (admm_halfspace_kernels.hpp) and ConePlane (admm_cone_kernels.hpp).  A plane says, per block,
 //     Step step(src, k, rb, c)      what it needs from the block's rows before they are applied (a second read, as the norm's)
 //     bool covers(step, r)          wave-uniform: row r of the block may be the plane's
 //     ZY2 row(step, v, r, box, P)   (z, y) of such a row; box = the row's own prox, for the QPs whose stage has no plane

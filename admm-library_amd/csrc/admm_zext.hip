@@ -1,10 +1,12 @@
 // admm_zext.hip -- entry points of what extends the z-update of a handle (admm_runtime.hpp): the fuel term, which
-// composes with every kind, and the payload of each ZKind -- scenario groups, soft weights, half-spaces: set, get, report.  Their
-// set-up entry points are in admm_setup.hip, their kernels behind admm_consensus.hpp, admm_soft.hpp and admm_halfspace.hpp.
+// composes with every kind, and the payload of each ZKind -- scenario groups, soft weights, half-spaces, approach cones: set, get,
+// report.  Their set-up entry points are in admm_setup.hip, their kernels behind admm_consensus.hpp, admm_soft.hpp,
+// admm_halfspace.hpp and admm_cone.hpp.
 #include "admm_runtime.hpp"
 #include "admm_consensus.hpp"
 #include "admm_soft.hpp"
 #include "admm_halfspace.hpp"
+#include "admm_cone.hpp"
 
 using namespace admm::rt;
 
@@ -22,6 +24,24 @@ int upload_halfspace(admm_handle* h, Mem mem, const double* a, const double* b) 
   const hipMemcpyKind kind = mem == Mem::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   HIP_TRY(hipMemcpyAsync(h->hs_a, a, sizeof(double) * (size_t)h->N * h->hs_nh, kind, h->stream));
   HIP_TRY(hipMemcpyAsync(h->hs_b, b, sizeof(double) * (size_t)h->N, kind, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return ADMM_OK;
+}
+
+// the cones of a cone handle into h->cone_c / cone_p / cone_g (their addresses never change), as upload_halfspace does the planes
+int upload_cone(admm_handle* h, Mem mem, const double* c, const double* apex, const double* gamma) {
+  int rc;
+  const int rows = h->N * h->cone_nh;
+  if (h->cone_perqp) {
+    if ((rc = upload_transposed(h, mem, c, h->cone_c, rows)) || (rc = upload_transposed(h, mem, apex, h->cone_p, rows)) ||
+        (rc = upload_transposed(h, mem, gamma, h->cone_g, h->N)))
+      return rc;
+    return ADMM_OK;
+  }
+  const hipMemcpyKind kind = mem == Mem::Device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  HIP_TRY(hipMemcpyAsync(h->cone_c, c, sizeof(double) * (size_t)rows, kind, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->cone_p, apex, sizeof(double) * (size_t)rows, kind, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->cone_g, gamma, sizeof(double) * (size_t)h->N, kind, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return ADMM_OK;
 }
@@ -128,6 +148,87 @@ static int halfspace_report_common(admm_handle* h, double* max_violation, int32_
   if (max_violation && (rc = io.copy_out(max_violation, h->hs_out, bsz))) return rc;
   if (n_active && (rc = io.copy_out(n_active, h->hs_cnt, csz))) return rc;
   if (lam && (rc = download_transposed(h, mem, h->hs_lam, lam, h->N))) return rc;
+  return io.finish();
+}
+
+// New cones on a cone handle, same form and nh: set_halfspace_common's order -- nothing of the handle is written before every
+// check has passed; the state is the (z, y) pair already and the factor does not depend on the cones.
+static int set_cone_common(admm_handle* h, const double* c, const double* apex, const double* gamma, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_set_cone_device" : "admm_set_cone";
+  if (!h || !c || !apex || !gamma) return fail(ADMM_ERR_INVALID, "NULL argument");
+  g_warn.clear();
+  int rc;
+  if ((rc = require_kind(h, ZKind::Cone, fn, /*adding=*/true))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  const int cnt = h->cone_perqp ? h->batch : 1, N = h->N, nh = h->cone_nh;
+  const size_t nc = (size_t)cnt * N * nh, ng = (size_t)cnt * N;
+  if ((rc = io.check_ptr(c, nc * sizeof(double), "c")) || (rc = io.check_ptr(apex, nc * sizeof(double), "apex")) ||
+      (rc = io.check_ptr(gamma, ng * sizeof(double), "gamma")))
+    return rc;
+  std::vector<char> any;
+  if (!io.dev()) {
+    if ((rc = cone_stages(fn, c, apex, gamma, cnt, N, nh, any))) return rc;
+  } else {
+    int bad;
+    if ((rc = io.begin()) || (rc = io.check_finite({{c, nc, "c"}, {apex, nc, "apex"}, {gamma, ng, "gamma"}}, &bad))) return rc;
+    if (bad >= 0) return fail(ADMM_ERR_INVALID, std::string(fn) + ": non-finite entry in c, apex or gamma");
+    if (h->cone_perqp) {            // the device-side findings: which stages have a cone for some QP, and whether a c'c or a slope is unusable
+      if (!h->cone_flags && (rc = dalloc(h, &h->cone_flags, (size_t)3 * N))) return rc;
+      std::vector<int> fl((size_t)3 * N);
+      HIP_TRY(hipMemsetAsync(h->cone_flags, 0, sizeof(int) * fl.size(), h->stream));
+      admm::launch_cone_scan(h->stream, c, gamma, h->batch, N, nh, h->cone_flags);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(fl.data(), h->cone_flags, sizeof(int) * fl.size(), hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      any.assign(N, 0);
+      for (int k = 0; k < N; ++k) {
+        if (fl[N + k]) return fail(ADMM_ERR_INVALID, std::string(fn) + ": c'c of stage " + std::to_string(k) + " is not a normal number (scale the axis)");
+        if (fl[2 * N + k])
+          return fail(ADMM_ERR_INVALID, std::string(fn) + ": gamma of stage " + std::to_string(k) + " must be a positive normal number with 1 + gamma^2 finite");
+        any[k] = fl[k] != 0;
+      }
+    } else {                        // the shared form is N (2 nh + 1) doubles: checked on the host, as a DeviceProblem's small arrays are
+      std::vector<double> ch(nc), ph(nc), gh(ng);
+      HIP_TRY(hipMemcpyAsync(ch.data(), c, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(ph.data(), apex, sizeof(double) * nc, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipMemcpyAsync(gh.data(), gamma, sizeof(double) * ng, hipMemcpyDeviceToHost, h->stream));
+      HIP_TRY(hipStreamSynchronize(h->stream));
+      if ((rc = cone_stages(fn, ch.data(), ph.data(), gh.data(), 1, N, nh, any))) return rc;
+    }
+  }
+  const admm_problem p = shared_problem(h);
+  if ((rc = halfspace_box_open(fn, &p, any, nh, "a cone"))) return rc;
+  HIP_TRY(hipStreamSynchronize(h->stream));   // kernels of the old cones are done before they change
+  if ((rc = upload_cone(h, mem, c, apex, gamma))) return rc;
+  h->cone_any = any;
+  return io.finish();
+}
+
+// largest violation of a cone by w, the stages whose y_xi is not zero, and rho |y_xi| (cone_report_kernel)
+static int cone_report_common(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, Mem mem, void* hip_stream) {
+  const char* fn = mem == Mem::Device ? "admm_get_cone_report_device" : "admm_get_cone_report";
+  if (!h) return fail(ADMM_ERR_INVALID, "NULL handle");
+  if (!max_violation && !n_active && !lam) return fail(ADMM_ERR_INVALID, std::string(fn) + ": at least one output must be given");
+  int rc;
+  if ((rc = require_kind(h, ZKind::Cone, fn))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  CallerIO io(h, fn, mem, hip_stream);
+  const size_t bsz = sizeof(double) * (size_t)h->batch, csz = sizeof(int32_t) * (size_t)h->batch;
+  if ((rc = io.check_ptr(max_violation, bsz, "max_violation")) ||
+      (rc = io.check_ptr(n_active, csz, "n_active", sizeof(int32_t), "int32 entries")) || (rc = io.check_ptr(lam, bsz * h->N, "lam")))
+    return rc;
+  if (!h->cone_out && (rc = dalloc(h, &h->cone_out, (size_t)h->pitch))) return rc;
+  if (!h->cone_cnt && (rc = dalloc(h, &h->cone_cnt, (size_t)h->pitch))) return rc;
+  if (lam && !h->cone_lam && (rc = dalloc(h, &h->cone_lam, (size_t)h->N * h->pitch, true))) return rc;
+  if ((rc = ensure_w(h)) || (rc = ensure_zy(h))) return rc;      // w of the last x-update; the state as the (z, y) pair
+  if ((rc = io.begin())) return rc;
+  admm::launch_cone_report(h->stream, h->w, h->y, h->cone_c, h->cone_p, h->cone_g, h->cone_out, h->cone_cnt, lam ? h->cone_lam : nullptr,
+                           h->fac.rho, h->N, h->nb, h->m, h->cone_nh, h->pitch, h->batch, h->cone_perqp);
+  HIP_TRY(hipGetLastError());
+  if (max_violation && (rc = io.copy_out(max_violation, h->cone_out, bsz))) return rc;
+  if (n_active && (rc = io.copy_out(n_active, h->cone_cnt, csz))) return rc;
+  if (lam && (rc = download_transposed(h, mem, h->cone_lam, lam, h->N))) return rc;
   return io.finish();
 }
 
@@ -244,6 +345,39 @@ int admm_get_halfspace_report(admm_handle* h, double* max_violation, int32_t* n_
 }
 int admm_get_halfspace_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream) {
   return halfspace_report_common(h, max_violation, n_active, lam, Mem::Device, hip_stream);
+}
+
+int admm_set_cone(admm_handle* h, const double* c, const double* apex, const double* gamma) {
+  return set_cone_common(h, c, apex, gamma, Mem::Host, nullptr);
+}
+int admm_set_cone_device(admm_handle* h, const double* c, const double* apex, const double* gamma, void* hip_stream) {
+  return set_cone_common(h, c, apex, gamma, Mem::Device, hip_stream);
+}
+
+// the cones in force, in the caller's order (c[b][k][i], apex[b][k][i], gamma[b][k]; one "QP" in the shared form)
+int admm_get_cone(admm_handle* h, double* c, double* apex, double* gamma) {
+  if (!h || !c || !apex || !gamma) return fail(ADMM_ERR_INVALID, "NULL argument");
+  int rc;
+  if ((rc = require_kind(h, ZKind::Cone, "admm_get_cone"))) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const int rows = h->N * h->cone_nh;
+  if (h->cone_perqp) {
+    if ((rc = download_transposed(h, Mem::Host, h->cone_c, c, rows)) || (rc = download_transposed(h, Mem::Host, h->cone_p, apex, rows)))
+      return rc;
+    return download_transposed(h, Mem::Host, h->cone_g, gamma, h->N);
+  }
+  HIP_TRY(hipMemcpyAsync(c, h->cone_c, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(apex, h->cone_p, sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(gamma, h->cone_g, sizeof(double) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return ADMM_OK;
+}
+
+int admm_get_cone_report(admm_handle* h, double* max_violation, int32_t* n_active, double* lam) {
+  return cone_report_common(h, max_violation, n_active, lam, Mem::Host, nullptr);
+}
+int admm_get_cone_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream) {
+  return cone_report_common(h, max_violation, n_active, lam, Mem::Device, hip_stream);
 }
 
 }  // extern "C"

@@ -51,6 +51,15 @@ class Problem:
     # sum_rows s_i max(lo_i - w_i, 0, w_i - hi_i) and the row's box is no longer enforced absolutely.  +inf = a hard row, 0 = its box is
     # ignored.  None = every row hard.  +inf on the control rows where unorm is finite or fuel positive.  Batch-shared dynamics only.
     soft: Optional[np.ndarray] = None
+    # one approach cone per stage:  r <= cone_g[k] s  on xi_k, the first nh state rows of block k, with e = c / |c|,
+    # s = e . (xi_k - p), r = |(xi_k - p) - s e|: axis cone_c[k], apex cone_p[k], slope cone_g[k] > 0 (the tangent of the half-angle).
+    # cone_c and cone_p are (N, nh) with cone_g (N,) -- shared by the batch -- or (batch, N, nh) with (batch, N) -- one set per QP;
+    # nh = cone_c.shape[-1], 1 <= nh <= n.  cone_c[k] = 0 exactly: no cone at that stage.  Where a stage has one for any QP, state rows
+    # 0 .. nh - 1 of the stage must have the box (-inf, inf).  All three or none; finite.  Batch-shared dynamics only; not with soft,
+    # consensus or half-spaces.  (They sit before `fuel`, which stays the last field.)
+    cone_c: Optional[np.ndarray] = None
+    cone_p: Optional[np.ndarray] = None
+    cone_g: Optional[np.ndarray] = None
     # one half-space per stage:  hs_a[k] . xi_k <= hs_b[k]  on xi_k, the first nh state rows of block k.  hs_a is
     # (N, nh) with hs_b (N,) -- shared by the batch -- or (batch, N, nh) with (batch, N) -- one set per QP; nh = hs_a.shape[-1],
     # 1 <= nh <= n.  hs_a[k] = 0 exactly: no half-space at that stage.  Where a stage has one for any QP, state rows 0 .. nh - 1 of the
@@ -97,8 +106,10 @@ class Problem:
 
     @property
     def z_kind(self) -> Optional[str]:
-        """The extension of the z-update the problem asks for: "consensus", "soft", "halfspace", or None.
+        """The extension of the z-update the problem asks for: "consensus", "soft", "halfspace", "cone", or None.
         validate() admits at most one; a fuel term and a thrust bound compose with each and are not one."""
+        if self.cone_c is not None:
+            return "cone"
         if self.hs_a is not None:
             return "halfspace"
         if self.soft is not None:
@@ -115,6 +126,8 @@ class Problem:
             rep.update(lo=np.ascontiguousarray(self.lo[start:stop]), hi=np.ascontiguousarray(self.hi[start:stop]))
         if self.hs_a is not None and np.ndim(self.hs_a) == 3:
             rep.update(hs_a=np.ascontiguousarray(self.hs_a[start:stop]), hs_b=np.ascontiguousarray(self.hs_b[start:stop]))
+        if self.cone_c is not None and np.ndim(self.cone_c) == 3:
+            rep.update({k: np.ascontiguousarray(getattr(self, k)[start:stop]) for k in ("cone_c", "cone_p", "cone_g")})
         return dataclasses.replace(self, **rep)
 
     def validate(self) -> None:
@@ -193,6 +206,11 @@ class Problem:
         if self.hs_a is not None and not hasattr(self.hs_a, "is_cuda"):
             # (CUDA tensors: what Solver.set_halfspace left here after the device form; the library has checked them on the device)
             check_halfspaces(self, self.hs_a, self.hs_b)
+        if len({self.cone_c is None, self.cone_p is None, self.cone_g is None}) != 1:
+            raise ValueError("cone_c, cone_p and cone_g must be given together")
+        if self.cone_c is not None and not hasattr(self.cone_c, "is_cuda"):
+            # (CUDA tensors: what Solver.set_cone left here after the device form; the library has checked them on the device)
+            check_cones(self, self.cone_c, self.cone_p, self.cone_g)
         if self.consensus is not None:
             G = int(self.consensus)
             if G != self.consensus or G < 1 or self.batch % G != 0:
@@ -247,6 +265,52 @@ def check_halfspaces(p, a, b) -> None:
         raise ValueError("state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with a half-space")
 
 
+def cone_form(c, apex, g, N: int, n: int, batch: int):
+    """(nh, per_qp) of cone arrays by their shapes: (N, nh) twice with (N,), or (batch, N, nh) twice with (batch, N).  ValueError
+    otherwise.  (With batch = 1 a 3-d array is the per-QP form.)"""
+    c, apex, g = np.asarray(c), np.asarray(apex), np.asarray(g)
+    if c.ndim == 2 and c.shape[0] == N and apex.shape == c.shape and g.shape == (N,):
+        per_qp = False
+    elif c.ndim == 3 and c.shape[:2] == (batch, N) and apex.shape == c.shape and g.shape == (batch, N):
+        per_qp = True
+    else:
+        raise ValueError("cone_c / cone_p / cone_g must be (N, nh) twice with (N,), or (batch, N, nh) twice with (batch, N); "
+                         f"got {c.shape}, {apex.shape} with {g.shape}")
+    nh = int(c.shape[-1])
+    if not 1 <= nh <= n:
+        raise ValueError(f"cone_c: nh = {nh} must lie in 1 .. n = {n}")
+    return nh, per_qp
+
+
+def check_cones(p, c, apex, g) -> None:
+    """The rules of Problem.cone_c / cone_p / cone_g against the rest of p (ValueError): shapes, finite entries, where c != 0 a normal
+    c.c and a positive normal slope with 1 + g^2 finite, an open box on state rows 0 .. nh - 1 of every stage that has a cone for some
+    QP."""
+    c, apex, g = (np.asarray(x, np.float64) for x in (c, apex, g))
+    nh, _ = cone_form(c, apex, g, p.N, p.n, p.batch)
+    if p.per_instance or p.lo.ndim == 3:
+        raise ValueError("approach cones need batch-shared dynamics and a batch-shared box (A, B LTI or LTV)")
+    if p.soft is not None or p.consensus is not None or p.hs_a is not None:
+        raise ValueError("approach cones cannot be combined with soft, consensus or half-spaces")
+    if not (np.all(np.isfinite(c)) and np.all(np.isfinite(apex)) and np.all(np.isfinite(g))):
+        raise ValueError("cone_c, cone_p and cone_g must be finite")
+    c3, g2 = c.reshape(-1, p.N, nh), g.reshape(-1, p.N)
+    nz = np.any(c3 != 0, axis=2)
+    tiny = np.finfo(np.float64).tiny
+    with np.errstate(over="ignore", under="ignore"):
+        nn = np.sum(c3 * c3, axis=2)
+        gg = 1.0 + g2 * g2
+    if np.any(nz & ~((nn >= tiny) & np.isfinite(nn))):
+        raise ValueError("cone_c: c.c of a stage with a cone must be a normal number (scale the axis)")
+    if np.any(nz & ~((g2 >= tiny) & np.isfinite(gg))):
+        raise ValueError("cone_g: the slope of a stage with a cone must be a positive normal number with 1 + g^2 finite")
+    active = np.any(nz, axis=0)                                            # (N,)
+    lo_x = np.broadcast_to(np.atleast_2d(p.lo), (p.N, p.nb))[:, p.m:p.m + nh]
+    hi_x = np.broadcast_to(np.atleast_2d(p.hi), (p.N, p.nb))[:, p.m:p.m + nh]
+    if np.any(lo_x[active] != -np.inf) or np.any(hi_x[active] != np.inf):
+        raise ValueError("state rows 0 .. nh - 1 must be unbounded (-inf, inf) at a stage with a cone")
+
+
 @dataclasses.dataclass
 class DeviceProblem:
     """A Problem whose arrays are fp64 torch tensors in the memory of ONE GPU (same fields, same shapes, same C order as Problem):
@@ -267,6 +331,9 @@ class DeviceProblem:
     name: str = ""
     consensus: Optional[int] = None             # Problem's field; scenario consensus has no device-memory setup (Solver refuses it)
     soft: Optional["torch.Tensor"] = None       # Problem's field; soft constraints have no device-memory setup (Solver refuses it)
+    cone_c: Optional["torch.Tensor"] = None     # Problem's fields; approach cones have no device-memory setup (Solver refuses it): the
+    cone_p: Optional["torch.Tensor"] = None     # device-memory route is Solver.set_cone with CUDA tensors
+    cone_g: Optional["torch.Tensor"] = None
     hs_a: Optional["torch.Tensor"] = None       # Problem's fields; half-spaces have no device-memory setup (Solver refuses it): the
     hs_b: Optional["torch.Tensor"] = None       # device-memory route is Solver.set_halfspace with CUDA tensors
     fuel: Optional["torch.Tensor"] = None      # Problem's field; the device entry points have no fuel term (Solver refuses it)
@@ -294,7 +361,8 @@ class DeviceProblem:
         return cls(N=p.N, A=t(p.A), B=t(p.B), Q=t(p.Q), R=t(p.R), QN=t(p.QN), x0=t(p.x0), lo=t(p.lo), hi=t(p.hi), q=t(p.q),
                    unorm=None if p.unorm is None else t(np.asarray(p.unorm, np.float64)), name=p.name,
                    fuel=None if p.fuel is None else t(np.asarray(p.fuel, np.float64)), consensus=p.consensus,
-                   soft=None if p.soft is None else t(np.asarray(p.soft, np.float64)), hs_a=t(p.hs_a), hs_b=t(p.hs_b))
+                   soft=None if p.soft is None else t(np.asarray(p.soft, np.float64)), hs_a=t(p.hs_a), hs_b=t(p.hs_b),
+                   cone_c=t(p.cone_c), cone_p=t(p.cone_p), cone_g=t(p.cone_g))
 
     def validate(self) -> None:
         """ValueError unless every array is a contiguous fp64 CUDA tensor on the device of x0 with Problem's shapes."""
@@ -309,6 +377,9 @@ class DeviceProblem:
         if self.hs_a is not None or self.hs_b is not None:
             raise ValueError("hs_a / hs_b: half-spaces have no device-memory setup: give a Problem with NumPy arrays "
                              "(Solver.set_halfspace takes CUDA tensors)")
+        if self.cone_c is not None or self.cone_p is not None or self.cone_g is not None:
+            raise ValueError("cone_c / cone_p / cone_g: approach cones have no device-memory setup: give a Problem with NumPy arrays "
+                             "(Solver.set_cone takes CUDA tensors)")
         dev =self.x0.device if torch.is_tensor(self.x0) else None
         for name in ("A", "B", "Q", "R", "QN", "x0", "lo", "hi", "q", "unorm"):
             a = getattr(self, name)
@@ -505,6 +576,96 @@ def cw_keepout(N: int = 40, batch: int = 6, radius: Optional[float] = None, free
         b[:, N - free_tail:] = 0.0
     return dataclasses.replace(p, hs_a=a, hs_b=b, fuel=None if fuel is None else np.float64(fuel),
                                name=f"cw_keepout_N{N}_b{batch}")
+
+
+def plain_solution(p: Problem, rho: float = 0.5, alpha: float = 1.6, eps: float = 1e-9, max_iter: int = 20000) -> np.ndarray:
+    """(batch, L): z of p's QPs with their box, thrust ball, fuel term and q -- no extension of the z-update -- by the ADMM of
+    DESIGN.md §2 in NumPy (Riccati x-update, batch-shared dynamics), run until ||w - z|| and rho ||z+ - z|| fall below
+    eps sqrt(L) for every QP.  What a generator needs of the unconstrained-by-its-extension trajectory; not a solver to time."""
+    N, n, m, nb, L = p.N, p.n, p.m, p.nb, p.L
+    A = np.broadcast_to(p.A, (N, n, n))
+    B = np.broadcast_to(p.B, (N, n, m))
+    P = p.QN + rho * np.eye(n)
+    K, Sinv = np.empty((N, m, n)), np.empty((N, m, m))
+    for k in range(N - 1, -1, -1):
+        PB = P @ B[k]
+        S = p.R + rho * np.eye(m) + B[k].T @ PB
+        Sinv[k] = np.linalg.inv(S)
+        K[k] = Sinv[k] @ (PB.T @ A[k])
+        P = p.Q + rho * np.eye(n) + A[k].T @ P @ A[k] - K[k].T @ S @ K[k]
+        P = 0.5 * (P + P.T)
+    lo = np.broadcast_to(np.atleast_2d(p.lo), (N, nb)).reshape(L)
+    hi = np.broadcast_to(np.atleast_2d(p.hi), (N, nb)).reshape(L)
+    un = np.full(N, np.inf) if p.unorm is None else np.broadcast_to(np.asarray(p.unorm, np.float64), (N,))
+    kap = (np.zeros(N) if p.fuel is None else np.broadcast_to(np.asarray(p.fuel, np.float64), (N,))) / rho
+    soc = np.isfinite(un) | (kap > 0)
+    batch = p.batch
+    z, y = np.zeros((batch, L)), np.zeros((batch, L))
+    for _ in range(max_iter):
+        g = (-rho * (z - y) + (0.0 if p.q is None else p.q)).reshape(batch, N, nb)
+        d, t = np.empty((N, batch, m)), np.zeros((batch, n))
+        for k in range(N - 1, -1, -1):
+            pk = g[:, k, m:] + t
+            h = pk @ B[k] + g[:, k, :m]
+            d[k] = h @ Sinv[k].T
+            t = pk @ A[k] - h @ K[k]
+        w, x = np.empty((batch, N, nb)), np.array(p.x0, np.float64)
+        for k in range(N):
+            u = -(x @ K[k].T) - d[k]
+            x = x @ A[k].T + u @ B[k].T
+            w[:, k, :m], w[:, k, m:] = u, x
+        w = w.reshape(batch, L)
+        v = alpha * w + (1.0 - alpha) * z + y
+        zn = np.minimum(np.maximum(v, lo), hi).reshape(batch, N, nb)
+        if soc.any():
+            vu = v.reshape(batch, N, nb)[:, :, :m]
+            nrm = np.sqrt(np.sum(vu * vu, axis=2))
+            tt = np.minimum(un, np.maximum(nrm - kap, 0.0))
+            zn[:, soc, :m] = (vu * np.where(nrm > tt, tt / np.where(nrm > 0, nrm, 1.0), 1.0)[:, :, None])[:, soc]
+        zn = zn.reshape(batch, L)
+        r, s = np.sqrt(np.sum((w - zn) ** 2, axis=1)), rho * np.sqrt(np.sum((zn - z) ** 2, axis=1))
+        z, y = zn, v - zn
+        if max(r.max(), s.max()) <= eps * np.sqrt(L):
+            break
+    return z
+
+
+def cw_approach(N: int = 40, batch: int = 6, pull: float = 0.05, free_tail: int = 3, thrust_norm: bool = False,
+                fuel: Optional[float] = None, seed0: int = SEED0) -> Problem:
+    """cw_rendezvous with an approach cone per stage and QP on the position rows, feasible by construction: with
+    the plain problem's solution (plain_solution) at hand, the axis of QP b is the direction of its initial position, the apex
+    lies behind the target by 1.5 x (the deepest overshoot along the axis) + 0.1 x (the initial range), and the slope is
+    1.05 x max_k r_k / s_k of that solution, which is then strictly inside.  A linear cost q = -pull t^ on the position rows, t^ a
+    fixed unit vector orthogonal to the axis, pulls the trajectory into the cone's surface.  The last `free_tail` stages carry no
+    cone (c = 0, apex = 0, slope 1).  thrust_norm / fuel: the thrust ball instead of the input box, and the minimum-fuel term on
+    top of it (2 pi / N is cw_rendezvous_fuel's weight)."""
+    p = cw_rendezvous(N=N, batch=batch, seed0=seed0, thrust_norm=thrust_norm or fuel is not None)
+    if fuel is not None:
+        p = dataclasses.replace(p, fuel=np.float64(fuel))
+    nh = 3
+    X = plain_solution(p).reshape(batch, N, p.nb)[:, :, p.m:p.m + nh]
+    rng0 = np.sqrt(np.sum(p.x0[:, :nh] ** 2, axis=1))
+    e = p.x0[:, :nh] / rng0[:, None]
+    along = np.einsum("bki,bi->bk", X, e)
+    back = 1.5 * np.maximum(-along.min(axis=1), 0.0) + 0.1 * rng0
+    apex = -back[:, None] * e
+    dl = X - apex[:, None, :]
+    s = np.einsum("bki,bi->bk", dl, e)
+    r = np.sqrt(np.maximum(np.sum(dl * dl, axis=2) - s * s, 0.0))
+    gam = 1.05 * (r / s)[:, :N - free_tail].max(axis=1)
+    # t^: the unit vector of e x z^ (e x x^ for an axis along z^), orthogonal to the axis
+    ref = np.where((np.abs(e[:, 2]) < 0.999)[:, None], np.array([0.0, 0.0, 1.0]), np.array([1.0, 0.0, 0.0]))
+    that = np.cross(e, ref)
+    that /= np.sqrt(np.sum(that * that, axis=1))[:, None]
+    q = np.zeros((batch, N, p.nb))
+    q[:, :, p.m:p.m + nh] = -pull * that[:, None, :]
+    c = np.repeat(e[:, None, :], N, axis=1)
+    ap = np.repeat(apex[:, None, :], N, axis=1)
+    g = np.repeat(gam[:, None], N, axis=1)
+    if free_tail > 0:
+        c[:, N - free_tail:], ap[:, N - free_tail:], g[:, N - free_tail:] = 0.0, 0.0, 1.0
+    return dataclasses.replace(p, q=q.reshape(batch, p.L), cone_c=c, cone_p=ap, cone_g=g,
+                               name=f"cw_approach_N{N}_b{batch}" + ("_fuel" if p.fuel is not None else ""))
 
 
 def cw_rendezvous_scenarios(N: int = 1000, groups: int = 1, group_size: int = 8, spread: float = 0.05, seed0: int = SEED0,

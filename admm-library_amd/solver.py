@@ -104,6 +104,14 @@ _SIGNATURES = {
     "admm_get_halfspace": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "admm_get_halfspace_report": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p]),
     "admm_get_halfspace_report_device": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p, C.c_void_p]),
+    # one approach cone per stage (ADMM_HIP_HAS_CONE): a second-order cone on the first nh state rows of every block
+    "admm_setup_cone": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), c_double_p, c_double_p, c_double_p,
+                                  c_double_p, C.c_int32, C.c_int32]),
+    "admm_set_cone": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "admm_set_cone_device": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p, C.c_void_p]),
+    "admm_get_cone": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "admm_get_cone_report": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p]),
+    "admm_get_cone_report_device": (C.c_int, [C.c_void_p, c_double_p, c_int32_p, c_double_p, C.c_void_p]),
     # device-memory forms (ABI v9): array pointers in the handle's GPU memory, the caller's hipStream_t last
     "admm_setup_device": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(CProblem), C.POINTER(COptions), C.c_void_p]),
     "admm_update_problem_device": (C.c_int, [C.c_void_p, C.POINTER(CProblem), C.c_void_p]),
@@ -302,6 +310,17 @@ class HalfspaceReport:
     lam: object = None
 
 
+@dataclasses.dataclass
+class ConeReport:
+    """Solver.cone_report(): per QP, max_violation = max_k (r_k - g_k s_k)+ / sqrt(1 + g_k^2) on w of the last
+    x-update (the distance of w_xi from its cone), n_active = stages with a cone whose y_xi is not zero (int32), and with
+    multipliers=True lam (batch, N) = rho |y_xi|_2, the size of the stage's multiplier (0 where the stage has no cone).  NumPy
+    arrays, or CUDA tensors with device=True."""
+    max_violation: object
+    n_active: object
+    lam: object = None
+
+
 class Solver:
     """One handle = one batch of QPs on one GPU.
 
@@ -341,7 +360,11 @@ class Solver:
             keep["fuel"] = None if problem.fuel is None else _abi.marshal_fuel(problem)
             head = (C.byref(self._h), C.byref(cp), C.byref(co))
             kind = problem.z_kind                # (validate() has admitted at most one extension of the z-update)
-            if kind == "halfspace":
+            if kind == "cone":
+                keep["cone_c"], keep["cone_p"], keep["cone_g"], nh, per_qp = _abi.marshal_cone(problem)
+                rc = self._lib.admm_setup_cone(*head, dptr(keep["fuel"]), dptr(keep["cone_c"]), dptr(keep["cone_p"]), dptr(keep["cone_g"]),
+                                               nh, int(per_qp))
+            elif kind == "halfspace":
                 keep["hs_a"], keep["hs_b"], nh, per_qp = _abi.marshal_halfspace(problem)
                 rc = self._lib.admm_setup_halfspace(*head, dptr(keep["fuel"]), dptr(keep["hs_a"]), dptr(keep["hs_b"]), nh, int(per_qp))
             elif kind == "soft":
@@ -364,6 +387,8 @@ class Solver:
                 raise ValueError("soft constraints are not supported on time-sharded handles")
             if problem.hs_a is not None:
                 raise ValueError("half-spaces are not supported on time-sharded handles")
+            if problem.cone_c is not None:
+                raise ValueError("approach cones are not supported on time-sharded handles")
             rank, nranks, fn = timeshard
             self._exchange = fn                     # the C side calls it for as long as the handle lives
             _check(self._lib, self._lib.admm_setup_timeshard(C.byref(self._h), C.byref(cp), C.byref(co), int(rank), int(nranks),
@@ -450,6 +475,8 @@ class Solver:
                 problem = self._keep_soft(problem)
             if problem.hs_a is not None or getattr(self.problem, "hs_a", None) is not None:
                 problem = self._keep_halfspace(problem)
+            if problem.cone_c is not None or getattr(self.problem, "cone_c", None) is not None:
+                problem = self._keep_cone(problem)
             cp, keep = _abi.marshal_problem(problem, self._row_major)        # (validates)
             t0 = time.perf_counter()
             _check(self._lib, self._lib.admm_update_problem(self._h, C.byref(cp)))
@@ -602,6 +629,75 @@ class Solver:
         lam = np.empty((self.batch, N)) if multipliers else None
         _check(self._lib, self._lib.admm_get_halfspace_report(self._h, dptr(mx), iptr(cnt), dptr(lam)))
         return HalfspaceReport(mx, cnt, lam)
+
+    def _keep_cone(self, problem):
+        """update_problem on a handle with approach cones: the handle's cones stay in force (admm_update_problem); the problem that
+        becomes self.problem carries them, and the new box is validated against them."""
+        if getattr(self.problem, "cone_c", None) is None:
+            raise ValueError("approach cones cannot be added to a handle: set up a new Solver")
+        cur = self.cone()
+        if problem.cone_c is not None and not all(np.array_equal(np.asarray(getattr(problem, k), np.float64), v)
+                                                  for k, v in zip(("cone_c", "cone_p", "cone_g"), cur)):
+            raise ValueError("update_problem keeps the handle's approach cones: change them with set_cone")
+        return dataclasses.replace(problem, cone_c=cur[0], cone_p=cur[1], cone_g=cur[2])
+
+    def _cone_form(self):
+        """(nh, per_qp) of the handle's cones; AdmmError on a handle without."""
+        if getattr(self.problem, "cone_c", None) is None:
+            raise AdmmError(1, "the handle has no approach cones (set Problem.cone_c / cone_p / cone_g)")
+        return tuple(self.problem.cone_c.shape)[-1], len(self.problem.cone_c.shape) == 3
+
+    def set_cone(self, c, apex, gamma):
+        """New cones (axis c, apex, slope gamma: the form and nh of Problem.cone_c / cone_p / cone_g) on a handle set up with them;
+        the state is kept as a warm start (admm_set_cone).  NumPy arrays, or CUDA tensors on the handle's GPU (admm_set_cone_device,
+        ordered on torch's current stream; self.problem then keeps the tensors).  A refused call changes nothing."""
+        nh, per_qp = self._cone_form()
+        N = self.problem.N
+        sc, sg = ((self.batch, N, nh), (self.batch, N)) if per_qp else ((N, nh), (N,))
+        if _on_gpu(c) or _on_gpu(apex) or _on_gpu(gamma):
+            dev = f"cuda:{self._device()}"
+            check_device_tensor("c", c, dev, sc)
+            check_device_tensor("apex", apex, dev, sc)
+            check_device_tensor("gamma", gamma, dev, sg)
+            _check(self._lib, self._lib.admm_set_cone_device(self._h, _tptr(c), _tptr(apex), _tptr(gamma), _stream(dev)))
+            self.problem = dataclasses.replace(self.problem, cone_c=c, cone_p=apex, cone_g=gamma)
+            return
+        c, apex, gamma = (np.ascontiguousarray(x, np.float64) for x in (c, apex, gamma))
+        if c.shape != sc or apex.shape != sc or gamma.shape != sg:
+            raise ValueError(f"set_cone keeps the handle's form: expected shapes {sc}, {sc} and {sg}, got {c.shape}, {apex.shape} and {gamma.shape}")
+        cand = dataclasses.replace(self.problem, cone_c=c, cone_p=apex, cone_g=gamma)
+        cand.validate()
+        _check(self._lib, self._lib.admm_set_cone(self._h, dptr(c), dptr(apex), dptr(gamma)))
+        self.problem = cand
+        self._warn()
+
+    def cone(self):
+        """(c, apex, gamma): the cones in force, in the shapes of Problem.cone_c / cone_p / cone_g (admm_get_cone)."""
+        nh, per_qp = self._cone_form()
+        N = self.problem.N
+        c, apex = (np.empty((self.batch, N, nh) if per_qp else (N, nh)) for _ in range(2))
+        g = np.empty((self.batch, N) if per_qp else (N,))
+        _check(self._lib, self._lib.admm_get_cone(self._h, dptr(c), dptr(apex), dptr(g)))
+        return c, apex, g
+
+    def cone_report(self, multipliers: bool = False, device: bool = False) -> ConeReport:
+        """admm_get_cone_report: per QP the largest violation of a cone by w, the number of stages whose cone moved their rows and,
+        with multipliers=True, rho |y_xi| per stage (batch, N), computed on the device.  device=True returns CUDA tensors through
+        admm_get_cone_report_device, ordered on torch's current stream."""
+        N = self.problem.N
+        if device:
+            import torch
+            dev = f"cuda:{self._device()}"
+            mx = torch.empty(self.batch, dtype=torch.float64, device=dev)
+            cnt = torch.empty(self.batch, dtype=torch.int32, device=dev)
+            lam = torch.empty((self.batch, N), dtype=torch.float64, device=dev) if multipliers else None
+            _check(self._lib, self._lib.admm_get_cone_report_device(self._h, _tptr(mx), C.cast(C.c_void_p(cnt.data_ptr()), c_int32_p),
+                                                                   _tptr(lam), _stream(dev)))
+            return ConeReport(mx, cnt, lam)
+        mx, cnt = np.empty(self.batch), np.empty(self.batch, np.int32)
+        lam = np.empty((self.batch, N)) if multipliers else None
+        _check(self._lib, self._lib.admm_get_cone_report(self._h, dptr(mx), iptr(cnt), dptr(lam)))
+        return ConeReport(mx, cnt, lam)
 
     def set_rho(self, rho: float):
         _check(self._lib, self._lib.admm_set_rho(self._h, float(rho)))

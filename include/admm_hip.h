@@ -347,6 +347,47 @@ int admm_get_halfspace(admm_handle* h, double* a, double* b);
 int admm_get_halfspace_report(admm_handle* h, double* max_violation, int32_t* n_active, double* lam);
 int admm_get_halfspace_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream);
 
+/* One approach cone per stage (new symbols, announced by ADMM_HIP_HAS_CONE -- no struct or signature changed, ABI
+ * version unchanged): stage k constrains xi_k, the first nh state rows of block k = (u_k, x_{k+1}), 1 <= nh <= n, to the second-order
+ * cone of axis c_k, apex p_k and slope gamma_k > 0 (the tangent of the half-angle):
+ *
+ *     r <= gamma s,     e = c / |c|,   s = e'(xi - p),   r = |(xi - p) - s e|_2
+ *
+ * c, apex, gamma are C order, c[b][k][i], apex[b][k][i], gamma[b][k]: shared by the batch (per_instance = 0: N nh, N nh and N
+ * doubles) or one set per QP (per_instance != 0: batch N nh, batch N nh and batch N).  c_k = 0 exactly: the stage has no cone and its
+ * rows keep their box.  Where a stage has a cone for any QP, state rows 0 .. nh - 1 of that stage must have the box (-inf, inf) (with
+ * stage_bounds = 0: of the one block).  Every entry must be finite; where c_k != 0, c_k'c_k must be a normal number and gamma_k a
+ * positive normal number with 1 + gamma_k^2 finite.  Only the z-update changes: the rows v = w^ + y of a stage with a cone get their
+ * Euclidean projection onto it -- v itself inside, the apex where v lies in the polar cone, else the nearest point of the surface
+ * (csrc/admm_prox.hpp, cone_project) -- independent of rho.  The cone is convex: no re-linearisation.  The other state rows and the
+ * control rows keep what they have (box, ball, fuel).
+ *
+ * admm_setup_cone: admm_setup_fuel (fuel may be NULL) with the cones, under the rules of admm_setup_halfspace: ADMM_ERR_INVALID for
+ *   nh out of range, a NULL array, a non-finite entry, an unusable c'c or gamma, a closed box under a cone; ADMM_ERR_UNSUPPORTED for
+ *   time_varying = 2 or a precision_mode other than ADMM_PRECISION_FP64; refused before a device is looked for.  The handle runs the
+ *   unfused one-lane fp64 path, the state is always the (z, y) pair, and everything that works on a half-space handle works on it.
+ *   admm_update_problem* keeps the cones and re-checks the open-box rule.  ADMM_ERR_UNSUPPORTED on such a handle: admm_mpc_advance*,
+ *   admm_probe_infeasibility*, admm_profile with fused_path != 0.
+ * admm_set_cone: replace c, apex, gamma (same form, same nh) between iterations; the state is kept as a warm start.  Every check
+ *   comes first: a refused call changes nothing.  ADMM_ERR_INVALID on a handle set up without cones.
+ * admm_set_cone_device: the arrays are device memory of the handle's GPU, under the rules of admm_set_state_device; the per-QP arrays
+ *   are checked on the device.  A captured graph survives either call: the cones keep their device addresses.
+ * admm_get_cone: the cones in force, in the caller's order and form.
+ * admm_get_cone_report: per QP (batch entries; any pointer may be NULL, not all):
+ *     max_violation = max_k (r_k - gamma_k s_k)+ / sqrt(1 + gamma_k^2)  on w, the dynamics-feasible iterate of the last x-update
+ *     n_active      = number of stages with a cone whose y_xi has a nonzero entry
+ *     lam[b][k]     = rho |y_xi|_2  (batch N doubles), the size of the stage's multiplier.  0 at a stage without a cone.
+ * admm_get_cone_report_device: the outputs are device memory of the handle's GPU, under the rules of admm_get_certificate_device
+ *   (n_active: 4-byte alignment). */
+#define ADMM_HIP_HAS_CONE 1
+int admm_setup_cone(admm_handle** out, const admm_problem* p, const admm_options* o, const double* fuel, const double* c,
+                    const double* apex, const double* gamma, int32_t nh, int32_t per_instance);
+int admm_set_cone(admm_handle* h, const double* c, const double* apex, const double* gamma);
+int admm_set_cone_device(admm_handle* h, const double* c, const double* apex, const double* gamma, void* hip_stream);
+int admm_get_cone(admm_handle* h, double* c, double* apex, double* gamma);
+int admm_get_cone_report(admm_handle* h, double* max_violation, int32_t* n_active, double* lam);
+int admm_get_cone_report_device(admm_handle* h, double* max_violation, int32_t* n_active, double* lam, void* hip_stream);
+
 /* Warm start / test hook: overwrite device state.  Any pointer may be NULL
  * (left unchanged).  Each is L*batch and must be finite (ADMM_ERR_INVALID otherwise, nothing uploaded). */
 int admm_set_state(admm_handle* h, const double* w, const double* z, const double* y);
