@@ -23,6 +23,17 @@ probe (sep against -eps, the open-row magnitude against eps |mu|_inf); `unclear`
 number against +inf in sep and defect) that are neither clearly nonzero nor zero by construction: there `defect` is a quotient of two
 rounding errors, and the probe's read-out says so per QP (defect_clear).  `soft_rows` counts, per soft report, the finite-weight rows
 that are neither clearly outside their box, nor clearly inside, nor exactly on a bound with |y| clear of s / rho.
+
+Half-spaces and approach cones (tests/_halfspace_ref.py, tests/_cone_ref.py: solve, prox, report; the payload is the problem's hs_* /
+cone_* fields, replaced by set_halfspace / set_cone under the checks of halfspace_stages / cone_stages and the open-box rule, kept by
+update_problem under the open-box rule).  Their reports count EXACT decisions -- lam > 0 of a plane, y_xi != 0 of a cone (a stage
+inside its cone has y_xi = 0 exactly) -- so the model keeps, per (QP, stage), whether rounding could flip the one the state holds.
+The unclear-stage rule: after every call that ends on a z-update a stage is marked when that update's input v_xi = z_xi + y_xi lies
+within 1e-6 max(1, |v_xi|_2) of the boundary -- |a . v - b| / |a| for a plane, |r - g s| / sqrt(1 + g^2) for a cone; the marks stay
+until the next z-update, and set_state with a y clears them (the caller's y is exact on both sides).  At a report a stage with a
+plane / cone is unclear when it is marked or when 0 < |lam| <= 1e-6 max(1, rho |y|_inf of its QP).  `plane_stages` receives, per
+report, (stages with a plane / cone, unclear stages); `z_stage_kinds` the stage kinds of the z-updates the model ran (a half-space
+handle: (active, satisfied, no plane) of the last z-update of every call; a cone handle: (inside, apex, surface, no cone) of each).
 """
 import dataclasses
 
@@ -32,7 +43,9 @@ import admm_ref as ar
 import oracle_c as oc
 import _cert_ref as cr
 import _consensus_ref as cs
+import _cone_ref as cn
 import _fuel_ref as fr
+import _halfspace_ref as hr
 import _infeas_ref as ir
 import _soft_ref as sr
 from admm_library_amd import mpc
@@ -46,6 +59,9 @@ class Refused(Exception):
     def __init__(self, code, why=""):
         super().__init__(f"refused ({code}): {why}")
         self.code = code
+
+
+_REFS = {"soft": sr, "consensus": cs, "halfspace": hr, "cone": cn}
 
 
 class HandleModel:
@@ -62,13 +78,16 @@ class HandleModel:
         self.resid = None            # (r, s, nw, nz, ny) of the last residual-evaluating iteration
         self.info = None             # dict of the last solve
         self.alternating = alternating
-        self.fused = fused and problem.soft is None and problem.consensus is None    # (such handles run the unfused path only)
+        self.fused = fused and problem.z_kind is None                # (a handle with an extension of the z-update runs the unfused path only)
         self.pair_form = True        # the state is held as the (z, y) pair (admm_profile modes 2 / 3 then add one iteration)
         self.iterations = 0          # applied since set-up
         self.margins = []
         self.probes = 0              # probes so far
         self.unclear = []            # (probe, what, QP, value, rounding scale) of a zero / nonzero decision that rounding could flip
         self.soft_rows = []          # per soft report: (rows with a finite weight, rows of none of the three kinds)
+        self.plane_stages = []       # per half-space / cone report: (stages with a plane / cone, unclear stages)
+        self.z_stage_kinds = []      # stage kinds at the z-updates of a half-space / cone handle (the module docstring)
+        self._edge = np.zeros((B, problem.N), bool)      # (QP, stage): the last z-update's input lay on the boundary, to rounding
         self._subs = None
         self._it = 0
         self._status = np.zeros(B, np.int32)
@@ -93,8 +112,16 @@ class HandleModel:
                     for b in range(self.p.batch)]
             self.w, self.z, self.y = (np.concatenate([o[k_] for o in outs]) for k_ in ("w", "z", "y"))
         elif self.p.z_kind is not None:
-            o = (sr if self.p.soft is not None else cs).solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw)
+            more, lv = {}, []
+            if self.p.z_kind == "halfspace":
+                more = dict(last_v=lv)
+            elif self.p.z_kind == "cone":
+                more = dict(kinds=self.z_stage_kinds)
+            o = _REFS[self.p.z_kind].solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw, **more)
             self.w, self.z, self.y = o.w, o.z, o.y
+            if lv:
+                self.z_stage_kinds.append(tuple(int(x.sum()) for x in hr.stage_kinds(self.p, lv[0])))
+            self._mark_edges()
         elif self.p.fuel is not None:
             o = fr.solve(self.p, rho=self.rho, z0=self.z, y0=self.y, **kw)
             self.w, self.z, self.y = o.w, o.z, o.y
@@ -129,7 +156,7 @@ class HandleModel:
         if self.per_qp and mode != 1:
             raise Refused(UNSUPPORTED, "per-instance dynamics: mode 1 only")
         if self.p.z_kind is not None and mode != 0:
-            raise Refused(UNSUPPORTED, "soft and scenario-consensus handles run the unfused path only")
+            raise Refused(UNSUPPORTED, "a handle with an extension of the z-update runs the unfused path only")
         k = {0: iters, 1: iters, 2: 2 * iters + 1, 3: 1}[mode] + (1 if mode in (2, 3) and self.pair_form else 0)
         self._advance(k, k if residuals else 0)
         if mode == 0:
@@ -159,14 +186,20 @@ class HandleModel:
             raise Refused(UNSUPPORTED, "no standalone z kernel with per-instance bounds")
         lo, hi = self._bounds()
         un = ar.expand_unorm(p.unorm, p.N)
-        if p.fuel is not None or p.soft is not None or p.consensus is not None:
+        if p.fuel is not None or p.z_kind is not None:
             wh = self.alpha * self.w + (1.0 - self.alpha) * self.z if self.alpha != 1.0 else self.w
             v = wh + self.y
             kap = fr.expand_fuel(p.fuel, p.N) / self.rho
-            if p.soft is not None:
+            if p.z_kind == "soft":
                 zn = sr.prox(v, lo, hi, un, kap, p.m, sr.expand_soft(p.soft, p.N, p.nb) / self.rho)
-            elif p.consensus is not None:
+            elif p.z_kind == "consensus":
                 zn = cs.prox(v, lo, hi, un, kap, p.m, int(p.consensus))
+            elif p.z_kind == "halfspace":
+                zn = hr.prox(v, lo, hi, un, kap, p.m, *hr.planes(p))
+                self.z_stage_kinds.append(tuple(int(x.sum()) for x in hr.stage_kinds(p, v)))
+            elif p.z_kind == "cone":
+                zn = cn.prox(v, lo, hi, un, kap, p.m, *cn.cones(p))
+                self.z_stage_kinds.append(cn.stage_kinds(p, v))
             else:
                 zn = fr.prox(v, lo, hi, un, kap, p.m)
             yn = v - zn
@@ -177,6 +210,7 @@ class HandleModel:
         self.z, self.y = zn, yn
         self.iterations += 1
         self.pair_form = True
+        self._mark_edges()
 
     # ---- state changes ----------------------------------------------------------------------------------------------------
     def set_rho(self, rho_new):
@@ -203,6 +237,7 @@ class HandleModel:
             self.z = np.array(z, np.float64)
         if y is not None:
             self.y = np.array(y, np.float64)
+            self._edge[:] = False                # (the caller's y: the same numbers on both sides)
         if z is not None or y is not None:
             self.pair_form = True
 
@@ -228,8 +263,11 @@ class HandleModel:
             raise Refused(INVALID, "problem class changed")
         if p.soft is not None:
             self._check_soft(new, p.soft, p.fuel)              # the control-row rule against the new problem
-        # the handle's fuel weights, soft weights and groups stay in force
-        self.p = dataclasses.replace(new, fuel=p.fuel, soft=p.soft, consensus=p.consensus)
+        if p.z_kind in ("halfspace", "cone"):                  # the open-box rule, with the stages of the handle's planes / cones
+            self._check_box_open(new, self._stages(self._payload(p)[0], p.cone_g))
+        # the handle's fuel weights, soft weights, groups, planes and cones stay in force
+        self.p = dataclasses.replace(new, fuel=p.fuel, soft=p.soft, consensus=p.consensus, hs_a=p.hs_a, hs_b=p.hs_b, cone_c=p.cone_c,
+                                     cone_p=p.cone_p, cone_g=p.cone_g)
         self._subs = None
         self.pair_form = True
 
@@ -262,11 +300,113 @@ class HandleModel:
         self._check_soft(self.p, soft, self.p.fuel)
         self.p = dataclasses.replace(self.p, soft=soft.copy())
 
+    # ---- half-spaces and approach cones -----------------------------------------------------------------------------------
+    @staticmethod
+    def _payload(p):
+        return (p.hs_a, p.hs_b) if p.z_kind == "halfspace" else (p.cone_c, p.cone_p, p.cone_g)
+
+    def _stages(self, axis, gamma=None):
+        """halfspace_stages / cone_stages after the finite check: a'a (c'c) a normal number and, for a cone, gamma a positive normal
+        number with 1 + gamma^2 finite, at every (QP, stage) whose axis is not 0 -> (N,) the stages with one for some QP."""
+        a3 = np.asarray(axis, np.float64).reshape(-1, self.p.N, np.shape(axis)[-1])
+        nz = np.any(a3 != 0.0, axis=2)
+        tiny = np.finfo(np.float64).tiny
+        with np.errstate(over="ignore", under="ignore"):
+            nn = np.sum(a3 * a3, axis=2)
+            if np.any(nz & ~((nn >= tiny) & np.isfinite(nn))):
+                raise Refused(INVALID, "a'a / c'c of a stage is not a normal number")
+            if gamma is not None:
+                g2 = np.asarray(gamma, np.float64).reshape(-1, self.p.N)
+                if np.any(nz & ~((g2 >= tiny) & np.isfinite(1.0 + g2 * g2))):
+                    raise Refused(INVALID, "gamma must be a positive normal number with 1 + gamma^2 finite")
+        return np.any(nz, axis=0)
+
+    def _check_box_open(self, p, stages):
+        """The open-box rule: state rows 0 .. nh - 1 of problem p unbounded at every stage of `stages`."""
+        nh = np.shape(self._payload(self.p)[0])[-1]
+        lo = np.broadcast_to(np.atleast_2d(p.lo), (p.N, p.nb))[:, p.m:p.m + nh]
+        hi = np.broadcast_to(np.atleast_2d(p.hi), (p.N, p.nb))[:, p.m:p.m + nh]
+        if np.any(lo[stages] != -np.inf) or np.any(hi[stages] != np.inf):
+            raise Refused(INVALID, "state rows 0 .. nh - 1 must be unbounded at a stage with a plane / cone")
+
+    def _set_payload(self, kind, fields, arrays):
+        p = self.p
+        if p.z_kind != kind:
+            raise Refused(INVALID, f"the handle was not set up with {kind} data: none can be added")
+        arrays = [np.array(a, np.float64) for a in arrays]
+        if any(a.shape != np.shape(b) for a, b in zip(arrays, self._payload(p))):
+            raise Refused(INVALID, "the form and nh of set-up are kept")
+        if any(not np.all(np.isfinite(a)) for a in arrays):
+            raise Refused(INVALID, "non-finite entry")
+        self._check_box_open(p, self._stages(arrays[0], arrays[2] if kind == "cone" else None))
+        self.p = dataclasses.replace(p, **dict(zip(fields, arrays)))
+
+    def set_halfspace(self, a, b):
+        """admm_set_halfspace*: new planes, same form and nh; the state and the factor stay."""
+        self._set_payload("halfspace", ("hs_a", "hs_b"), (a, b))
+
+    def set_cone(self, c, apex, gamma):
+        """admm_set_cone*: new cones, same form and nh; the state and the factor stay."""
+        self._set_payload("cone", ("cone_c", "cone_p", "cone_g"), (c, apex, gamma))
+
+    def halfspace(self):
+        if self.p.z_kind != "halfspace":
+            raise Refused(INVALID, "the handle has no half-spaces")
+        return tuple(np.array(a, np.float64) for a in self._payload(self.p))
+
+    def cone(self):
+        if self.p.z_kind != "cone":
+            raise Refused(INVALID, "the handle has no approach cones")
+        return tuple(np.array(a, np.float64) for a in self._payload(self.p))
+
+    def _mark_edges(self):
+        """The unclear-stage rule at a z-update (the module docstring): its input is z + y of its output."""
+        p = self.p
+        if p.z_kind not in ("halfspace", "cone"):
+            return
+        nh = np.shape(self._payload(p)[0])[-1]
+        v = (self.z + self.y).reshape(p.batch, p.N, p.nb)[:, :, p.m:p.m + nh]
+        scale = np.maximum(1.0, np.sqrt(np.sum(v * v, axis=2)))
+        if p.z_kind == "halfspace":
+            A, Bv = hr.planes(p)
+            nn = np.sum(A * A, axis=2)
+            act = nn != 0.0
+            dist = np.abs(np.sum(A * v, axis=2) - Bv) / np.sqrt(np.where(act, nn, 1.0))
+        else:
+            C, Pa, G = cn.cones(p)
+            act, s, r, _, _ = cn._coords(C, Pa, v)
+            dist = np.abs(r - G * s) / np.sqrt(1.0 + G * G)
+        self._edge = act & (dist <= 1e-6 * scale)
+
+    def _report(self, kind, lam):
+        p = self.p
+        if p.z_kind != kind:
+            raise Refused(INVALID, f"the handle was not set up with {kind} data")
+        ref = hr if kind == "halfspace" else cn
+        mx, cnt, lm = ref.report(p, self.w, self.y, self.rho)
+        axis = (hr.planes(p) if kind == "halfspace" else cn.cones(p))[0]
+        norm = np.sqrt(np.sum(axis * axis, axis=2))                          # (batch, N): |a_k| / |c_k|, 0 where the stage has none
+        act = norm != 0.0
+        y_inf = np.abs(self.y).max(axis=1)[:, None]
+        small = (lm != 0.0) & (np.abs(lm) <= 1e-6 * np.maximum(1.0, self.rho * y_inf))
+        unclear = act & (self._edge | small)
+        self.plane_stages.append((int(act.sum()), int(unclear.sum())))
+        return dict(max_violation=mx, n_active=cnt, lam=lm, with_lam=bool(lam), norm=norm, unclear=unclear.sum(axis=1))
+
+    def halfspace_report(self, lam=False):
+        """admm_get_halfspace_report* -> dict(max_violation, n_active, lam, with_lam: whether the caller asks for lam, norm: |a_k| per
+        (QP, stage), unclear: per QP the stages whose exact decision rounding could flip)."""
+        return self._report("halfspace", lam)
+
+    def cone_report(self, lam=False):
+        """admm_get_cone_report*: as halfspace_report, norm = |c_k|."""
+        return self._report("cone", lam)
+
     def mpc_advance(self, plant=None, du=None, dx=None, x_meas=None, q_tail=None, tail="copy"):
         """admm_mpc_advance: u = z_u,0 + du, x0 <- x+ (the plant's, or x_meas), w, z, y and q one stage on -> dict(u=, x_next=)."""
         p = self.p
-        if p.consensus is not None:
-            raise Refused(UNSUPPORTED, "not available on a scenario-consensus handle")
+        if p.z_kind in ("consensus", "halfspace", "cone"):
+            raise Refused(UNSUPPORTED, "not available on a scenario-consensus handle, nor on one with half-spaces or approach cones")
         if self.per_qp:
             raise Refused(UNSUPPORTED, "not available with per-instance dynamics")
         if x_meas is not None and (plant is not None or dx is not None):
@@ -303,8 +443,8 @@ class HandleModel:
         span = int(span)
         if span < 1 or not (np.isfinite(eps) and eps >= 0.0):
             raise Refused(INVALID, "span must be >= 1, eps finite and >= 0")
-        if self.per_qp or self.p.consensus is not None or self.opt.precision_mode == PRECISION_MIXED:
-            raise Refused(UNSUPPORTED, "per-instance dynamics, scenario consensus and the mixed-precision mode have no probe")
+        if self.per_qp or self.p.z_kind in ("consensus", "halfspace", "cone") or self.opt.precision_mode == PRECISION_MIXED:
+            raise Refused(UNSUPPORTED, "per-instance dynamics, scenario consensus, half-spaces, approach cones and the mixed-precision mode have no probe")
         y0 = self.y.copy()
         self._advance(span, 0)                  # (the state afterwards is that of get; run(span, 0); get: a get leaves the form alone)
         ref = ir.probe(self.opened(), y0, self.y, span, eps)

@@ -14,7 +14,13 @@ A kind with ext=True also draws the receding-horizon step (admm_mpc_advance*, a 
 own, "probe": an iteration call and a read-out at once -- 65 ops with eight classes), and, on a handle with soft weights or scenario
 groups, admm_set_soft, the soft report and the consensus read-out, with the calls such handles refuse in the refused class.  There
 the ops of a class are dealt from a shuffled deck, so that three seeds hold every one.  The kinds without the flag keep their
-sequences to the bit (DIGESTS, asserted by tests/test_handle_model_host.py).
+sequences to the bit (DIGESTS, asserted by tests/test_handle_model_host.py), and so do the kinds with it that predate PLANE_KINDS
+(EXT_DIGESTS).
+
+PLANE_KINDS are handles with one half-space or one approach cone per stage: admm_set_halfspace* / admm_set_cone* among the state
+changes (stages gain and lose their plane / cone), admm_get_halfspace / admm_get_cone and the reports among the read-outs, and among
+the refused calls the receding-horizon step, the probe, the fused profile, a payload with a NaN, with a plane / cone over a closed box
+or with a slope <= 0, and an admm_update_problem that closes the box under a plane / cone in force.
 """
 import dataclasses
 
@@ -102,6 +108,50 @@ def _soft_di(seed, dN=0):
     return dataclasses.replace(p, soft=sw)
 
 
+def closed_stages(N):
+    """The stages random_planes / random_cones leave without a plane / cone and with their box closed: every fourth from stage 2."""
+    off = np.zeros(N, bool)
+    off[2::4] = True
+    return off
+
+
+def dormant_stages(N):
+    """Of the open stages, every third (from the second): no plane / cone at set-up, so that admm_set_* can give them one."""
+    out = np.zeros(N, bool)
+    out[np.flatnonzero(~closed_stages(N))[1::3]] = True
+    return out
+
+
+def _planes(base, what, nh, per_qp):
+    """base(seed, dN) with one half-space / approach cone per stage on the first nh state rows (random_planes / random_cones: the box
+    of every open stage opened, by the stage index alone, so every variant of admm_update_problem keeps the pattern), the dormant
+    stages without one.  make.full: the same problem with the payload of every open stage, which admm_set_* perturbs."""
+    def full(seed, dN=0):
+        p = base(seed, dN)
+        if what == "halfspace":
+            from test_halfspace_host import random_planes
+            return random_planes(p, nh, per_qp, seed=100 + seed)
+        from test_cone_host import random_cones
+        return random_cones(p, nh, per_qp, seed=100 + seed)
+
+    def make(seed, dN=0):
+        p = full(seed, dN)
+        d = dormant_stages(p.N)
+        if what == "halfspace":
+            a, b = np.array(p.hs_a), np.array(p.hs_b)
+            a[..., d, :] = 0.0
+            b[..., d] = 0.0
+            p = dataclasses.replace(p, hs_a=a, hs_b=b)
+        else:
+            c = np.array(p.cone_c)
+            c[..., d, :] = 0.0
+            p = dataclasses.replace(p, cone_c=c)
+        p.validate()
+        return p
+    make.full = full
+    return make
+
+
 _FIRST = dict(N=33, n=6, m=3, batch=69, with_q=False)
 _THRUST = dict(N=37, n=6, m=3, batch=9, thrust_norm=True)
 _LEAN = dict(N=45, n=6, m=3, batch=67, with_q=False, state_bounds=False)
@@ -182,7 +232,83 @@ KINDS.update({
                                 seeds=(5, 7, 8), stationary_rows=0.25),
 })
 NEW_KINDS = tuple(k for k in KINDS if k not in OLD_KINDS)
+
+# Handles with one half-space / one approach cone per stage (plane="halfspace" / "cone"): the unfused path only, no receding-horizon
+# step and no probe (seven classes, 50 ops).  Shapes follow the z kernel's geometry (the header of tests/test_gpu_cone.py: one lane =
+# two adjacent QPs, 512 columns per workgroup, chunks of whole blocks).  unclear_stages (none needs it): the largest share of a
+# report's plane / cone stages whose exact decision rounding could flip; without it the committed seeds have none.
+_PLANE = dict(ext=True, unfused=True, family="one_lane_fp64")
+_SHARED = dict(N=33, n=6, m=3, batch=69)
+_WIDE = dict(N=12, n=4, m=2, batch=514)
+for _what in ("halfspace", "cone"):
+    KINDS.update({
+        # odd batch with a pad column; chunks of 4 blocks, the last of one; rho changes inside a solve
+        f"{_what}_shared_relaxed": dict(make=_planes(_ltv(**_SHARED), _what, 3, False),
+                                        opt=dict(rho=0.3, alpha=1.6, segments=4, zrows=36, **ADAPT), plane=_what, **_PLANE),
+        # plane / cone, thrust ball and fuel shrink in one block, two blocks per chunk; admm_set_fuel and admm_set_* interleaved
+        f"{_what}_perqp_fuel": dict(make=_planes(_fuel, _what, 6 if _what == "halfspace" else 2, True),
+                                    opt=dict(rho=0.3, segments=5, zrows=18), plane=_what, fuel=True, **_PLANE),
+        # two workgroups along the batch; the payload replaced under a captured graph; the device forms and their scan kernel
+        f"{_what}_perqp_graph": dict(make=_planes(_ltv(**_WIDE), _what, 2, True), opt=dict(rho=0.3, segments=3, flags=F.FLAG_GRAPH),
+                                     plane=_what, device_io=True, **_PLANE),
+    })
+PLANE_KINDS = tuple(k for k in KINDS if KINDS[k].get("plane"))
+for _kind, _seeds in {"halfspace_shared_relaxed": (3, 4, 5), "halfspace_perqp_graph": (1, 2, 4), "cone_perqp_fuel": (1, 2, 4),
+                      "cone_perqp_graph": (1, 2, 15)}.items():
+    KINDS[_kind]["seeds"] = _seeds          # (picked like the margins' seeds: every op dealt, no unclear stage in any report)
 SEEDS = (1, 2, 3)
+
+# sha256 of repr(sequence(kind, seed)) of the kinds with ext=True that predate the half-space and cone kinds, taken before those existed
+EXT_DIGESTS = {
+    ("soft_box_relaxed", 2): "a79dfea7cd8c848908d5f4aba7624a0782f5ddff81b3e2c57f8b901f07a10f62",
+    ("soft_box_relaxed", 4): "9b979128716145f5aa47249af42625da98d7f4c3862f4950379303f9b5e42c33",
+    ("soft_box_relaxed", 8): "e719f4e72c72f4aa6b6b9f98f2bab311b2a74ab205fd692832b25957e1b44e31",
+    ("soft_fuel_thrust", 2): "40888f078fc73715fd582d7aaeab67645e92f8342a01668518cfbff1dde86a51",
+    ("soft_fuel_thrust", 3): "b61c8c0fc85fc83f32a9343cb97cee9947bc9d92f627e5b56a7e80ae119ade25",
+    ("soft_fuel_thrust", 4): "97482fe3cc53460b83f3d4f8318cce5b2b82592215d7ffb0876af0313d679e0b",
+    ("soft_graph", 3): "3cd28bcd60e65e2d400080b00105b4e06bac07ae9b4af61b04c636284256be57",
+    ("soft_graph", 4): "bd78ebededb92e184b834e4f8223ba5502772ba0549ac78261de9dbece3db02f",
+    ("soft_graph", 7): "e0d43bb45afaaf75bace4ad798cec812150149ea522ca7574ba74297103763c8",
+    ("consensus_G3", 1): "5c65371bcd9562f9bbc2aabe436dd41ec61eb70d5d9e858a03424ad906d380ad",
+    ("consensus_G3", 2): "14c15a3adf9e3bdda0842f7d47b68b6b6259ddd7173cf6a4cc60aeb9e9d8a891",
+    ("consensus_G3", 3): "fad0f72c403f63d26024c6d10bd0efe5d0924f3aa382055c50bdd43d0d7a45bb",
+    ("consensus_G65_fuel", 1): "de1f862854cf3832c22fee4bc623fae1a1c977dba98233900e79f9485ccc3c9f",
+    ("consensus_G65_fuel", 2): "2d7ccad980703906696ba7376c2822996d26236c03ea08fac9ebe21b356afae6",
+    ("consensus_G65_fuel", 3): "c13e76680619b3e5d02b421d26fca9ca47619c9f25ec8b3d0a6b8f6f186d361e",
+    ("consensus_wide", 1): "dab107bb75844dcc034d1a146241c5ca1415331d5e9ed8cc0263d4affa77a784",
+    ("consensus_wide", 2): "c80db634f58dcec8e6c6e236bf48892c8fbd14ffd955755a57c42652051ffa14",
+    ("consensus_wide", 3): "5e6884c1031c049e7562f4833a3c57efcd322f83cc9fcdef39ab5f02d0c7bf06",
+    ("one_lane_alt_ext", 1): "64dbe59d27d88b226f16ec2b72cfb7734f1e7187deaf63a02df47e4aa861932e",
+    ("one_lane_alt_ext", 4): "e8b21fa16c922c5a2c9ed564a419bc3f22d7c8a50ac5ef3656b0abe6689ffe4c",
+    ("one_lane_alt_ext", 6): "23e8aaaefba67083732968ceaa1dc377f30b5e0d9a29002368e2916a627f96ea",
+    ("lean_xfree_ext", 2): "c0c441bcd8d39eb718891ff8cbb39de7b55ec00b96bc1dec0c563870c2baa3aa",
+    ("lean_xfree_ext", 4): "68f50a06a31944ec14deb8bed7c6c29708e0a8d5504881dd45bb83f7ec536271",
+    ("lean_xfree_ext", 5): "03018861121ca932d021b9d49bfc84ed118bd067f159b6b313e6e09362f87331",
+    ("plain_fused_ext", 1): "3e69c3c0ba2b7963d41979bee6e4d41a0d8b00d3b159eb30c385e48aeb7dc283",
+    ("plain_fused_ext", 2): "3d8a3ec55f10893c14a35b55a193958e27b2b244130b7f2dddb7b11a473c3cb2",
+    ("plain_fused_ext", 3): "ec2ff820e13a1e1d2a11aacdfed3fadfb8a4f6009c72efea6c46295e4b69536f",
+    ("unfused_ext", 2): "618080c35e1384fa16084a090c05d1ab9aca4225da59e6201cad3739cbec32ca",
+    ("unfused_ext", 3): "07522fe7eb12860b301bbc166decdc2e41661e9e0cab87e24b383197fb0b5ebc",
+    ("unfused_ext", 4): "a6923277bd8f17c142323e43ac12d4d987100cf8770784316bb7a7027556ab63",
+    ("graph_replay_ext", 1): "229196d1923cf53b011150b62f9e404f40eaee128f4e7519a576ba6cd08d146e",
+    ("graph_replay_ext", 2): "3dd18cda917f3d997ce88dcb9c99c25c9019432c4df6c386b16f01280775fa06",
+    ("graph_replay_ext", 4): "a575facfd52c17145c686b0cc051e777382edf699f63580ddc37c2145acfd39c",
+    ("mfma_fp64_ext", 1): "b36663cf22a9c130c3fa1fbee004585ab7b55b6b18e1d4fa09694517a1a42888",
+    ("mfma_fp64_ext", 2): "24548eadcebb8a88934dccdb552da821c280143e1e7b29bb03e348a4d71ed73c",
+    ("mfma_fp64_ext", 3): "67a57f888b3fb8cbd07497864cac89c2e4140cb9da72832398bded5892d2b418",
+    ("fuel_thrust_ext", 1): "2a265cf097f0c67ce690afb3df9b3047aab0fbf64241f1544bfd04aa01900dd6",
+    ("fuel_thrust_ext", 2): "9775153e6dc7189af66c836ffb60b8ea69c638f7e5a344c4288f8840a1662ea0",
+    ("fuel_thrust_ext", 3): "de893e5870821877fe2ddd7bc4a7cd34637c27525c67c4803f0f9ecc743a2f4a",
+    ("probe_di_position_box", 1): "1f0cb5ca5da7db45736d9e21d271c0d883565c925b19c63d6399d42588492f4b",
+    ("probe_di_position_box", 2): "b04a54ceddc3bc3342985fc558ced499d8610b3debc2693a863faa0a9ff1fda0",
+    ("probe_di_position_box", 3): "4a524cbffa1328ee720849f7e825a2a28463b7ef40ab7f20b08bac9cc7724d8c",
+    ("probe_di_pinned", 1): "99178c69abe85bc70a0476ffbe5ba77e6d14f9aaa7e19a4eb090c83358feb34a",
+    ("probe_di_pinned", 2): "f26efd454c877f236c949821e24c6a77c7d76f4a81ebfd03a140b0cf0e2cd854",
+    ("probe_di_pinned", 3): "fb75ee51a3b869509693b9790a7948a726257d0de19f1054ba7d754c378d04da",
+    ("soft_probe_corridor", 5): "ad053d1f883b9de7cbb46ea5a0daf539d252f329c31f2186ca9248241df7c830",
+    ("soft_probe_corridor", 7): "239834c9dfebfef9c7093cbc8bbbc32f3b3dd3d9ac1062f335d16bc4eb95e01a",
+    ("soft_probe_corridor", 8): "3a179b2a3ff4e25f7c62d682afbc1565cf5eb978f112349b6535d97ba688f0d6",
+}
 
 # sha256 of repr(sequence(kind, seed)) of the kinds that predate ext=True, taken before the flag existed: their sequences stay as they were
 DIGESTS = {
@@ -265,7 +391,7 @@ def options(kind):
 
 def classes_of(kind):
     cfg = KINDS[kind]
-    probe = cfg.get("ext", False) and not cfg.get("consensus")                  # (a consensus handle refuses the probe)
+    probe = cfg.get("ext", False) and not cfg.get("consensus") and not cfg.get("plane")     # (such handles refuse the probe)
     return tuple(c for c in CLASSES if (c != "solve" or cfg.get("solve", True)) and (c != "probe" or probe))
 
 
@@ -285,8 +411,8 @@ def legal_ops(kind):
         "probe": [],
     }
     if cfg.get("ext"):
-        soft, cons = cfg.get("soft", False), cfg.get("consensus", False)
-        if cons:
+        soft, cons, x = cfg.get("soft", False), cfg.get("consensus", False), cfg.get("plane")
+        if cons or x:
             ops["refused"] += ["refuse_mpc", "refuse_probe"]
         else:
             ops["change"] += ["mpc_advance"] + (["mpc_advance_device"] if dev else [])
@@ -298,7 +424,12 @@ def legal_ops(kind):
             ops["refused"] += ["refuse_set_soft_neg"] + (["refuse_set_fuel_on_soft_rows"] if cfg.get("fuel") else [])
         if cons:
             ops["readout"] += ["consensus", "consensus_device"]
-        if soft or cons:
+        if x:                                                                   # x = "halfspace" / "cone"
+            ops["change"] += [f"set_{x}"] + ([f"set_{x}_device"] if dev else [])
+            ops["readout"] += [f"get_{x}", f"{x}_report", f"{x}_report_device"]
+            refusals = [f"refuse_set_{x}_closed_box", f"refuse_set_{x}_nan"] + (["refuse_set_cone_gamma"] if x == "cone" else [])
+            ops["refused"] += refusals + ["refuse_update_closed_box"] + ([r + "_device" for r in refusals] if dev else [])
+        if soft or cons or x:
             ops["refused"] += ["refuse_profile_fused"]
     return {c: ops[c] for c in classes_of(kind)}
 
@@ -400,6 +531,12 @@ def sequence(kind, seed):
             args = (k, bool(rng.integers(2)))
         elif name == "set_soft":
             args = (float(np.round(4.0 ** rng.uniform(-1.0, 1.0), 3)), int(rng.integers(1, 1 << 30)))
+        elif name in SET_PLANE:
+            args = (float(np.round(2.0 ** rng.uniform(-1.0, 1.0), 3)), int(rng.integers(1, 1 << 30)))     # a scale, the seed of the arrays
+        elif name in PLANE_REPORTS:
+            args = (bool(rng.integers(2)),)                                     # lam asked for
+        elif name.startswith(("refuse_set_halfspace_nan", "refuse_set_cone_nan", "refuse_set_cone_gamma")):
+            args = (int(rng.integers(2)),)                                      # which array holds the NaN; gamma = 0 or negative
         if cls in cost:
             used += k
         seq.append((name, args))
@@ -410,6 +547,10 @@ def problem_has_q(kind):
     return problem(kind).q is not None
 
 
+SET_PLANE = ("set_halfspace", "set_halfspace_device", "set_cone", "set_cone_device")
+PLANE_REPORTS = ("halfspace_report", "halfspace_report_device", "cone_report", "cone_report_device")
+
+
 def op_class(name, args):
     if name in ("solve", "solve_pieces"):
         return "solve"
@@ -418,7 +559,7 @@ def op_class(name, args):
     if name in ("infeasibility", "infeasibility_device"):
         return "probe"
     if name in ("get", "get_device", "residuals", "rho_per_qp", "certificate", "soft_report", "soft_report_device", "consensus",
-                "consensus_device"):
+                "consensus_device", "get_halfspace", "get_cone") + PLANE_REPORTS:
         return "readout"
     if name == "step_z":
         return "resid" if args[0] else "odd"
@@ -464,11 +605,17 @@ def materialise(kind, name, args, model, snap):
         q = p.q * (1.0 + 0.2 * rng.standard_normal(p.q.shape)) + 0.02 * rng.standard_normal(p.q.shape) if which & 2 else None
         return dict(x0=x0, q=q)
     if name == "update_problem":
-        return dict(problem=dataclasses.replace(problem(kind, args[0]), fuel=None, soft=None))     # (the handle's weights stay in force)
+        return dict(problem=dataclasses.replace(problem(kind, args[0]), **_DROP))          # (the handle's weights, planes and cones stay in force)
     if name == "refuse_update_N":
-        return dict(problem=dataclasses.replace(problem(kind, 2, dN=1), fuel=None, soft=None))
+        return dict(problem=dataclasses.replace(problem(kind, 2, dN=1), **_DROP))
+    if name == "refuse_update_closed_box":          # a finite bound on a state row under a plane / cone in force
+        new = dataclasses.replace(problem(kind, 2), **_DROP)
+        live = np.flatnonzero(np.any(np.asarray(plane_payload(p)[0]).reshape(-1, p.N, plane_nh(p)) != 0.0, axis=(0, 2)))
+        lo = np.array(new.lo, np.float64)
+        lo[live[len(live) // 2], p.m + plane_nh(p) - 1] = -5.0
+        return dict(problem=dataclasses.replace(new, lo=lo))
     if name == "refuse_update_lohi":
-        new = dataclasses.replace(problem(kind, 2), fuel=None, soft=None)
+        new = dataclasses.replace(problem(kind, 2), **_DROP)
         lo = np.array(new.lo, np.float64, order="C")                            # (reshape(-1) below must be a view)
         finite = np.flatnonzero(np.isfinite(np.asarray(new.hi).reshape(-1)))
         k = int(finite[len(finite) // 2])                                       # one bounded row in the middle of the box
@@ -527,7 +674,60 @@ def materialise(kind, name, args, model, snap):
         f = np.array(p.fuel, np.float64)
         f[SOFT_FUEL_STAGE] = 0.1
         return dict(fuel=f)
+    if name in SET_PLANE:
+        return dict(payload=new_payload(kind, *args))
+    if name.startswith(("refuse_set_halfspace", "refuse_set_cone")):
+        # the payload in force with one entry changed, in the last QP of the per-QP form
+        arrs = [np.array(a, np.float64, order="C") for a in plane_payload(p)]
+        N, nh = p.N, plane_nh(p)
+        axis = arrs[0].reshape(-1, N, nh)                                        # (views of the copies)
+        if "closed_box" in name:                    # a plane / cone on a stage whose box is closed
+            k = int(np.flatnonzero(closed_stages(N))[1])
+            axis[-1, k, 0] = 1.0
+        elif "nan" in name:
+            arrs[args[0]].reshape(-1)[arrs[args[0]].size - 1 - (N // 2) * (nh if args[0] == 0 else 1)] = np.nan
+        else:                                       # the slope of a stage with a cone
+            k = int(np.flatnonzero(np.any(axis[-1] != 0.0, axis=1))[-1])
+            arrs[2].reshape(-1, N)[-1, k] = (0.0, -0.5)[args[0]]
+        return dict(payload=tuple(arrs))
     return {}
+
+
+_DROP = dict(fuel=None, soft=None, hs_a=None, hs_b=None, cone_c=None, cone_p=None, cone_g=None)
+
+
+def plane_payload(p):
+    """(a, b) / (c, apex, gamma) of a problem with half-spaces / approach cones."""
+    return (p.hs_a, p.hs_b) if p.hs_a is not None else (p.cone_c, p.cone_p, p.cone_g)
+
+
+def plane_nh(p):
+    return int(np.shape(plane_payload(p)[0])[-1])
+
+
+def new_payload(kind, scale, seed):
+    """What admm_set_halfspace* / admm_set_cone* is given: the payload of every open stage (make.full) scaled and perturbed -- the
+    signs and the zero entries of an axis stay -- then taken away from about a third of the open stages (dormant ones among them: the
+    others of those gain one) and, in the per-QP form, from a tenth of the remaining (QP, stage) pairs."""
+    cfg = KINDS[kind]
+    full = cfg["make"].full(cfg.get("seed0", 10))
+    rng = np.random.default_rng(seed)
+    arrs = [np.array(a, np.float64) for a in plane_payload(full)]
+    N = full.N
+    gone = closed_stages(N) | (rng.uniform(size=N) < 0.3)
+    axis = arrs[0] * scale * np.clip(1.0 + 0.1 * rng.standard_normal(arrs[0].shape), 0.5, 1.5)
+    if cfg["plane"] == "halfspace":
+        b = arrs[1] * scale + 0.05 * np.sqrt(np.sum(axis * axis, axis=-1)) * rng.standard_normal(arrs[1].shape)
+        rest = [b]
+    else:
+        rest = [arrs[1] + 0.05 * rng.standard_normal(arrs[1].shape), arrs[2] * np.clip(1.0 + 0.1 * rng.standard_normal(arrs[2].shape), 0.5, 1.5)]
+    off = np.broadcast_to(gone, axis.shape[:-1]).copy()
+    if axis.ndim == 3:
+        off |= rng.uniform(size=off.shape) < 0.1
+    axis[off] = 0.0
+    if cfg["plane"] == "halfspace":
+        rest[0][off] = 0.0
+    return (axis,) + tuple(rest)
 
 
 def apply_model(model, name, args, concrete):
@@ -552,12 +752,18 @@ def apply_model(model, name, args, concrete):
         return model.set_state(**concrete)
     if name == "update_instances":
         return model.update_instances(**concrete)
-    if name in ("update_problem", "refuse_update_N", "refuse_update_lohi"):
+    if name in ("update_problem", "refuse_update_N", "refuse_update_lohi", "refuse_update_closed_box"):
         return model.update_problem(concrete["problem"])
     if name in ("set_fuel", "refuse_set_fuel_neg", "refuse_set_fuel_on_soft_rows"):
         return model.set_fuel(concrete["fuel"])
     if name in ("set_soft", "refuse_set_soft_neg"):
         return model.set_soft(concrete["soft"])
+    if name in SET_PLANE or name.startswith(("refuse_set_halfspace", "refuse_set_cone")):
+        return (model.set_halfspace if "halfspace" in name else model.set_cone)(*concrete["payload"])
+    if name in ("get_halfspace", "get_cone"):
+        return dict(payload=model.halfspace() if name == "get_halfspace" else model.cone())
+    if name in PLANE_REPORTS:
+        return dict(plane_report=(model.halfspace_report if "halfspace" in name else model.cone_report)(args[0]))
     if name in ("mpc_advance", "mpc_advance_device") or name.startswith("refuse_mpc"):
         return dict(mpc=model.mpc_advance(**concrete))
     if name in ("infeasibility", "infeasibility_device"):

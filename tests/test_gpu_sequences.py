@@ -19,6 +19,15 @@ rows of the soft kinds that stay violated, y = s / rho there: stationary_rows in
 model's z: max_violation is a difference of z and a bound (tau), the penalty a sum of weight times violation (tau x the sum of the
 finite weights), and n_violated is exact -- the host tests keep every finite-weight row of every committed report clearly outside its
 box, clearly inside, or exactly on a bound with |y| away from s / rho.
+
+The half-space and cone kinds (ops.PLANE_KINDS): admm_get_halfspace / admm_get_cone must return the last accepted payload bit for
+bit, and the bounds of the reports follow from the iterate tolerances tau_w, tau_y = 1e-10 max(1, |.|_inf) of the model's w and y,
+which bound every entry, so a stage's nh rows differ by at most sqrt(nh) tau in the 2-norm.  max_violation is the distance of w_xi
+from the half-space (a . w_xi - b)+ / |a|, or from the cone (r - g s)+ / sqrt(1 + g^2): a distance to a convex set is 1-Lipschitz in
+w_xi, and so is the maximum over the stages: sqrt(nh) tau_w.  A plane's lam_k = rho (a_k . y_xi) / |a_k|^2 changes by at most
+rho |a_k| sqrt(nh) tau_y / |a_k|^2 = rho sqrt(nh) tau_y / |a_k|; a cone's lam_k = rho |y_xi|_2 by at most rho sqrt(nh) tau_y; both are
+exactly 0 where the stage has no plane / cone.  n_active counts exact decisions (lam > 0; y_xi != 0) and is compared exactly: the
+host tests keep every stage of every committed report clear of the unclear-stage rule of tests/_handle_model.py.
 """
 import ctypes as C
 
@@ -94,9 +103,28 @@ def _apply_gpu(s, name, args, c):
         return _rc(lib, lib.admm_set_soft(s._h, _abi.dptr(np.ascontiguousarray(c["soft"], np.float64))))
     if name == "refuse_set_fuel_on_soft_rows":          # (likewise)
         return _rc(lib, lib.admm_set_fuel(s._h, _abi.dptr(np.ascontiguousarray(c["fuel"], np.float64))))
-    if name == "refuse_update_N" and getattr(s.problem, "soft", None) is not None:      # (likewise: the wrapper re-attaches the weights)
-        cp, keep = _abi.marshal_problem(c["problem"], s._row_major)
+    plane = getattr(s.problem, "z_kind", None)
+    plane = plane if plane in ("halfspace", "cone") else None
+    if (name == "refuse_update_N" and (getattr(s.problem, "soft", None) is not None or plane)) or name == "refuse_update_closed_box":
+        cp, keep = _abi.marshal_problem(c["problem"], s._row_major)        # (likewise: the wrapper re-attaches the weights, planes, cones)
         return _rc(lib, lib.admm_update_problem(s._h, C.byref(cp)))
+    if name in ops.SET_PLANE:
+        return getattr(s, "set_" + plane)(*[_tensor(a) if name.endswith("_device") else a for a in c["payload"]])
+    if name.startswith(("refuse_set_halfspace", "refuse_set_cone")):
+        if name.endswith("_device"):          # the wrapper checks shapes and devices only: the findings are the device's
+            return getattr(s, "set_" + plane)(*[_tensor(a) for a in c["payload"]])
+        return _rc(lib, getattr(lib, "admm_set_" + plane)(s._h, *[_abi.dptr(np.ascontiguousarray(a, np.float64)) for a in c["payload"]]))
+    if name in ("get_halfspace", "get_cone"):
+        return dict(payload=getattr(s, plane)())
+    if name in ops.PLANE_REPORTS:
+        r = getattr(s, plane + "_report")(multipliers=args[0], device=name.endswith("_device"))
+        if name.endswith("_device"):
+            import torch
+            torch.cuda.synchronize()
+            r = [None if a is None else a.cpu().numpy() for a in (r.max_violation, r.n_active, r.lam)]
+        else:
+            r = [r.max_violation, r.n_active, r.lam]
+        return dict(plane_report=dict(max_violation=r[0], n_active=r[1], lam=r[2]))
     if name == "soft_report":
         r = s.soft_report()
         return dict(soft_report=dict(penalty=r.penalty, max_violation=r.max_violation, n_violated=r.n_violated))
@@ -195,7 +223,7 @@ def _worst(what, ratio, tol):
     _WORST[key] = max(_WORST.get(key, 0.0), float(ratio))
 
 
-def _compare(got, ref, model, tol):
+def _compare(got, ref, model, tol, unclear_ok=False):
     for k in ("w", "z", "y"):
         if k in ref:
             _close(k, got[k], ref[k], tol)
@@ -246,6 +274,31 @@ def _compare(got, ref, model, tol):
             _worst("soft_report." + k, v, tol)
         assert all(v <= 1.0 for v in ratios.values()), ratios
         assert g["n_violated"].dtype == np.int32 and np.array_equal(g["n_violated"], r["n_violated"]), (g["n_violated"], r["n_violated"])
+    if "payload" in ref:
+        assert len(got["payload"]) == len(ref["payload"])
+        for g, r in zip(got["payload"], ref["payload"]):
+            assert g.shape == r.shape and np.array_equal(g, r), np.abs(g - r).max()
+    if "plane_report" in ref:       # the bounds of the file header
+        g, r = got["plane_report"], ref["plane_report"]
+        kind, nh = model.p.z_kind, ops.plane_nh(model.p)
+        tau_w, tau_y = (tol * max(1.0, np.abs(a).max()) for a in (model.w, model.y))
+        ratios = {"max_violation": np.abs(g["max_violation"] - r["max_violation"]).max() / (np.sqrt(nh) * tau_w)}
+        assert (g["lam"] is not None) == r["with_lam"]
+        if r["with_lam"]:
+            act = r["norm"] != 0.0
+            bound = model.rho * np.sqrt(nh) * tau_y / (np.where(act, r["norm"], 1.0) if kind == "halfspace" else 1.0)
+            assert g["lam"].shape == r["lam"].shape and not g["lam"][~act].any()
+            ratios["lam"] = (np.abs(g["lam"] - r["lam"]) / bound)[act].max() if act.any() else 0.0
+        print(f"    {kind} report, error / bound:", {k: float(f"{v:.3g}") for k, v in ratios.items()}, "active stages:",
+              int(r["n_active"].sum()), "unclear:", int(r["unclear"].sum()))
+        for k, v in ratios.items():
+            _worst(f"{kind}_report.{k}", v, tol)
+        assert all(v <= 1.0 for v in ratios.values()), ratios
+        assert g["n_active"].dtype == np.int32
+        if unclear_ok:              # (a kind that declares unclear_stages: within the QP's unclear stages)
+            assert np.all(np.abs(g["n_active"].astype(np.int64) - r["n_active"]) <= r["unclear"]), (g["n_active"], r["n_active"], r["unclear"])
+        else:
+            assert np.array_equal(g["n_active"], r["n_active"]), (g["n_active"], r["n_active"])
 
 
 def _run(kind, seed, monkeypatch, compare=True):
@@ -292,7 +345,7 @@ def _run(kind, seed, monkeypatch, compare=True):
                 continue
             print(f"  op {i} {name}{args}")
             try:
-                _compare(got, ref, model, tol)
+                _compare(got, ref, model, tol, bool(cfg.get("unclear_stages")))
             except AssertionError as e:
                 raise AssertionError(f"{kind} seed {seed}: read-out {i} {name}{args} differs from the model: {e}\n"
                                      f"first op after the last passing read-out: {last_ok + 1}\nops so far: {(seq + final)[:i + 1]}") from e

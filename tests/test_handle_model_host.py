@@ -10,8 +10,10 @@ import pytest
 
 import admm_library_amd as pkg
 import oracle_c as oc
+import _cone_ref as cn
 import _consensus_ref as cs
 import _fuel_ref as fr
+import _halfspace_ref as hr
 import _infeas_ref as ir
 import _op_sequences as ops
 import _soft_ref as sr
@@ -31,8 +33,8 @@ def _problems():
 
 
 def _oracle(p, **kw):
-    if p.fuel is not None or p.soft is not None or p.consensus is not None:
-        r = (sr if p.soft is not None else cs if p.consensus is not None else fr).solve(p, **kw)
+    if p.fuel is not None or p.z_kind is not None:
+        r = {"soft": sr, "consensus": cs, "halfspace": hr, "cone": cn, None: fr}[p.z_kind].solve(p, **kw)
         return dict(w=r.w, z=r.z, y=r.y, r=r.r, s=r.s, rho=r.rho, rho_updates=r.rho_updates, iters=r.iters, status=r.status,
                     iters_run=r.iters_run)
     return oc.solve(p, **kw)
@@ -148,13 +150,26 @@ def _ext_problems():
             "soft_fuel": ops.problem("soft_fuel_thrust")}
 
 
-EXT = ["soft", "consensus", "soft_fuel"]
+def _plane_problems():
+    from test_cone_host import random_cones
+    from test_halfspace_host import random_planes
+    base = pkg.random_ltv(N=12, n=4, m=2, batch=6, seed=3)
+    return {"halfspace": random_planes(base, 2, True), "cone": random_cones(base, 2, False),
+            "halfspace_fuel": ops.problem("halfspace_perqp_fuel"), "cone_fuel": ops.problem("cone_perqp_fuel")}
+
+
+def _all_ext():
+    return dict(_ext_problems(), **_plane_problems())
+
+
+PLANES = ["halfspace", "cone", "halfspace_fuel", "cone_fuel"]
+EXT = ["soft", "consensus", "soft_fuel"] + PLANES
 
 
 @pytest.mark.parametrize("alpha", [1.0, 1.6])
 @pytest.mark.parametrize("name", EXT)
 def test_ext_iterate_and_run_compose_to_one_reference_run(built, name, alpha):
-    p = _ext_problems()[name]
+    p = _all_ext()[name]
     m = HandleModel(p, pkg.Options(rho=0.3, alpha=alpha))
     assert not m.fused
     calls = [("iterate", 1), ("run", 4, 3), ("run", 1, 2), ("iterate", 6), ("run", 9, 1), ("run", 7, 0), ("run", 5, 5)]
@@ -173,7 +188,7 @@ def test_ext_iterate_and_run_compose_to_one_reference_run(built, name, alpha):
 @pytest.mark.parametrize("alpha", [1.0, 1.6])
 @pytest.mark.parametrize("name", EXT)
 def test_ext_step_x_then_step_z_is_one_iteration(built, name, alpha):
-    p = _ext_problems()[name]
+    p = _all_ext()[name]
     a, b = HandleModel(p, pkg.Options(rho=0.3, alpha=alpha)), HandleModel(p, pkg.Options(rho=0.3, alpha=alpha))
     a.iterate(3)
     b.iterate(3)
@@ -186,7 +201,7 @@ def test_ext_step_x_then_step_z_is_one_iteration(built, name, alpha):
 
 @pytest.mark.parametrize("name", EXT)
 def test_ext_solve_is_the_references_solve(built, name):
-    p = _ext_problems()[name]
+    p = _all_ext()[name]
     opt = pkg.Options(rho=0.3, **SOLVE, **ADAPT)
     m = HandleModel(p, opt)
     m.iterate(3)
@@ -202,7 +217,7 @@ def test_ext_solve_is_the_references_solve(built, name):
 
 @pytest.mark.parametrize("name", EXT)
 def test_ext_set_rho_reproduces_an_adaptive_solve(built, name):
-    p = _ext_problems()[name]
+    p = _all_ext()[name]
     kw = dict(rho=0.3, max_iter=40, check_interval=5, stop=False, **ADAPT)
     ref = _oracle(p, **kw)
     assert ref["rho_updates"] >= 1
@@ -323,6 +338,117 @@ def test_update_problem_keeps_soft_weights_and_groups(built):
         assert m.p.soft is p.soft and m.p.consensus == p.consensus and m.p.fuel is p.fuel and m.p.A is not p.A
 
 
+@pytest.mark.parametrize("name", PLANES)
+def test_a_refused_plane_op_leaves_the_model_alone(built, name):
+    """Every refusal of admm_set_halfspace* / admm_set_cone* (a NaN, an a'a / c'c that is no normal number, a slope that is none, a
+    closed box under the new payload, another form, a handle of another kind), of admm_update_problem (a closed box under a payload
+    in force), and the calls such a handle does not have."""
+    p = _plane_problems()[name]
+    cone = p.z_kind == "cone"
+    m = HandleModel(p, pkg.Options(rho=0.3))
+    assert not m.fused
+    m.run(3, 1)
+    before = [a.copy() for a in m.get() + m.residuals()]
+    edge = m._edge.copy()
+    pay = [np.array(a, np.float64) for a in ops.plane_payload(p)]
+    nh, N = ops.plane_nh(p), p.N
+
+    def changed(i, where, value):
+        arrs = [a.copy() for a in pay]
+        arrs[i].reshape((-1, N) + arrs[i].shape[pay[0].ndim - 1:])[where] = value
+        return arrs
+    live = int(np.flatnonzero(np.any(pay[0].reshape(-1, N, nh) != 0, axis=(0, 2)))[0])
+    bad = [changed(0, (0, live, 0), np.nan), changed(1, (0, live), np.inf), changed(0, (0, live), 1e-170 * np.eye(1, nh)[0]),
+           changed(0, (0, 2, 0), 1.0), [a[..., :-1] for a in pay] if pay[0].ndim == 2 else [a[:-1] for a in pay]]
+    if cone:
+        bad += [changed(2, (0, live), g) for g in (0.0, -0.5, 1e-310, 1e200, np.nan)]
+    setter = m.set_cone if cone else m.set_halfspace
+    calls = [((lambda arrs=arrs: setter(*arrs)), INVALID) for arrs in bad]
+    closed = dataclasses.replace(p, lo=np.array(p.lo), **ops._DROP)
+    closed.lo[live, p.m + nh - 1] = -5.0
+    other = (m.set_halfspace, (pay[0], pay[1])) if cone else (m.set_cone, (pay[0], pay[0], pay[1]))
+    calls += [(lambda: m.update_problem(closed), INVALID), (lambda: other[0](*other[1]), INVALID),
+              (lambda: (m.halfspace if cone else m.cone)(), INVALID), (lambda: (m.halfspace_report if cone else m.cone_report)(), INVALID),
+              (lambda: m.set_soft(np.ones_like(p.lo)), INVALID), (lambda: m.consensus(), INVALID),
+              (lambda: m.mpc_advance(), UNSUPPORTED), (lambda: m.infeasibility(3), UNSUPPORTED), (lambda: m.infeasibility(0), INVALID),
+              (lambda: m.profile(1, False, 1), UNSUPPORTED)]
+    for i, (call, code) in enumerate(calls):
+        with pytest.raises(Refused) as e:
+            call()
+        assert e.value.code == code, i
+    assert m.p is p and all(np.array_equal(a, b) for a, b in zip(before, m.get() + m.residuals())) and not m.margins
+    assert np.array_equal(edge, m._edge) and not m.plane_stages
+    # a stage without a plane / cone: its slope and its box are not looked at; a payload on a dormant stage is accepted
+    ok = changed(0, (slice(None), live), 0.0)
+    if cone:
+        ok[2].reshape(-1, N)[:, live] = -1.0
+    setter(*ok)
+    assert all(np.array_equal(a, b) for a, b in zip((m.cone if cone else m.halfspace)(), ok)) and m.p is not p
+    m.update_problem(closed)                    # ... and the box of that stage may close now
+
+
+def test_update_problem_keeps_planes_and_cones(built):
+    for kind in ("halfspace_perqp_fuel", "cone_shared_relaxed"):
+        m = ops.new_model(kind)
+        p = m.p
+        new = ops.materialise(kind, "update_problem", (3,), m, None)["problem"]
+        assert new.z_kind is None and new.fuel is None
+        m.update_problem(new)
+        assert all(a is b for a, b in zip(ops.plane_payload(m.p), ops.plane_payload(p))) and m.p.fuel is p.fuel and m.p.A is not p.A
+        assert m.p.z_kind == p.z_kind
+        # the open-box rule is re-checked with the stages of the payload in force, not with those of set-up
+        full = ops.new_payload(kind, 1.0, 5)
+        gained = np.any(full[0].reshape(-1, p.N, ops.plane_nh(p)) != 0, axis=(0, 2)) & ops.dormant_stages(p.N)
+        assert gained.any()
+        closed = dataclasses.replace(new, lo=np.array(new.lo))
+        closed.lo[np.flatnonzero(gained)[0], p.m] = -5.0
+        m.update_problem(closed)                # dormant at set-up: its box may close
+        m.update_problem(new)
+        (m.set_cone if p.z_kind == "cone" else m.set_halfspace)(*full)
+        with pytest.raises(Refused) as e:
+            m.update_problem(closed)
+        assert e.value.code == INVALID
+
+
+def test_the_unclear_stage_rule(built):
+    """A z-update input put on a plane, and on a cone's surface, marks the stage; one put clear of them does not; set_state with a y
+    clears the marks; a multiplier of rounding size is unclear at the report."""
+    for name in ("halfspace", "cone"):
+        p = _plane_problems()[name]
+        m = HandleModel(p, pkg.Options(rho=0.3))
+        m.iterate(2)
+        nh = ops.plane_nh(p)
+        rep = (m.halfspace_report if name == "halfspace" else m.cone_report)
+        base = rep()["unclear"].sum()
+        k = int(np.flatnonzero(np.any(np.asarray(ops.plane_payload(p)[0]).reshape(-1, p.N, nh) != 0, axis=(0, 2)))[0])
+        rows = slice(k * p.nb + p.m, k * p.nb + p.m + nh)
+        if name == "halfspace":
+            a, b = hr.planes(p)
+            on = a[0, k] * b[0, k] / (a[0, k] @ a[0, k])                    # a point of the plane
+        else:
+            c, apex, g = cn.cones(p)
+            e = c[0, k] / np.linalg.norm(c[0, k])
+            on = apex[0, k] + 1.0 * e + g[0, k] * np.array([-e[1], e[0]])   # s = 1, r = g: on the surface (nh = 2)
+        w = m.w.copy()
+        w[0, rows] = on * (1.0 + 1e-9)
+        m.set_state(w=w, y=np.zeros_like(m.y))
+        m.alpha = 1.0
+        m.step_z()                              # v = w
+        assert m._edge[0, k] and m._edge.sum() <= 1 + base
+        r = rep()
+        assert r["unclear"][0] >= 1 and m.plane_stages[-1][1] >= 1
+        m.set_state(y=m.y)
+        assert not m._edge.any()
+        w[0, rows] = on * 1.01
+        m.set_state(w=w, y=np.zeros_like(m.y))
+        m.step_z()
+        assert not m._edge[0, k]
+        y = np.zeros_like(m.y)
+        y[0, rows] = 1e-9 * (a[0, k] if name == "halfspace" else np.ones(nh))  # 0 < lam <= 1e-6: a decision rounding could flip
+        m.set_state(y=y)
+        assert rep()["unclear"][0] == 1
+
+
 # ---- the committed sequences ----------------------------------------------------------------------------------------------
 
 @functools.lru_cache(maxsize=None)
@@ -385,6 +511,112 @@ def test_the_old_kinds_keep_their_sequences():
     for kind, seed in old:
         assert not ops.KINDS[kind].get("ext")
         assert hashlib.sha256(repr(ops.sequence(kind, seed)).encode()).hexdigest() == ops.DIGESTS[kind, seed], (kind, seed)
+
+
+def test_the_ext_kinds_keep_their_sequences():
+    """The kinds with ext=True that predate the half-space and cone kinds draw what they drew: sha256 of repr(sequence(kind, seed)),
+    taken before legal_ops() and sequence() learnt the new ops."""
+    ext = [(kind, seed) for kind in ops.NEW_KINDS for seed in ops.seeds(kind)]
+    assert sorted(ops.EXT_DIGESTS) == sorted(ext) and len(ext) == 48
+    for kind, seed in ext:
+        assert ops.KINDS[kind].get("ext") and not ops.KINDS[kind].get("plane")
+        assert hashlib.sha256(repr(ops.sequence(kind, seed)).encode()).hexdigest() == ops.EXT_DIGESTS[kind, seed], (kind, seed)
+    assert list(ops.KINDS) == list(ops.OLD_KINDS + ops.NEW_KINDS + ops.PLANE_KINDS)
+
+
+def test_the_plane_kinds_are_what_they_are_for(built):
+    """Set-up facts of the half-space and cone kinds that need no GPU: the shapes behind the z kernel's geometry, the closed, open
+    and dormant stages, and the classes and ops of such a handle."""
+    assert len(ops.PLANE_KINDS) == 6 and all(len(ops.seeds(k)) == 3 for k in ops.PLANE_KINDS)
+    for kind in ops.PLANE_KINDS:
+        cfg, p = ops.KINDS[kind], ops.problem(kind)
+        assert cfg["ext"] and cfg["unfused"] and cfg["family"] == "one_lane_fp64" and p.z_kind == cfg["plane"]
+        assert "probe" not in ops.classes_of(kind) and len(ops.classes_of(kind)) == 7
+        nh, N, m = ops.plane_nh(p), p.N, p.m
+        live = np.any(np.asarray(ops.plane_payload(p)[0]).reshape(-1, N, nh) != 0, axis=(0, 2))
+        closed, dormant = ops.closed_stages(N), ops.dormant_stages(N)
+        assert np.array_equal(live, ~closed & ~dormant) and 0.25 <= dormant.sum() / (~closed).sum() <= 0.4
+        for variant in range(1, 6):             # the box of every variant: open on the open stages, closed on the others
+            q = ops.problem(kind, variant)
+            assert np.all(q.lo[~closed, m:m + nh] == -np.inf) and np.all(q.hi[~closed, m:m + nh] == np.inf)
+            assert np.all(np.isfinite(q.lo[closed, m:m + nh]).any(axis=1) | np.isfinite(q.hi[closed, m:m + nh]).any(axis=1))
+        names = {n for ns in ops.legal_ops(kind).values() for n in ns}
+        x = cfg["plane"]
+        assert {f"set_{x}", f"get_{x}", f"{x}_report", f"{x}_report_device", "refuse_mpc", "refuse_probe", "refuse_profile_fused",
+                "refuse_update_closed_box", f"refuse_set_{x}_closed_box", f"refuse_set_{x}_nan"} <= names
+        assert ("refuse_set_cone_gamma" in names) == (x == "cone") and "mpc_advance" not in names and "infeasibility" not in names
+        assert (f"set_{x}_device" in names) == (f"refuse_set_{x}_nan_device" in names) == bool(cfg.get("device_io"))
+        other = "cone" if x == "halfspace" else "halfspace"
+        assert not any(other in n for n in names)
+    for kind in ops.OLD_KINDS + ops.NEW_KINDS:  # the new ops are absent from the sequences of every other kind
+        assert not any("halfspace" in n or "cone" in n or n == "refuse_update_closed_box" for ns in ops.legal_ops(kind).values() for n in ns)
+    for x in ("halfspace", "cone"):
+        p = ops.problem(f"{x}_shared_relaxed")  # a pad column; chunks of 4 blocks, the last of one
+        opt = ops.options(f"{x}_shared_relaxed")
+        assert p.batch % 2 and opt.zrows == 4 * p.nb and p.N % 4 == 1 and p.q is not None and opt.alpha == 1.6 and opt.adapt_interval > 0
+        assert np.ndim(ops.plane_payload(p)[0]) == 2
+        p = ops.problem(f"{x}_perqp_fuel")      # two blocks per chunk beside the ball and the fuel shrink, the last of one
+        opt = ops.options(f"{x}_perqp_fuel")
+        assert opt.zrows == 2 * p.nb and p.N % 2 == 1 and p.fuel is not None and np.isfinite(p.unorm).any() and np.ndim(ops.plane_payload(p)[0]) == 3
+        p = ops.problem(f"{x}_perqp_graph")     # a second workgroup along the batch (512 columns each, two QPs per lane)
+        assert p.batch > 512 and ops.options(f"{x}_perqp_graph").flags & ops.F.FLAG_GRAPH and np.ndim(ops.plane_payload(p)[0]) == 3
+
+
+def test_the_plane_sequences_exercise_what_they_are_for(built):
+    """Over the committed seeds of the half-space and cone kinds: every new refused op refused with the code of include/admm_hip.h; in
+    every kind a stage gains and a stage loses its plane / cone; all three branches of the cone's projection at the z-updates of
+    every cone kind, active and satisfied planes at those of every half-space kind; reports with n_active > 0 and with
+    max_violation > 0, with and without lam; a rho change inside a solve of a half-space kind and of a cone kind; and no unclear
+    stage in any report (a condition on the committed seeds, as the margins are: other seeds are picked until it holds)."""
+    codes = {"refuse_mpc": UNSUPPORTED, "refuse_probe": UNSUPPORTED, "refuse_profile_fused": UNSUPPORTED, "refuse_update_closed_box": INVALID,
+             "refuse_set_cone_gamma": INVALID, "refuse_set_cone_gamma_device": INVALID}
+    for x in ("halfspace", "cone"):
+        for r in ("closed_box", "nan"):
+            codes.update({f"refuse_set_{x}_{r}": INVALID, f"refuse_set_{x}_{r}_device": INVALID})
+    seen = set()
+    rho_in_solve = {"halfspace": 0, "cone": 0}
+    for kind in ops.PLANE_KINDS:
+        cfg = ops.KINDS[kind]
+        x = cfg["plane"]
+        gained = lost = active = viol = with_lam = without = gets = 0
+        kinds = []
+        for seed in ops.seeds(kind):
+            model, log = _model_run(kind, seed)
+            share = cfg.get("unclear_stages", 0.0)
+            assert share <= 0.02 and model.plane_stages
+            assert all(bad <= share * stages for stages, bad in model.plane_stages), (kind, seed, model.plane_stages)
+            kinds += model.z_stage_kinds
+            m2 = ops.new_model(kind)            # the stages with a plane / cone before and after every accepted admm_set_*
+            for i, name, args, out, code in log:
+                if name in codes:
+                    assert code == codes[name], (kind, seed, i, name, code)
+                    seen.add(name)
+                if name in ops.SET_PLANE:
+                    assert code is None
+                    N, nh = m2.p.N, ops.plane_nh(m2.p)
+                    old = np.any(np.asarray(ops.plane_payload(m2.p)[0]).reshape(-1, N, nh) != 0, axis=(0, 2))
+                    new = ops.new_payload(kind, *args)
+                    getattr(m2, "set_" + x)(*new)
+                    now = np.any(new[0].reshape(-1, N, nh) != 0, axis=(0, 2))
+                    gained += int((now & ~old).sum())
+                    lost += int((old & ~now).sum())
+                    assert not now[ops.closed_stages(N)].any()
+                if out and "payload" in out:
+                    gets += 1
+                if out and "plane_report" in out:
+                    r = out["plane_report"]
+                    active += int(r["n_active"].sum() > 0)
+                    viol += int(r["max_violation"].max() > 0)
+                    with_lam += r["with_lam"]
+                    without += not r["with_lam"]
+                if out and "info" in out:
+                    rho_in_solve[x] += out["info"]["rho_updates"]
+        assert gained > 0 and lost > 0 and active > 0 and viol > 0 and with_lam > 0 and without > 0 and gets > 0, \
+            (kind, gained, lost, active, viol, with_lam, without, gets)
+        total = np.sum(kinds, axis=0)
+        assert len(total) == (4 if x == "cone" else 3) and (total > 0).all(), (kind, total)     # every branch, and stages without
+    assert seen == set(codes), set(codes) - seen
+    assert all(v > 0 for v in rho_in_solve.values()), rho_in_solve
 
 
 def test_the_new_kinds_are_what_they_are_for(built):
